@@ -21,11 +21,15 @@ nccl) before every step.
 (``python -m torch.distributed.run --nproc-per-node N``, rendezvous on
 127.0.0.1); under torchrun (RANK / WORLD_SIZE set) it is one of the ranks.
 
-After the timed loop rank 0 (N = 1) checks the device results of the SAME
-particle state against the CPU oracle (``parity_max_rel``, ``--no-check`` to
-skip) and, for the default workload, measures the secondary configurations of
-BASELINE.md section 4 (``extra``: other sizes, unsorted, variable h, the
-reference's own "cube" parameterisation; ``--no-extras`` to skip).
+A plain run sets up, warms up, times the K steps and prints the headline.
+With ``--full``, after the timed loop rank 0 (N = 1) also checks the device
+results of the SAME particle state against the CPU oracle (``parity_max_rel``,
+``--no-check`` to skip), takes the counters and the neighbour-pair count of the
+roofline, times the CPU baseline and, for the default workload, measures the
+secondary configurations of BASELINE.md section 4 (``extra``: other sizes,
+unsorted, variable h, the reference's own "cube" parameterisation;
+``--no-extras`` to skip); for N > 1 the 1-vs-N parity check runs first.
+``--dump-outputs DIR`` writes the output fields of the last timed step.
 
 Prints ONE JSON line (rank 0).
 """
@@ -66,6 +70,8 @@ ELEMENTWISE_TOL_CANCELLING = PARITY_TOL / ELEMENTWISE_FLOOR
 PARITY_TOL_F32 = 5e-5
 ELEMENTWISE_FLOOR_F32 = 1e-3
 ELEMENTWISE_TOL_F32 = PARITY_TOL_F32 / ELEMENTWISE_FLOOR_F32
+DUMP_BYTES = 60 * 10 ** 6    # --dump-outputs: data of all files together, below 64 MB with the .npy headers
+DUMP_SEED = 2024             # ... the particles kept when the outputs are larger
 
 
 # ---------------------------------------------------------------------------
@@ -618,6 +624,32 @@ def copy_arrays(arrays):
     return out
 
 
+def dump_outputs(w, outdir):
+    """--dump-outputs: the output fields (`Workload.fields`) of this rank's real particles as the device holds them
+    after the last step, one DIR/<array>_<field>.npy (float64) each.  Rows are in the lexicographic order of the
+    particles' positions (inputs the step does not change), so that two builds that order the particles differently
+    on the device write the same files; when all fields together exceed DUMP_BYTES, every array keeps the same
+    fraction of its particles, drawn with DUMP_SEED."""
+    os.makedirs(outdir, exist_ok=True)
+    per = [(a, a.gpu.get_number_of_particles(True), [f for f in w.fields if f in a.properties]) for a in w.arrays]
+    total = sum(n * len(fields) * 8 for _, n, fields in per)
+    frac = min(1.0, DUMP_BYTES / float(total)) if total else 1.0
+    rng = np.random.default_rng(DUMP_SEED)
+    for a, n, fields in per:
+        if n == 0 or not fields:
+            continue
+        buf = np.empty(a.gpu.get_number_of_particles())     # (slab runs: the ghosts behind the real particles)
+
+        def col(p):
+            return a.gpu.pull_into(p, buf)[:n].copy()
+        rows = np.lexsort((col('z'), col('y'), col('x')))
+        m = int(n * frac)
+        if m < n:
+            rows = rows[np.sort(rng.choice(n, m, replace=False))]
+        for f in fields:
+            np.save(os.path.join(outdir, '%s_%s.npy' % (a.name, f)), col(f)[rows])
+
+
 # ---------------------------------------------------------------------------
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -657,6 +689,14 @@ def parse_args(argv=None):
     ap.add_argument('--opt', action='append', default=[], help='key=value library option')
     ap.add_argument('--no-reorder', action='store_true',
                     help='skip Solver.reorder_particles() before timing')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the oracle parity check (1-vs-N parity for N > 1), the counters, the '
+                         'neighbour-pair count, the secondary configurations and the CPU baseline (each still off with '
+                         'its --no-* flag); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', default=None, dest='dump_outputs', metavar='DIR',
+                    help='after the timed steps write the output fields of the last step as DIR/<array>_<field>.npy '
+                         '(float64, rank 0\'s real particles in the order of their positions, a seeded sample when '
+                         'they exceed %d MB)' % (DUMP_BYTES // 10 ** 6))
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-check', action='store_true', help='skip the oracle parity check')
     ap.add_argument('--no-extras', action='store_true', help='skip the secondary configurations')
@@ -985,7 +1025,7 @@ def run(args, rank, local_rank, world, dist):
         torch.cuda.synchronize()
 
     extra = {}
-    if world > 1 and hasattr(dist, 'all_gather'):
+    if args.full and world > 1 and hasattr(dist, 'all_gather'):
         # 1-vs-N parity of a small instance before anything is timed
         extra['parity_1_vs_n_ranks_max_rel'] = multi_rank_parity(
             args, rank, local_rank, world, dist, tstream)
@@ -994,7 +1034,7 @@ def run(args, rank, local_rank, world, dist):
     n_local = sum(a.get_number_of_particles() for a in w.arrays)
     nnps, a_eval, halo, domain, step, ordered = setup(args, w, rank, world, dist, ctx)
     host_in = None
-    if rank == 0 and world == 1 and not args.no_check:
+    if args.full and rank == 0 and world == 1 and not args.no_check:
         # inputs as the device holds them now (after the spatial reordering)
         for a in w.arrays:
             a.gpu.pull()
@@ -1011,7 +1051,7 @@ def run(args, rank, local_rank, world, dist):
     # flop-side reading of the pair loop that SURVEY 8(d) asks for next to the
     # HBM one
     pairs = None
-    if args.workload == 'cube' and rank == 0:
+    if args.full and args.workload == 'cube' and rank == 0:
         pairs = nnps.count_neighbors(0, 0)
     pair_ms, pair_launches = timers['pair']
     n_total = n_local * world          # real particles only (ghosts are extra work)
@@ -1029,6 +1069,8 @@ def run(args, rank, local_rank, world, dist):
         w.transport = None
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(w, args.dump_outputs)
 
     # HBM bytes per launch of the dominant kernel come from a separate
     # rocprofv3 --pmc run of this same command (profiles/); only quoted when
@@ -1050,7 +1092,7 @@ def run(args, rank, local_rank, world, dist):
         traffic = None
     # ... unless rocprofv3 is on this box: then the counters are taken in THIS run (three short child runs)
     measured_kernel = None
-    if world == 1 and not args.no_counters and not args.ablate:
+    if args.full and world == 1 and not args.no_counters and not args.ablate:
         wl_flags = ['--workload', args.workload, '--n1', str(args.n1), '--dtype', args.dtype, '--params', args.params,
                     '--dx', repr(args.dx), '--variant', str(args.variant)]
         if args.vary_h:
@@ -1138,7 +1180,7 @@ def run(args, rank, local_rank, world, dist):
     if host_in is not None:
         tol = PARITY_TOL if args.dtype == 'f64' else 5e-5   # fp32: tests/test_hip_parity.py::test_fp32_arithmetic_vs_golden
         extra.update(parity_check(w, host_in, nnps, domain, tol))
-    if world == 1 and not args.no_extras and args.workload == 'cube' \
+    if args.full and world == 1 and not args.no_extras and args.workload == 'cube' \
             and args.params == 'db' and not args.vary_h and args.n1 == 159 \
             and args.dtype == 'f64' and not args.ablate:
         del nnps, a_eval, step      # free this workload's device state first (252^3 needs room)
@@ -1147,7 +1189,7 @@ def run(args, rank, local_rank, world, dist):
         t1 = extra['secondary'].get('C4 dam break dx 0.0035 (16 M) on one GPU', {}).get('ms_per_step')
         extra['projected_strong_scaling_8'] = projected_strong_scaling(args, local_rank, tstream, t_one_gpu_ms=t1)
         extra['time_stepping'] = time_stepping(local_rank, tstream)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # on the size of the reported workload itself (159^3 for the headline line: ~1.1 s per pass on the box's cores);
         # --cpu-n1 overrides the sample
         n_cpu = args.cpu_n1 or (args.n1 if args.workload == 'cube' else 100)

@@ -60,6 +60,6 @@ else
     run_one dam_break_4m 2 --workload dam_break --dx 0.0055
     run_one dam_break_4m_vh 0 --workload dam_break --dx 0.0055 --vary-h 0.15
     run_one cube_vh 0 --vary-h 0.15
-    # (the 16 M dam break is timed and checked by the default bench line: extra.secondary)
+    # (the 16 M dam break is timed and checked by `bench.py --full`: extra.secondary)
 fi
 du -sh "$ROOT/gpurun_out/$TAG"

@@ -486,8 +486,135 @@ def case_steppers():
     print('wrote', path)
 
 
+def case_compiled_kernels():
+    """The reference's COMPILED smoothing kernels (pysph/base/c_kernels.pyx, what
+    its Cython backend evaluates; built into oracle/_ref/ by oracle/build_ref.sh)
+    on random (r, h, xij), r = 0, r on the support radius and beyond it, each
+    kernel constructed with this package's fac and radius_scale:
+    tests/test_oracle_golden.py::test_oracle_kernels_vs_compiled_reference."""
+    import glob
+    import importlib.util
+    from pysph_amd import kernels as K
+    so = glob.glob(os.path.join(REPO, 'oracle', '_ref', 'c_kernels*.so'))
+    if not so:
+        raise RuntimeError('oracle/_ref/c_kernels not built (oracle/build_ref.sh)')
+    spec = importlib.util.spec_from_file_location('c_kernels', so[0])
+    ck = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ck)
+    out = {}
+    rng = np.random.default_rng(42)
+    for cls, dims in ((K.CubicSpline, (1, 2, 3)), (K.WendlandQuintic, (2, 3)),
+                      (K.QuinticSpline, (1, 2, 3)), (K.Gaussian, (1, 2, 3))):
+        for dim in dims:
+            k = cls(dim=dim)
+            ref = getattr(ck, cls.__name__)(dim=dim, fac=k.fac, radius_scale=k.radius_scale)
+            h = rng.uniform(0.05, 2.0, 400)
+            q = np.concatenate([rng.uniform(0, 1.2 * k.radius_scale, 394), [0.0, 1.0, 2.0, 3.0, k.radius_scale, 1e-13]])
+            r, xij = np.empty(h.size), np.zeros((h.size, 3))
+            w, dwdq, grad = np.empty(h.size), np.empty(h.size), np.zeros((h.size, 3))
+            for i in range(h.size):
+                r[i] = float(q[i] * h[i])
+                d = rng.normal(size=3)
+                d[dim:] = 0.0
+                nd = float(np.sqrt(d @ d))
+                xij[i] = (d / nd * r[i]) if nd > 0 else d
+                w[i] = ref.py_kernel(xij[i], r[i], h[i])
+                dwdq[i] = ref.py_dwdq(r[i], h[i])
+                ref.py_gradient(xij[i], r[i], h[i], grad[i])
+            key = '%s/%d/' % (cls.__name__, dim)
+            out.update({key + 'fac': np.array(k.fac), key + 'radius_scale': np.array(k.radius_scale),
+                        key + 'deltap': np.array(ref.py_get_deltap()), key + 'h': h, key + 'r': r,
+                        key + 'xij': xij, key + 'w': w, key + 'dwdq': dwdq, key + 'grad': grad})
+    path = os.path.join(HERE, 'compiled_kernels.npz')
+    np.savez_compressed(path, **out)
+    print('wrote', path)
+
+
+def _sha256_lines(lines):
+    import hashlib
+    return hashlib.sha256('\n'.join(lines).encode()).hexdigest()
+
+
+def case_reference_pins():
+    """What this package's marshalling and translator make of the reference's OWN
+    objects (schemes, kernels, AccelerationEval, equation classes): the C-ABI
+    structs and MegaGroup order of tests/test_reference_objects.py, and per
+    translated reference equation the SHA-256 of its generated code (comments
+    aside, tests/test_codegen.py::_body_lines) with its property lists, or the
+    symbols and source flags of a family, which
+    tests/test_codegen.py::test_reference_classes_translate_like_the_restatements
+    compares with the in-repo restatements.  Numbers, names and digests only."""
+    import json
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_reference_objects import _marshal
+    from test_codegen import _arrays, _body_lines
+    from pysph.sph.scheme import WCSPHScheme as RefWCSPH, TVFScheme as RefTVF
+    from pysph.sph.acceleration_eval import AccelerationEval as RefAE
+    from pysph.base.kernels import WendlandQuintic as RefKernel
+    from pysph_amd.kernels import kernel_id
+    from pysph_amd.codegen import GeneratedFamily
+    from pysph_amd.particle_array import get_particle_array_tvf_fluid, get_particle_array_wcsph
+    pins = {}
+    # tests/test_reference_objects.py
+    arrays = db.create_particles(0.2)
+    kw = dict(dim=3, rho0=db.ro, c0=db.c0, h0=0.26, hdx=1.3, gz=-9.81,
+              alpha=db.alpha, beta=db.beta, gamma=db.gamma, hg_correction=True,
+              tensile_correction=False)
+    rk = RefKernel(dim=3)
+    pins['wcsph_scheme'] = {
+        'marshal': _marshal(RefWCSPH(['fluid'], ['boundary', 'obstacle'], **kw).get_equations(), arrays),
+        'kernel': {'id': kernel_id(rk), 'fac': rk.fac, 'radius_scale': rk.radius_scale,
+                   'deltap': rk.get_deltap(), 'dim': rk.dim}}
+    pa = get_particle_array_tvf_fluid(name='fluid', x=np.zeros(4))
+    kw_tvf = dict(dim=3, rho0=1.0, c0=10.0, nu=0.01, p0=100.0, pb=100.0, h0=0.1, gx=0.1, alpha=0.2)
+    pins['tvf_scheme'] = {'marshal': _marshal(RefTVF(['fluid'], [], **kw_tvf).get_equations(), [pa])}
+    kw.pop('tensile_correction')
+    ae = RefAE(arrays, RefWCSPH(['fluid'], ['boundary', 'obstacle'], **kw).get_equations(), RefKernel(dim=3))
+    pins['acceleration_eval'] = {
+        'mega_groups': [{dest: [[e.name for e in no_src.equations],
+                                {src: [e.name for e in g.equations] for src, g in by_src.items()},
+                                [e.name for e in all_src.equations]]
+                         for dest, (no_src, by_src, all_src) in mg.data.items()} for mg in ae.mega_groups],
+        'marshal': _marshal(ae.equation_groups, arrays)}
+    # tests/test_codegen.py::test_reference_classes_translate_like_the_restatements
+    import pysph.sph.wc.transport_velocity as tv
+    import pysph.sph.wc.basic as wb
+    import pysph.sph.basic_equations as be
+    import pysph.sph.wc.density_correction as dcorr
+    arrays = _arrays()
+    tr = {}
+    for name, kw in [
+            ('SetWallVelocity', dict(dest='wall', sources=['fluid'])),
+            ('SolidWallPressureBC', dict(dest='wall', sources=['fluid'], rho0=1.0, p0=100.0, gy=-1.0)),
+            ('SolidWallNoSlipBC', dict(dest='fluid', sources=['wall'], nu=0.01)),
+            ('ContinuitySolid', dict(dest='fluid', sources=['wall'])),
+            ('VolumeSummation', dict(dest='fluid', sources=['fluid', 'wall'])),
+            ('VolumeFromMassDensity', dict(dest='fluid', sources=None))]:
+        f = GeneratedFamily(kw['dest'], [getattr(tv, name)(**kw)], arrays, 3, 'r')
+        tr[name] = {'body_sha256': _sha256_lines(_body_lines(f.source)), 'din': f.din, 'dout': f.dout,
+                    'sprops': f.sprops}
+    pf = get_particle_array_wcsph(name='fluid', x=np.zeros(2))
+    pf.add_property('rhotmp')
+    f = GeneratedFamily('fluid', [dcorr.ShepardFilter('fluid', ['fluid'])], {'fluid': pf}, 2, 'r')
+    tr['ShepardFilter'] = {'body_sha256': _sha256_lines(_body_lines(f.source)),
+                           'loop_all': f.loop_all, 'split_init': f.split_init}
+    f = GeneratedFamily('fluid', [
+        be.ContinuityEquation('fluid', ['fluid', 'wall']),
+        wb.MomentumEquation('fluid', ['fluid', 'wall'], c0=10.0, alpha=0.2, beta=0.1,
+                            gz=-9.81, tensile_correction=True),
+        be.XSPHCorrection('fluid', ['fluid'], eps=0.5)], arrays, 2, 'ref_wcsph')
+    tr['wcsph_family'] = {'symbols': sorted(f.symbols), 'src_flags': f.src_flags}
+    pins['translations'] = tr
+    path = os.path.join(HERE, 'reference_pins.json')
+    with open(path, 'w') as fh:
+        json.dump(pins, fh, indent=1)     # (key order is part of what is pinned)
+        fh.write('\n')
+    print('wrote', path)
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['kernels', 'sd_1d', 'wcsph_cube_varh', 'tvf_cube',
-                             'wcsph_dam', 'wcsph_dam_varh', 'steppers', 'elastic_2d', 'elastic_3d', 'tvf_wall']
+                             'wcsph_dam', 'wcsph_dam_varh', 'steppers', 'elastic_2d', 'elastic_3d', 'tvf_wall',
+                             'compiled_kernels', 'reference_pins']
     for w in which:
         globals()['case_' + w]()

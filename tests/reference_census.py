@@ -2,7 +2,7 @@
 
 Run in a process of its own (it plants stand-ins for compyle / cyarray / the
 Cython particle array in sys.modules so that as many pysph.sph modules as
-possible import) by tests/test_codegen.py; prints one JSON object
+possible import), by hand where the reference is present; prints one JSON object
 {"ok": [...], "bad": {class: reason}, "import_failed": [...]}.
 Needs /root/reference: build-container only."""
 import sys, os, types, inspect, importlib, pkgutil, collections, json

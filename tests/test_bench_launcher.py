@@ -174,3 +174,48 @@ def test_timed_region_is_exactly_k_steps_behind_the_breakdown_and_the_warm_up():
     names = [e[0] + (str(e[1]) if len(e) > 1 else '') for e in log]
     assert names == (['enable1', 'step', 'reset'] + ['step'] * 5 + ['barrier', 'enable2'] + ['step'] * 2 +
                      ['reset', 'barrier'] + ['step'] * 5 + ['barrier', 'enable0']), names
+
+
+def test_dump_outputs_is_independent_of_the_device_order_and_capped(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): the same particles held in two different device orders, ghosts behind
+    the real ones, write the same files -- float64 output fields only, rows in position order -- and a seeded sample
+    of the same rows when the outputs exceed the byte budget"""
+    import numpy as np
+    import bench
+
+    class Helper(object):
+        def __init__(self, pa, order, n_ghosts):
+            self.pa, self.order, self.n_ghosts = pa, order, n_ghosts
+
+        def get_number_of_particles(self, real=False):
+            return self.order.size + (0 if real else self.n_ghosts)
+
+        def pull_into(self, prop, out):
+            out[:] = np.concatenate([self.pa.properties[prop][self.order], np.full(self.n_ghosts, np.nan)])
+            return out
+
+    class Array(object):
+        def __init__(self, name, n, seed):
+            rng = np.random.default_rng(seed)
+            self.name = name
+            self.properties = {p: rng.normal(size=n) for p in ('x', 'y', 'z', 'au', 'p')}
+
+    def dump(order_seed, outdir):
+        w = bench.Workload()
+        w.fields = ('au', 'p', 'arho')          # arho: not a property of these arrays
+        w.arrays = [Array('fluid', 600, 1), Array('wall', 200, 2)]
+        for k, a in enumerate(w.arrays):
+            a.gpu = Helper(a, np.random.default_rng(order_seed + k).permutation(a.properties['x'].size), 7)
+        bench.dump_outputs(w, str(outdir))
+        return {f.name: np.load(str(f)) for f in sorted(outdir.iterdir())}
+
+    a, b = dump(10, tmp_path / 'a'), dump(20, tmp_path / 'b')
+    assert sorted(a) == ['fluid_au.npy', 'fluid_p.npy', 'wall_au.npy', 'wall_p.npy']
+    assert all(a[k].dtype == np.float64 and np.array_equal(a[k], b[k]) for k in a)
+    assert a['fluid_p.npy'].size == 600 and np.all(np.isfinite(a['fluid_au.npy']))
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 8 * 2 * 400)   # two fields of half of the 800 particles
+    c, d = dump(10, tmp_path / 'c'), dump(30, tmp_path / 'd')
+    assert sum(v.nbytes for v in c.values()) <= bench.DUMP_BYTES
+    assert (c['fluid_au.npy'].size, c['wall_p.npy'].size) == (300, 100)
+    assert all(np.array_equal(c[k], d[k]) for k in c)
+    assert np.all(np.isin(c['fluid_au.npy'], a['fluid_au.npy']))

@@ -45,7 +45,7 @@ def _run_two_ranks(argv):
 @pytest.mark.gpu
 def test_bench_weak_scaling_path_two_ranks():
     out = _run_two_ranks(['--gpus', '2', '--n1', '32', '--steps', '3', '--warmup', '1',
-                          '--no-cpu-baseline'])
+                          '--no-cpu-baseline', '--full'])
     json.dumps(out)
     assert out['n_gpus'] == 2 and out['scaling'] == 'weak'
     assert out['config']['parallelism'] == 'slab2'
@@ -58,7 +58,7 @@ def test_bench_weak_scaling_path_two_ranks():
 @pytest.mark.gpu
 def test_bench_dam_break_strong_scaling_path_two_ranks():
     out = _run_two_ranks(['--gpus', '2', '--workload', 'dam_break', '--dx', '0.05',
-                          '--steps', '2', '--warmup', '1', '--no-cpu-baseline'])
+                          '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--full'])
     assert out['n_gpus'] == 2 and out['scaling'] == 'strong'
     from pysph_amd.examples import dam_break_3d as db
     total = sum(a.get_number_of_particles() for a in db.create_particles(0.05))
@@ -260,7 +260,7 @@ def test_elastic_two_slabs_match_one_domain_by_gid(argv):
 @pytest.mark.gpu
 def test_bench_elastic_strong_scaling_path_two_ranks():
     out = _run_two_ranks(['--gpus', '2', '--workload', 'elastic', '--rings-dx', '2e-3', '--steps', '2',
-                          '--warmup', '1', '--no-cpu-baseline'])
+                          '--warmup', '1', '--no-cpu-baseline', '--full'])
     assert out['n_gpus'] == 2 and out['scaling'] == 'strong' and out['config']['parallelism'] == 'slab2'
     import bench
     total = bench.make_rings3d(2e-3)[0].get_number_of_particles()
@@ -270,7 +270,7 @@ def test_bench_elastic_strong_scaling_path_two_ranks():
 @pytest.mark.gpu
 def test_bench_taylor_green_path_two_ranks():
     out = _run_two_ranks(['--gpus', '2', '--workload', 'taylor_green', '--n1', '20', '--steps', '2',
-                          '--warmup', '1', '--no-cpu-baseline'])
+                          '--warmup', '1', '--no-cpu-baseline', '--full'])
     assert out['n_gpus'] == 2 and out['config']['parallelism'] == 'slab2'
     assert out['config']['particles_per_gpu'] == 20 ** 3
 

@@ -11,7 +11,6 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-REF = '/root/reference'
 
 
 def _arrays():
@@ -235,21 +234,28 @@ def test_mixed_destination_rules():
         _CGroup(Group([mom, Scales('fluid', ['wall'])]), ids, arrays, 3)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
+def _sha256_lines(lines):
+    import hashlib
+    return hashlib.sha256('\n'.join(lines).encode()).hexdigest()
+
+
 def test_reference_classes_translate_like_the_restatements():
-    """The reference's own wall-equation classes go through the same translator
-    and give the SAME generated code as tests/wall_equations_fixture.py (comments
+    """The reference's own wall-equation classes, put through the same translator,
+    gave the SAME generated code as tests/wall_equations_fixture.py (comments
     aside): the in-repo bodies are the reference's semantics, statement by
-    statement.  A few other reference equations are translated and compiled to
-    show the drop-in for real pysph objects (WDP, RHOIJ1, VIJ ...)."""
-    for p in (REF, os.path.join(REPO, 'oracle', '_stubs')):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    import pysph.sph.wc.transport_velocity as tv
-    import pysph.sph.wc.basic as wb
-    import pysph.sph.basic_equations as be
+    statement.  The reference's side is stored in tests/golden/reference_pins.json
+    (tests/golden/make_golden.py reference_pins: SHA-256 of the generated code and
+    the property lists); the restatements must translate to it.  The same holds for
+    a loop_all equation (ShepardFilter, density_correction.py:24-46: initialize()
+    split off).  The reference's ContinuityEquation + MomentumEquation +
+    XSPHCorrection, as one family, used the symbols (WDP, RHOIJ1, VIJ ...) and
+    source flags of their restatements in tests/custom_equations.py, whose family
+    is compiled."""
+    import json
     import wall_equations_fixture as mine
     from pysph_amd.codegen import GeneratedFamily
+    with open(os.path.join(REPO, 'tests', 'golden', 'reference_pins.json')) as f:
+        ref = json.load(f)['translations']
     arrays = _arrays()
     cases = [
         ('SetWallVelocity', dict(dest='wall', sources=['fluid'])),
@@ -259,63 +265,29 @@ def test_reference_classes_translate_like_the_restatements():
         ('VolumeSummation', dict(dest='fluid', sources=['fluid', 'wall'])),
         ('VolumeFromMassDensity', dict(dest='fluid', sources=None)),
     ]
-    # a loop_all equation: ShepardFilter (density_correction.py:24-46) vs the
-    # restatement the GPU test runs; initialize() must be split off
-    import pysph.sph.wc.density_correction as dcorr
     sys.path.insert(0, os.path.join(REPO, 'tests'))
     import custom_equations as ce
     from pysph_amd.particle_array import get_particle_array_wcsph
     pf = get_particle_array_wcsph(name='fluid', x=np.zeros(2))
     pf.add_property('rhotmp')
-    a = GeneratedFamily('fluid', [dcorr.ShepardFilter('fluid', ['fluid'])], {'fluid': pf}, 2, 'r')
     b = GeneratedFamily('fluid', [ce.ShepardFilter('fluid', ['fluid'])], {'fluid': pf}, 2, 'm')
-    assert _body_lines(a.source) == _body_lines(b.source)
-    assert a.loop_all and a.split_init
+    assert ref['ShepardFilter'] == {'body_sha256': _sha256_lines(_body_lines(b.source)),
+                                    'loop_all': b.loop_all, 'split_init': b.split_init}
+    assert b.loop_all and b.split_init
     for name, kw in cases:
-        a = GeneratedFamily(kw['dest'], [getattr(tv, name)(**kw)], arrays, 3, 'r')
         b = GeneratedFamily(kw['dest'], [getattr(mine, name)(**kw)], arrays, 3, 'm')
-        assert _body_lines(a.source) == _body_lines(b.source), name
-        assert (a.din, a.dout, a.sprops) == (b.din, b.dout, b.sprops)
+        assert ref[name]['body_sha256'] == _sha256_lines(_body_lines(b.source)), name
+        assert (ref[name]['din'], ref[name]['dout'], ref[name]['sprops']) == (b.din, b.dout, b.sprops)
     fam = GeneratedFamily('fluid', [
-        be.ContinuityEquation('fluid', ['fluid', 'wall']),
-        wb.MomentumEquation('fluid', ['fluid', 'wall'], c0=10.0, alpha=0.2, beta=0.1,
-                            gz=-9.81, tensile_correction=True),
-        be.XSPHCorrection('fluid', ['fluid'], eps=0.5)], arrays, 2, 'ref_wcsph')
+        ce.PyContinuity('fluid', ['fluid', 'wall']),
+        ce.PyMomentum('fluid', ['fluid', 'wall'], c0=10.0, alpha=0.2, beta=0.1,
+                      gz=-9.81, tensile_correction=True),
+        ce.PyXSPH('fluid', ['fluid'], eps=0.5)], arrays, 2, 'ref_wcsph')
+    r = ref['wcsph_family']
+    assert r['symbols'] == sorted(fam.symbols) and r['src_flags'] == fam.src_flags
     assert {'WDP', 'WIJ', 'DWIJ', 'VIJ', 'RHOIJ1'} <= fam.symbols
     assert fam.src_flags == {'fluid': 7, 'wall': 3}
     fam.build()
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference tree only exists in the build container')
-def test_reference_equation_census():
-    """Every Equation subclass of the reference's pysph.sph package that can be
-    imported here (tests/reference_census.py plants stand-ins for compyle,
-    cyarray and the Cython particle array, in a process of its own) goes
-    through the translator.  What is refused, and why:
-
-    * scatter writes to SOURCE arrays (rigid_body, swe ParticleAcceleration):
-      the device loop is a gather;
-    * 2-D list locals, > 20 source properties, recursion / list arguments to
-      non-helper functions;
-    * MLSFirstOrder3D: its loop_all calls augmented_matrix with five arguments
-      (density_correction.py:189; the 2-D twin passes six)."""
-    import json
-    import subprocess
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'tests', 'reference_census.py')],
-                         stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600, check=True)
-    d = json.loads(out.stdout.decode().strip().splitlines()[-1])
-    ok = set(k.split('.')[-1] for k in d['ok'])
-    assert len(d['ok']) >= 252, (len(d['ok']), d['bad'])
-    assert len(d['ok']) >= 5 * len(d['bad'])
-    for name in ('GradientCorrectionPreStep', 'GradientCorrection', 'MixedGradientCorrection',
-                 'UpdateMomentMatrix', 'EvaluateP', 'CopyPFromGhost', 'MLSFirstOrder2D',
-                 'ComputeNormals', 'SetWallVelocityNew', 'MomentumEquationDeltaSPH',
-                 'SolidWallNoSlipBC', 'ShepardFilter', 'CRKSPHSymmetric',
-                 'MomentumEquationWithStress', 'HookesDeviatoricStressRate'):
-        assert name in ok, name
-    reasons = ' '.join(d['bad'].values())
-    for expected in ('source arrays are read-only', 'more than 20 source properties'):
-        assert expected in reasons
 
 
 def test_locals_named_like_cpp_keywords_or_skeleton_variables():

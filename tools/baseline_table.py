@@ -1,4 +1,4 @@
-"""print the BASELINE.md section-4 tables from a `python bench.py` JSON line (profiles/rNN_bench_default.json)"""
+"""print the BASELINE.md section-4 tables from a `python bench.py --full` JSON line (profiles/rNN_bench_default.json)"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 e = d['extra']

@@ -19,7 +19,7 @@ shift
 mkdir -p gpurun_out/$OUT
 export TMPDIR=/tmp
 cp pysph_amd/libsphhip.so /tmp/main.so
-B="python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5"
 summ() {
   python -c "
 import json,sys
