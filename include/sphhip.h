@@ -497,6 +497,45 @@ int sph_halo_append_promised(sph_ctx *ctx, int array_id, int nprops, const int *
  * sph_halo_append and made real with sph_array_resize(n, n).                 */
 int sph_halo_remove_selected(sph_ctx *ctx, int array_id, size_t *n_left);
 
+/* ---------------------------------------------------------------------- */
+/* Open boundaries: rows cross between particle arrays on the device
+ * (InletBase.update / OutletBase.update, pysph/sph/bc/inlet_outlet_manager.py:
+ * 586-621, 710-743).  Only counts cross to the host; rows keep their order
+ * (appended in ascending source index, removed by a stable compaction -- the
+ * reference's remove_particles fills holes from the end: same SETS).         */
+/* ---------------------------------------------------------------------- */
+/* IOEvaluate.loop (inlet_outlet_manager.py:393-406) for every row (real_only:
+ * the real rows) of the array: disp = (x - x0) . n with plane = {x0, y0, z0,
+ * xn, yn, zn}, ioid = 1 if disp > 1e-6 and disp - maxdist < 1e-6, 2 if
+ * disp - maxdist > 1e-6, else 0 (the reference's default maxdist is 1000).
+ * Written to the device properties "disp" / "ioid" when the array has them,
+ * and kept as the array's SELECTION (one class per row) for the calls below
+ * until its rows change.  The three class counts are reduced on the device;
+ * counts_out (3 values) reads them now (one small device->host copy), NULL
+ * leaves them for sph_io_counts.                                             */
+int sph_io_classify(sph_ctx *ctx, int array_id, const double *plane, double maxdist, int real_only, size_t *counts_out);
+/* The class counts of several classified arrays in ONE device->host copy:
+ * counts_out[3 * k + ioid] for array ids[k] (the "np.where(ioid == ...)" sizes
+ * of InletBase.update / OutletBase.update).                                  */
+int sph_io_counts(sph_ctx *ctx, int narrays, const int *ids, size_t *counts_out);
+/* Append the rows of class `which_ioid` of src to the real rows of dst, in
+ * ascending source index (extract_particles(idx, dest_array, props),
+ * device_helper.py:660-672): the listed properties are copied; a device
+ * property of dst that is not listed, or that src lacks, reads 0 on the new
+ * rows.  dst may be empty; ghosts behind its real rows are SPH_ERR_STATE.
+ * keep_source = 0 also removes the rows from src (sph_io_remove_selected).
+ * The receiver's h / m knowledge and the neighbour grid are invalidated.     */
+int sph_io_transfer(sph_ctx *ctx, int src_id, int dst_id, int which_ioid, int nprops, const int *props, int keep_source);
+/* x, y, z += (dx, dy, dz) on the rows of array_id whose INDEX has class
+ * which_ioid in the selection of flags_array_id (the same array: the inlet's
+ * wrap-back by +length n; the index-aligned ghost inlet: -length n,
+ * inlet_outlet_manager.py:611-618).                                          */
+int sph_io_shift_selected(sph_ctx *ctx, int array_id, int which_ioid, int flags_array_id, double dx, double dy, double dz);
+/* Remove the rows of class which_ioid: stable compaction of every device
+ * property (remove_particles, device_helper.py:480-525; the kept rows keep
+ * their order).  Requires n == n_real.  n_left (may be NULL): rows that stay. */
+int sph_io_remove_selected(sph_ctx *ctx, int array_id, int which_ioid, size_t *n_left);
+
 /* Box-wrap the first n_real particles along `axis` into [vmin, vmax]:
  * v < vmin -> v + translate; v > vmax -> v - translate
  * (CPUDomainManager._box_wrap_periodic, pysph/base/nnps_base.pyx:699-748).   */

@@ -833,6 +833,11 @@ class _Body(object):
         hoisted to its top, a bare ``return`` leaves just this equation"""
         pad = '    ' * ind
         out = [pad + '[&]() {  // %s' % self.where]
+        if getattr(self.eq, '_fp_contract_', True) is False:
+            # an equation whose results must not depend on WHICH multiply-adds the compiler fuses (it chooses per
+            # kernel: the same expression came out fused differently in two kernels of one family): every
+            # product and sum of this body is rounded on its own, in source order
+            out.append(pad + '    #pragma clang fp contract(off)')
         for name, (kind, n) in sorted(self.locals.items()):
             if kind == 'array':
                 out.append(pad + '    double %s[%d] = {};' % (_cn(name), n))

@@ -146,6 +146,8 @@ int sph_ctx_destroy(sph_ctx *c)
     }
     for (auto &H : c->halo)
         for (int s = 0; s < 2; s++) { H.flag[s].release(); H.pos[s].release(); H.list[s].release(); }
+    for (auto &I : c->io) I.code.release();
+    c->io_counts.release();
     for (DevBuf *b : {&c->dbgc, &c->gapq, &c->cub_tmp, &c->red_part, &c->red_out, &c->posh, &c->aux, &c->fposb, &c->dkeys, &c->dperm,
                       &c->tmp_u32a, &c->tmp_u32b, &c->gen_state, &c->nlbuf, &c->splitcnt, &c->scan_part, &c->bigq, &c->sort_tab, &c->xflag, &c->dom_counts})
         b->release();
@@ -283,6 +285,9 @@ int sph_array_fill(sph_ctx *c, int id, int prop, double value, size_t offset, si
     HIP_TRY(hipSetDevice(c->device));
     hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, A.prop[prop] + offset, n, value);
     if (prop == SPH_X || prop == SPH_Y || prop == SPH_Z || prop == SPH_H) c->nnps_valid = false;
+    // positions written here may lie anywhere, as those of sph_array_push: the next neighbour update looks at the
+    // particles before it bins (it does not reuse the previous update's bounds)
+    if (prop == SPH_X || prop == SPH_Y || prop == SPH_Z) c->lag.valid = false;
     const bool same_h = prop == SPH_H && A.h_seen && !A.h_dirty && A.h_lo == value && A.h_hi == value;
     const bool same_m = prop == SPH_M && A.m_seen && !A.m_dirty && A.m_lo == value && A.m_hi == value;
     if (!same_h && !same_m) sph_mark_written(A, prop);

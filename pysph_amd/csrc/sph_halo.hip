@@ -1061,3 +1061,282 @@ extern "C" int sph_array_props(sph_ctx *c, int id, int *out, int cap, int *n)
     *n = k;
     return SPH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Open boundaries: particles cross from one array to another on the device (InletBase.update / OutletBase.update,
+// pysph/sph/bc/inlet_outlet_manager.py:586-621, 710-743).  The reference classifies with an IOEvaluate evaluator, pulls
+// ioid, builds index lists with numpy and moves the rows with extract_particles / remove_particles; here the class of
+// every row stays on the device (IoState::code), the moves read it, and only the three counts cross to the host.
+// Rows keep their order everywhere: appended rows in ascending source index, removal is a stable compaction (the
+// reference fills the holes from the end; as SETS of particles the results agree).
+// ---------------------------------------------------------------------------------------------------------------------
+struct IoPlane {
+    double x, y, z, xn, yn, zn, maxdist;
+};
+
+// ioid of IOEvaluate.loop (inlet_outlet_manager.py:393-406): the same expression and the same three comparisons.  The
+// generated IOEvaluate family (pysph_amd/inlet_outlet.py) must give every particle the same disp, bit for bit, and so the
+// same class at a threshold: both bodies are compiled with floating-point contraction OFF -- with it on the compiler
+// picks per kernel which of the three products stays a multiply (two kernels of one generated family differed).
+__global__ __launch_bounds__(256) void k_io_classify(const double *__restrict__ x, const double *__restrict__ y,
+                                                     const double *__restrict__ z, size_t n_cls, size_t n, IoPlane P,
+                                                     double *__restrict__ disp, double *__restrict__ ioid,
+                                                     uint8_t *__restrict__ code, uint32_t *__restrict__ counts)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int id = 3; // no class: not counted, never selected
+    if (i < n_cls) {
+#pragma clang fp contract(off)
+        const double d = (x[i] - P.x) * P.xn + (y[i] - P.y) * P.yn + (z[i] - P.z) * P.zn;
+        const double beyond = d - P.maxdist;
+        if (d > 1e-6 && beyond < 1e-6) id = 1;
+        else if (beyond > 1e-6) id = 2;
+        else id = 0;
+        if (disp) disp[i] = d;
+        if (ioid) ioid[i] = (double)id;
+    }
+    if (i < n) code[i] = id == 3 ? (uint8_t)0xff : (uint8_t)id;
+    // (every lane of the wavefront arrives here: one atomic per class and wavefront)
+    for (int k = 0; k < 3; k++) {
+        const unsigned long long b = __ballot(id == k);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(&counts[k], (uint32_t)__popcll(b));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_io_flags(const uint8_t *__restrict__ code, size_t n, int which, int invert,
+                                                  uint32_t *__restrict__ flag)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool sel = code[i] == (uint8_t)which;
+    flag[i] = (sel != (invert != 0)) ? 1u : 0u;
+}
+
+// every device property of the receiving array in one launch (blockIdx.y = property, as k_halo_gather_multi):
+// s[k] == nullptr: the source lacks the property or it is not among the copied ones -- the new rows read 0
+struct IoXfer {
+    const double *s[SPH_PROP_COUNT];
+    double *d[SPH_PROP_COUNT];
+};
+
+__global__ __launch_bounds__(256) void k_io_transfer(IoXfer T, const uint32_t *__restrict__ list, size_t count, size_t n0)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const int k = blockIdx.y;
+    const double *s = T.s[k];
+    T.d[k][n0 + i] = s ? s[list[i]] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_io_shift(const uint8_t *__restrict__ code, size_t n, int which, double *__restrict__ x,
+                                                  double *__restrict__ y, double *__restrict__ z, double dx, double dy, double dz)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || code[i] != (uint8_t)which) return;
+    if (x) x[i] += dx;
+    if (y) y[i] += dy;
+    if (z) z[i] += dz;
+}
+
+static int io_check(sph_ctx *c, int id, const char *who)
+{
+    if (!c || id < 0 || id >= SPH_MAX_ARRAYS) { sph_set_error("%s: bad arguments", who); return SPH_ERR_ARG; }
+    if (!c->arr[id].used) { sph_set_error("%s: array %d was never sized (sph_array_resize)", who, id); return SPH_ERR_STATE; }
+    return SPH_OK;
+}
+
+static int io_selection(sph_ctx *c, int id, int which, const char *who)
+{
+    SPH_TRY(io_check(c, id, who));
+    if (which < 0 || which > 2) { sph_set_error("%s: ioid must be 0, 1 or 2 (got %d)", who, which); return SPH_ERR_ARG; }
+    const IoState &I = c->io[id];
+    if (!I.valid || I.nsel != c->arr[id].n) {
+        sph_set_error("%s: array %d has no current selection (call sph_io_classify; rows changed since?)", who, id);
+        return SPH_ERR_STATE;
+    }
+    return SPH_OK;
+}
+
+static int io_read_counts(sph_ctx *c)
+{
+    // the whole table in one copy: SPH_MAX_ARRAYS * 4 words = 128 bytes into the pinned landing pad
+    HIP_TRY(hipMemcpyAsync(c->pinned, c->io_counts.ptr, SPH_MAX_ARRAYS * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+extern "C" int sph_io_classify(sph_ctx *c, int id, const double *plane, double maxdist, int real_only, size_t *counts_out)
+{
+    SPH_TRY(io_check(c, id, "sph_io_classify"));
+    if (!plane) { sph_set_error("sph_io_classify: plane is NULL"); return SPH_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    DevArray &A = c->arr[id];
+    IoState &I = c->io[id];
+    const size_t n = A.n, n_cls = real_only ? A.n_real : A.n;
+    if (n_cls && (!A.prop[SPH_X] || !A.prop[SPH_Y] || !A.prop[SPH_Z])) {
+        sph_set_error("sph_io_classify: array %d has no device coordinates", id);
+        return SPH_ERR_MISSING_PROP;
+    }
+    if (!c->io_counts.ptr) {
+        SPH_TRY(c->io_counts.reserve(SPH_MAX_ARRAYS * 4 * sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(c->io_counts.ptr, 0, SPH_MAX_ARRAYS * 4 * sizeof(uint32_t), c->stream));
+    }
+    uint32_t *counts = c->io_counts.as<uint32_t>() + 4 * id;
+    HIP_TRY(hipMemsetAsync(counts, 0, 4 * sizeof(uint32_t), c->stream));
+    SPH_TRY(I.code.reserve(n + 64));
+    if (n) {
+        const int p_disp = sph_prop_id("disp"), p_ioid = sph_prop_id("ioid");
+        IoPlane P = {plane[0], plane[1], plane[2], plane[3], plane[4], plane[5], maxdist};
+        hipLaunchKernelGGL(k_io_classify, dim3(div_up(n, 256)), dim3(256), 0, c->stream, A.prop[SPH_X], A.prop[SPH_Y], A.prop[SPH_Z],
+                           n_cls, n, P, p_disp >= 0 ? A.prop[p_disp] : nullptr, p_ioid >= 0 ? A.prop[p_ioid] : nullptr,
+                           I.code.as<uint8_t>(), counts);
+    }
+    I.nsel = n;
+    I.valid = true;
+    I.counts_known = false;
+    if (counts_out) {
+        SPH_TRY(io_read_counts(c));
+        const uint32_t *h = (const uint32_t *)c->pinned + 4 * id;
+        for (int k = 0; k < 3; k++) I.count[k] = counts_out[k] = h[k];
+        I.counts_known = true;
+    }
+    return SPH_OK;
+}
+
+extern "C" int sph_io_counts(sph_ctx *c, int narrays, const int *ids, size_t *counts_out)
+{
+    if (!c || narrays < 1 || narrays > SPH_MAX_ARRAYS || !ids || !counts_out) { sph_set_error("sph_io_counts: bad arguments"); return SPH_ERR_ARG; }
+    for (int a = 0; a < narrays; a++) SPH_TRY(io_selection(c, ids[a], 0, "sph_io_counts"));
+    HIP_TRY(hipSetDevice(c->device));
+    SPH_TRY(io_read_counts(c));
+    for (int a = 0; a < narrays; a++) {
+        IoState &I = c->io[ids[a]];
+        const uint32_t *h = (const uint32_t *)c->pinned + 4 * ids[a];
+        for (int k = 0; k < 3; k++) I.count[k] = counts_out[3 * a + k] = h[k];
+        I.counts_known = true;
+    }
+    return SPH_OK;
+}
+
+// ascending list of the rows of class `which` (invert: of every other row) in c->dkeys
+static int io_list(sph_ctx *c, int id, int which, int invert, size_t count)
+{
+    const size_t n = c->arr[id].n;
+    SPH_TRY(c->tmp_u32a.reserve((n + 64) * 8));
+    SPH_TRY(c->tmp_u32b.reserve((n + 64) * 8));
+    SPH_TRY(c->dkeys.reserve((count + 64) * 4));
+    uint32_t *flag = c->tmp_u32a.as<uint32_t>(), *pos = c->tmp_u32b.as<uint32_t>();
+    hipLaunchKernelGGL(k_io_flags, dim3(div_up(n, 256)), dim3(256), 0, c->stream, c->io[id].code.as<uint8_t>(), n, which, invert, flag);
+    SPH_TRY(dev_scan_u32(c, flag, pos, n, true));
+    hipLaunchKernelGGL(k_list_scatter, dim3(div_up(n, 256)), dim3(256), 0, c->stream, flag, pos, n, c->dkeys.as<uint32_t>());
+    return SPH_OK;
+}
+
+extern "C" int sph_io_remove_selected(sph_ctx *c, int id, int which, size_t *n_left)
+{
+    SPH_TRY(io_selection(c, id, which, "sph_io_remove_selected"));
+    HIP_TRY(hipSetDevice(c->device));
+    DevArray &A = c->arr[id];
+    IoState &I = c->io[id];
+    if (!I.counts_known) { sph_set_error("sph_io_remove_selected: the counts of array %d were not read (sph_io_counts)", id); return SPH_ERR_STATE; }
+    if (A.n != A.n_real) { sph_set_error("sph_io_remove_selected: drop ghost particles first (n=%zu, n_real=%zu)", A.n, A.n_real); return SPH_ERR_STATE; }
+    const size_t n = A.n, gone = I.count[which];
+    if (gone > n) { sph_set_error("sph_io_remove_selected: %zu selected rows of %zu", gone, n); return SPH_ERR_STATE; }
+    if (n_left) *n_left = n - gone;
+    if (gone == 0) return SPH_OK;
+    const size_t keepn = n - gone;
+    if (keepn) {
+        // keep flags -> positions -> ascending list of the kept rows, then the compaction of sph_halo_remove_selected
+        // (never its hole filling: that one does not preserve the order)
+        SPH_TRY(io_list(c, id, which, 1, keepn));
+        const uint32_t *list = c->dkeys.as<uint32_t>();
+        if (!A.spare || A.spare_cap != A.cap) {
+            if (A.spare) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(A.spare)); A.spare = nullptr; }
+            HIP_TRY(hipMalloc((void **)&A.spare, A.cap * sizeof(double)));
+            A.spare_cap = A.cap;
+        }
+        double *tmp = A.spare;
+        for (int p = 0; p < SPH_PROP_COUNT; p++) {
+            if (!A.prop[p]) continue;
+            hipLaunchKernelGGL(k_compact_f64, dim3(div_up(keepn, 256)), dim3(256), 0, c->stream, A.prop[p], list, keepn, tmp);
+            double *old = A.prop[p];
+            A.prop[p] = tmp;
+            tmp = old;
+        }
+        A.spare = tmp;
+    }
+    sph_mark_removed(A, keepn);
+    A.n = A.n_real = keepn;
+    A.has_padding = false;
+    A.perm_n = 0; A.perm_direct_n = 0; // another memory order
+    A.tflag_valid = A.tflag_valid && keepn > 0;
+    I.valid = false;
+    c->nnps_valid = false;
+    return SPH_OK;
+}
+
+extern "C" int sph_io_transfer(sph_ctx *c, int src_id, int dst_id, int which, int nprops, const int *props, int keep_source)
+{
+    SPH_TRY(io_selection(c, src_id, which, "sph_io_transfer"));
+    SPH_TRY(io_check(c, dst_id, "sph_io_transfer"));
+    if (src_id == dst_id || nprops < 0 || (nprops && !props)) { sph_set_error("sph_io_transfer: bad arguments"); return SPH_ERR_ARG; }
+    for (int k = 0; k < nprops; k++)
+        if (props[k] < 0 || props[k] >= SPH_PROP_COUNT) { sph_set_error("sph_io_transfer: bad property id %d", props[k]); return SPH_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    DevArray &S = c->arr[src_id], &D = c->arr[dst_id];
+    IoState &I = c->io[src_id], &J = c->io[dst_id];
+    if (!I.counts_known) { sph_set_error("sph_io_transfer: the counts of array %d were not read (sph_io_counts)", src_id); return SPH_ERR_STATE; }
+    if (D.n != D.n_real) {
+        sph_set_error("sph_io_transfer: the receiving array has ghosts behind its real rows: drop them first (n=%zu, n_real=%zu)", D.n, D.n_real);
+        return SPH_ERR_STATE;
+    }
+    const size_t count = I.count[which], n0 = D.n;
+    if (count > S.n) { sph_set_error("sph_io_transfer: %zu selected rows of %zu", count, S.n); return SPH_ERR_STATE; }
+    if (count == 0) return SPH_OK;
+    SPH_TRY(io_list(c, src_id, which, 0, count));
+    const bool j_current = J.valid && J.nsel == n0;
+    SPH_TRY(sph_array_resize(c, dst_id, n0 + count, n0 + count)); // (grows through the capacity logic; marks h and m of the receiver unknown)
+    bool listed[SPH_PROP_COUNT] = {};
+    for (int k = 0; k < nprops; k++) listed[props[k]] = true;
+    IoXfer T;
+    int np = 0;
+    for (int p = 0; p < SPH_PROP_COUNT; p++) {
+        if (!D.prop[p]) continue;
+        T.d[np] = D.prop[p];
+        T.s[np] = (listed[p] && S.prop[p]) ? S.prop[p] : nullptr;
+        np++;
+    }
+    if (np)
+        hipLaunchKernelGGL(k_io_transfer, dim3(div_up(count, 256), (unsigned)np), dim3(256), 0, c->stream, T, c->dkeys.as<uint32_t>(), count, n0);
+    // the receiver's own selection stays what it was: the new rows have no class
+    if (j_current) {
+        SPH_TRY(J.code.reserve(n0 + count + 64, true, c->stream));
+        HIP_TRY(hipMemsetAsync(J.code.as<uint8_t>() + n0, 0xff, count, c->stream));
+        J.nsel = n0 + count;
+    } else {
+        J.valid = false;
+    }
+    if (listed[SPH_M]) D.m_mixed_ghosts = false;
+    D.perm_n = 0;               // (sph_nnps_reorder_array: not before the next update)
+    c->nnps_valid = false;
+    c->lag.valid = false;       // rows from another array may lie outside the previous update's bounds
+    if (!keep_source) SPH_TRY(sph_io_remove_selected(c, src_id, which, nullptr));
+    return SPH_OK;
+}
+
+extern "C" int sph_io_shift_selected(sph_ctx *c, int id, int which, int flags_id, double dx, double dy, double dz)
+{
+    SPH_TRY(io_selection(c, flags_id, which, "sph_io_shift_selected"));
+    SPH_TRY(io_check(c, id, "sph_io_shift_selected"));
+    HIP_TRY(hipSetDevice(c->device));
+    DevArray &A = c->arr[id];
+    const IoState &I = c->io[flags_id];
+    // (another array than the classified one: index-aligned with it, as the ghost inlet is with its inlet)
+    if (A.n != I.nsel) { sph_set_error("sph_io_shift_selected: array %d has %zu rows, the selection of array %d covers %zu", id, A.n, flags_id, I.nsel); return SPH_ERR_ARG; }
+    if (A.n == 0) return SPH_OK;
+    hipLaunchKernelGGL(k_io_shift, dim3(div_up(A.n, 256)), dim3(256), 0, c->stream, I.code.as<uint8_t>(), A.n, which, A.prop[SPH_X],
+                       A.prop[SPH_Y], A.prop[SPH_Z], dx, dy, dz);
+    c->nnps_valid = false;
+    c->lag.valid = false;
+    return SPH_OK;
+}

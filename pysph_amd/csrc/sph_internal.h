@@ -106,6 +106,17 @@ struct HaloState {
     size_t nsel = 0; // particles the flags of the last sph_halo_select cover
 };
 
+// open boundaries (sph_io_* in sph_halo.hip): the class of every row at the last sph_io_classify of the array -- the ioid of
+// the reference's IOEvaluate, 0 / 1 / 2, one byte per row (0xff: not classified: rows behind the real ones of a real_only
+// pass, rows a transfer appended since) -- and the three counts, on the host once a count read brought them
+struct IoState {
+    DevBuf code;
+    size_t nsel = 0;            // rows `code` covers; the selection is current while this is the array's n
+    bool valid = false;
+    bool counts_known = false;  // count[] below holds what the device counted
+    size_t count[3] = {0, 0, 0};
+};
+
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
 // T_N_*: launch counters only (no time): pair launches on EOS-fused records, launches that kept / reused neighbour lists
 enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 6, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_COUNT };
@@ -157,6 +168,8 @@ struct sph_ctx {
     bool own_stream = false;
     DevArray arr[SPH_MAX_ARRAYS];
     HaloState halo[SPH_MAX_ARRAYS];
+    IoState io[SPH_MAX_ARRAYS];
+    DevBuf io_counts;             // uint32 [SPH_MAX_ARRAYS][4]: the class counts of sph_io_classify, reduced on the device
 
     // grid of the last sph_nnps_update
     bool nnps_valid = false;

@@ -122,6 +122,11 @@ SIGNATURES = {
     'sph_nnps_set_ghost_faces': (C.c_int, [_P, C.c_int, C.c_double, C.c_double]),
     'sph_read_values': (C.c_int, [_P, C.c_int, C.POINTER(_P), _PD]),
     'sph_halo_remove_selected': (C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
+    'sph_io_classify': (C.c_int, [_P, C.c_int, _PD, C.c_double, C.c_int, C.POINTER(C.c_size_t)]),
+    'sph_io_counts': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    'sph_io_transfer': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    'sph_io_shift_selected': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
+    'sph_io_remove_selected': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     'sph_prop_register': (C.c_int, [C.c_char_p]),
     'sph_eval_generated': (C.c_int, [_P, _P, _P, C.c_double, C.c_double]),
     'sph_reduce_max': (C.c_int, [_P, C.c_int, C.c_int, _PD]),
@@ -538,7 +543,19 @@ class HipDeviceHelper(object):
         pa.resize(n)
         pa.set_num_real_particles(nreal)
         on_device = set(self.device_props())
+        self.host_stale = False
         for p in pa.properties:
+            st = getattr(pa, 'stride', {}).get(p, 1)
+            if st > 1 and get_npy(pa, p).dtype == np.float64:
+                # a strided property lives on the device as its components p__0 ...
+                comps = [prop_id('%s__%d' % (p, k)) for k in range(st)]
+                if n and all(c in on_device for c in comps):
+                    col = np.empty(n)
+                    for k, c in enumerate(comps):
+                        _check(self.lib.sph_array_pull(self.ctx._h, self.array_id, c,
+                                                       col.ctypes.data_as(_PD), 0, n))
+                        get_npy(pa, p)[k:n * st:st] = col
+                continue
             pid = prop_id(p)
             if pid not in on_device:
                 continue
@@ -736,6 +753,135 @@ class HipDeviceHelper(object):
         if align:
             out.align_particles()
         return out
+
+
+    # -- structural operations that stay on the device (open boundaries) ---------
+    # The rows to move are chosen ON the device (`classify_plane`: the ioid of the
+    # reference's IOEvaluate) and moved there; the host learns three counts.  The
+    # host ParticleArray follows in SHAPE only -- length, tag (all Local), pid --
+    # its float properties are stale until `pull` / `sync_host`, exactly as after
+    # a slab migration.  Order contract: appended rows arrive in ascending source
+    # index, removal is a stable compaction (as `remove_particles` above; the
+    # reference's ParticleArray.remove_particles fills holes from the end).
+    def _no_ghosts(self, what):
+        owner = getattr(self, 'ghost_owner', None)
+        if owner is not None or self.get_number_of_particles() != self.get_number_of_particles(True):
+            raise SphError(
+                "%s: array '%s' has device ghosts behind its real rows%s; open boundaries on "
+                "slab-decomposed / periodic arrays are not supported -- drop the ghosts through "
+                "their owner first" % (what, self._pa.name,
+                                       ' (managed by %s)' % owner if owner else ''))
+
+    def _host_follow(self):
+        """the host array takes the device's length; new rows are Local.  No
+        value is moved and, in the steady state, nothing is allocated: every
+        property becomes a view of the buffer it had, which is replaced (with
+        the device's head-room, zero-filled) only when it is outgrown -- a
+        million-particle fluid changes its length after almost every stage."""
+        from .particle_array import ParticleArray
+        pa = self._pa
+        n = self.get_number_of_particles()
+        if n != pa.get_number_of_particles():
+            if isinstance(pa, ParticleArray):
+                pid = get_npy(pa, 'pid')
+                rank = int(pid[0]) if pid.size else 0
+                for key, arr in list(pa.properties.items()):
+                    st = pa.stride.get(key, 1)
+                    base = arr.base if isinstance(arr.base, np.ndarray) and arr.base.ndim == 1 \
+                        and arr.base.dtype == arr.dtype else arr
+                    if base.size < n * st:
+                        base = np.zeros((n + n // 8 + 64) * st, dtype=arr.dtype)
+                        if key == 'pid' and rank:
+                            base[:] = rank
+                    pa.properties[key] = base[:n * st]
+                pa._n = n
+            else:
+                pa.resize(n)
+                get_npy(pa, 'tag')[:] = 0
+        pa.set_num_real_particles(n)
+        self._n = n
+        self.host_stale = True
+
+    def classify_plane(self, refpoint, normal, maxdist=1000.0, real_only=False, read=True):
+        """ioid of every row against the plane through `refpoint` with outward
+        `normal` (IOEvaluate, inlet_outlet_manager.py:349-406): written to the
+        device properties ioid / disp when the array has them, kept as the
+        array's selection.  Returns the counts (n0, n1, n2) -- one small
+        device->host read -- or None with read=False (`read_io_counts` then
+        reads those of several arrays at once)."""
+        self._sync_size()
+        plane = (C.c_double * 6)(*([float(v) for v in refpoint] + [float(v) for v in normal]))
+        out = (C.c_size_t * 3)()
+        _check(self.lib.sph_io_classify(self.ctx._h, self.array_id, plane, float(maxdist),
+                                        int(bool(real_only)), out if read else None))
+        return (int(out[0]), int(out[1]), int(out[2])) if read else None
+
+    @staticmethod
+    def read_io_counts(*helpers):
+        """[(n0, n1, n2)] of the last classify_plane of each helper, ONE read"""
+        h0 = helpers[0]
+        ids = (C.c_int * len(helpers))(*[h.array_id for h in helpers])
+        out = (C.c_size_t * (3 * len(helpers)))()
+        _check(h0.lib.sph_io_counts(h0.ctx._h, len(helpers), ids, out))
+        return [tuple(int(out[3 * k + j]) for j in range(3)) for k in range(len(helpers))]
+
+    def _transfer_ids(self, dest, props):
+        """device ids of the properties that travel: `props` (None: all) that
+        this array holds on the device and the destination's host array has"""
+        pa, pd = self._pa, dest._pa
+        mine = set(self.device_props())
+        ids = []
+        for key in (pa.properties if props is None else props):
+            if key not in pa.properties or key not in pd.properties:
+                continue
+            st = getattr(pa, 'stride', {}).get(key, 1)
+            for name in ([key] if st == 1 else ['%s__%d' % (key, k) for k in range(st)]):
+                pid = prop_id(name)
+                if pid >= 0 and pid in mine:
+                    _check(self.lib.sph_array_ensure_prop(dest.ctx._h, dest.array_id, pid))
+                    ids.append(pid)
+        return ids
+
+    def transfer_selected(self, dest_helper, ioid, props=None, keep=True):
+        """append this array's rows of class `ioid` to `dest_helper`'s array
+        (extract_particles(idx, dest_array, props), device_helper.py:660-672;
+        destination properties that are not copied read 0 on the new rows);
+        keep=False also removes them here.  Returns the number of rows moved."""
+        if dest_helper.ctx is not self.ctx:
+            raise SphError('transfer_selected: both arrays must live in one HipContext')
+        dest_helper._no_ghosts('transfer_selected')
+        if not keep:
+            self._no_ghosts('transfer_selected')
+        ids = self._transfer_ids(dest_helper, props)
+        arr = (C.c_int * max(len(ids), 1))(*ids)
+        n0 = dest_helper.get_number_of_particles()
+        _check(self.lib.sph_io_transfer(self.ctx._h, self.array_id, dest_helper.array_id, int(ioid),
+                                        len(ids), arr, int(bool(keep))))
+        moved = dest_helper.get_number_of_particles() - n0
+        if moved:
+            dest_helper._host_follow()
+            if not keep:
+                self._host_follow()
+        return moved
+
+    def remove_selected(self, ioid):
+        """delete this array's rows of class `ioid` (stable); returns how many"""
+        self._no_ghosts('remove_selected')
+        left = C.c_size_t()
+        n0 = self.get_number_of_particles()
+        _check(self.lib.sph_io_remove_selected(self.ctx._h, self.array_id, int(ioid), C.byref(left)))
+        if left.value != n0:
+            self._host_follow()
+        return n0 - left.value
+
+    def shift_selected(self, ioid, dx, dy, dz, flags=None):
+        """x, y, z += (dx, dy, dz) on the rows whose INDEX has class `ioid` in the
+        selection of `flags` (another helper with as many rows; default: this
+        array's own selection)"""
+        flags = self if flags is None else flags
+        _check(self.lib.sph_io_shift_selected(self.ctx._h, self.array_id, int(ioid), flags.array_id,
+                                              float(dx), float(dy), float(dz)))
+        self.host_stale = True
 
 
 _HELPERS = {}
