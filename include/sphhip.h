@@ -375,6 +375,39 @@ int sph_eval_generated(sph_ctx *ctx, const sph_kernel *kernel, sph_gen_family *f
 int sph_reduce_max(sph_ctx *ctx, int array_id, int prop, double *out);
 
 /* ---------------------------------------------------------------------- */
+/* interpolation of particle fields onto points                             */
+/* replaces the equations pysph/tools/interpolator.py builds for its         */
+/* AccelerationEval (:454-498) and the per-property evaluation of            */
+/* Interpolator.interpolate (:343-381).                                      */
+/* ---------------------------------------------------------------------- */
+enum sph_interp_method {
+    SPH_INTERP_SHEPARD = 0,     /* InterpolateFunction, interpolator.py:18-29: sum W_ij f_j / sum W_ij */
+    SPH_INTERP_SPH = 1,         /* InterpolateSPH :32-37: sum (m_j / rho_j) W_ij f_j */
+    SPH_INTERP_ORDER1 = 2,      /* SummationDensity + SPHFirstOrderApproximationPreStep :64-103 + SPHFirstOrderApproximation
+                                 * :106-172 (Liu & Liu 2006): value and gradient from the moment matrix */
+    SPH_INTERP_SPLASH = 3,      /* SPLASHInterpolateProperty :40-45: as SPH with W(r, h_i) of the point */
+    SPH_INTERP_SPLASH_NORM = 4  /* SPLASHInterpolatePropertyNormalized :48-61: W(r, h_j) of the particle, normalised */
+};
+#define SPH_INTERP_MAX_PROPS 64
+/* Interpolate `nprops` properties of the `nsrc` source arrays onto the particles of array `dest` (the interpolation
+ * points: x, y, z, h on the device) in ceil(nprops / 4) neighbour sweeps.  out_props: the destination properties that
+ * receive the results -- one per property, or four per property for SPH_INTERP_ORDER1 (value, d/dx, d/dy, d/dz;
+ * components beyond the kernel's dim are 0); -1 skips an output.  With host_out != NULL the results take no destination
+ * property at all (out_props is ignored and may be NULL; user property slots are a small process-wide table): they are
+ * written to a private device block and the first n_pull points of every result row are copied to
+ * host_out[row * n_pull ...] (rows in the order of out_props) before the call returns.  Every accumulator starts from
+ * zero on every call; a candidate outside the neighbour criterion adds exactly zero whatever its record holds.
+ * A source array without device storage for a property contributes the value 0 for it (interpolator.py:360-366) and
+ * still counts in the denominators.  SPH_INTERP_ORDER1 takes V_j = m_j / rho_j with the summation density over all
+ * source arrays (all particles, ghosts included: the real=False group of :479-482) from a private buffer -- the
+ * sources' rho is NOT overwritten -- and keeps the moment matrices until the next sph_nnps_update or write of h / m
+ * (sph_timer_get "n_interp_moment" counts the moment passes, "n_interp_sweep" the property sweeps).  fp64 always:
+ * options arith_f32 / record_f32 do not apply.  Needs a valid sph_nnps_update over the sources and `dest`
+ * (SPH_ERR_STATE otherwise); bad ids, more than SPH_MAX_ARRAYS arrays or an unknown method are SPH_ERR_ARG.       */
+int sph_interpolate(sph_ctx *ctx, const sph_kernel *kernel, int method, int dest, int nsrc, const int *srcs,
+                    int nprops, const int *props, const int *out_props, double *host_out, size_t n_pull);
+
+/* ---------------------------------------------------------------------- */
 /* ghost-particle halos (slab decomposition, one process per GPU)           */
 /* replaces ParallelManager.compute_remote_particles / remote_exchange_data */
 /* (pysph/parallel/parallel_manager.pyx:1159-1243, :159-210); the transport */

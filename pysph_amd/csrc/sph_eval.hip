@@ -2707,3 +2707,8 @@ static int reduce_minmax(sph_ctx *c, int id, int prop, double *out, bool want_ma
     *out = sgn * c->pinned[0];
     return SPH_OK;
 }
+
+// ---------------------------------------------------------------------------
+// interpolation of particle fields onto points (sph_interpolate)
+// ---------------------------------------------------------------------------
+#include "sph_interp.h"

@@ -119,7 +119,8 @@ struct IoState {
 
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
 // T_N_*: launch counters only (no time): pair launches on EOS-fused records, launches that kept / reused neighbour lists
-enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 6, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_COUNT };
+// T_N_INTERP_MOM / _SWEEP: moment passes / property sweeps of sph_interpolate
+enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 6, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_COUNT };
 
 struct Timer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -290,6 +291,13 @@ struct sph_ctx {
     struct { bool valid = false; unsigned long long epoch = 0; int dst = -1, src = -1; size_t start = 0, stop = 0, nd = 0; } nl;
     unsigned long long nnps_epoch = 0; // bumped by every sph_nnps_update
     double h_known[2] = {0.0, -1.0};   // sph_nnps_set_h_range: hmin, hmax (hmax < 0: unknown)
+
+    // sph_interpolate (sph_interp.h): m / rho and the private summation density of every source array (original order), and
+    // the moment matrices of the first-order method with what they were computed for
+    DevBuf interp_vol[SPH_MAX_ARRAYS], interp_vol1[SPH_MAX_ARRAYS], interp_rho[SPH_MAX_ARRAYS], // (interp_vol1: m / summation density, order1's own)
+           interp_mom, interp_out; // interp_out: results on their way to the host
+    struct { bool valid = false; unsigned long long epoch = 0; int dest = -1, nsrc = 0, srcs[SPH_MAX_ARRAYS] = {}, kind = 0, dim = 0;
+             double fac = 0; size_t nd = 0; unsigned hm_writes = 0; } interp_mc;
 
     void *comm = nullptr;   // SphComm of libsphcomm.so (sph_comm.hip), or nullptr
 

@@ -130,6 +130,8 @@ SIGNATURES = {
     'sph_prop_register': (C.c_int, [C.c_char_p]),
     'sph_eval_generated': (C.c_int, [_P, _P, _P, C.c_double, C.c_double]),
     'sph_reduce_max': (C.c_int, [_P, C.c_int, C.c_int, _PD]),
+    'sph_interpolate': (C.c_int, [_P, C.POINTER(SphKernel), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                  C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _PD, C.c_size_t]),
     'sph_reduce_min': (C.c_int, [_P, C.c_int, C.c_int, _PD]),
     'sph_integrate_stage': (C.c_int, [_P, C.c_int, C.c_int, C.c_int,
                                       C.c_double]),

@@ -94,14 +94,17 @@ def create_particles(dx=0.02, hdx=hdx):
 
 
 def run(dx=0.04, n_steps=20, tf=None, cfl=0.3, reorder_freq=50, ctx=None,
-        adaptive=True, log=None):
+        adaptive=True, log=None, probe=None):
     """The time loop of ``Solver.solve`` (pysph/solver/solver.py:430-520) for
     this problem with everything device-resident: EPEC integrator with
     ``WCSPHStep`` for the fluid (boundary and obstacle have no stepper, as in
     ``WCSPHScheme.configure_solver`` scheme.py:360-386), adaptive time step
     from the device reductions (integrator.py:161-200), particles re-ordered
     into cell order every ``reorder_freq`` steps (solver.py:296-302).  One push
-    before the loop, one pull after.  Returns (arrays, stats)."""
+    before the loop, one pull after.  `probe`: an optional callable
+    ``(step, t, arrays, ctx)`` invoked after each step, e.g. to sample the
+    device-resident state through ``pysph_amd.tools.Interpolator(ctx=ctx,
+    sync=False)`` (examples/probe_slice.py).  Returns (arrays, stats)."""
     import time
 
     from .. import device as dev
@@ -139,6 +142,8 @@ def run(dx=0.04, n_steps=20, tf=None, cfl=0.3, reorder_freq=50, ctx=None,
                 dt = new
         if log and step % log == 0:
             print('step %d  t = %.5f  dt = %.3e' % (step, t, dt))
+        if probe is not None:
+            probe(step, t, arrays, ctx)
     ctx.synchronize()
     wall = time.perf_counter() - t0
     for a in arrays:

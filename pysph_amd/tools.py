@@ -7,10 +7,14 @@ Same constructor arguments and methods (``evaluate``, ``update``,
 reference's, the default neighbour search is ``HipNNPS``.  Host arrays stay
 authoritative (``sync='auto'``): inputs are pushed before and results pulled
 after every ``evaluate``.
+
+``Interpolator`` (pysph/tools/interpolator.py) lives in
+``pysph_amd/interpolator.py`` and is re-exported here.
 """
 from .acceleration_eval import AccelerationEval, SPHCompiler
 from .kernels import Gaussian
 from .nnps import HipNNPS
+from .interpolator import Interpolator, get_bounding_box, get_nx_ny_nz  # noqa: F401
 
 
 class SPHEvaluator(object):
