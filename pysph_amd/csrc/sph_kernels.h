@@ -60,24 +60,26 @@ template <> struct SphKernel<1> { // CubicSpline
     }
 };
 
+// The reference tests q < 2 (kernels.py:318); at q == 2 the polynomial is an exact zero (t = 0), so q <= 2 returns the
+// same value -- and the same bits, sign of the zero included, as INSUP = true, which has no test at all.
 template <> struct SphKernel<2> { // WendlandQuintic
     static constexpr bool HAS_DWQ = true; // dw/q = -5 (1 - q/2)^3: no division by r needed
     template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q)
     {
         R t = R(1) - R(0.5) * q;
-        return (INSUP || q < R(2)) ? R(-5) * t * t * t : R(0);
+        return (INSUP || q <= R(2)) ? R(-5) * t * t * t : R(0);
     }
     template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q)
     {
         R t = R(1) - R(0.5) * q;
         R v = t * t * t * t * (R(2) * q + R(1));
-        return (INSUP || q < R(2)) ? v : R(0);
+        return (INSUP || q <= R(2)) ? v : R(0);
     }
     template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q)
     {
         R t = R(1) - R(0.5) * q;
         R v = R(-5) * q * t * t * t;
-        return (INSUP || q < R(2)) ? v : R(0);
+        return (INSUP || q <= R(2)) ? v : R(0);
     }
 };
 

@@ -158,7 +158,9 @@ template <class F> struct fam_eosf<F, decltype((void)F::EOSF)> { static constexp
 // ---------------------------------------------------------------------------
 // fast fp64 reciprocal / square root: hardware estimate (v_rcp_f64 / v_rsq_f64,
 // ~2^-26 relative) + SPH_NEWTON_STEPS Newton steps: one step leaves ~1e-14
-// relative (measured: tools/microbench/rcp_accuracy.hip), two ~1 ulp.  No
+// relative (measured: tools/microbench/rcp_accuracy.hip; asserted over
+// [2^-200, 2^200] by tests/test_device_functions.py: rcp 2.0e-15, sqrt and
+// rsqrt 4.0e-15), two ~1 ulp.  No
 // div_scale/div_fixup range handling -- operands here are densities, distances
 // and smoothing lengths, far from the fp64 range limits.  The 1e-10 parity
 // budget (BASELINE.json) is four orders of magnitude above the one-step error;
@@ -295,6 +297,18 @@ template <int KK, bool UH, class T> __device__ __forceinline__ T pair_gradfac(co
     if (SphKernel<KK>::HAS_DWQ) t = SphKernel<KK>::template dwq<UH>(g.q) * (g.fac * g.h1 * g.h1);
     else t = SphKernel<KK>::template dw<UH>(g.q) * (g.fac * g.h1) * g.rinv;
     return g.rij > T(1e-12) ? t : T(0);
+}
+
+// Absolute slack of the fp32 prefilter for ONE particle: 1.5e-6 of the largest magnitude its fp32 coordinates can
+// take.  Inside the grid that is the row window / the grid's extent L (wave-uniform `slack`); a particle OUTSIDE the
+// grid (clamped into the outermost cells: fixed bounds, ghosts, a lagged update) has |fpos| beyond the extent and
+// its rounding, 2^-24 |fpos| per coordinate, grows with it: then 3e-6 |fpos| (|fpos - origin| <= 2 |fpos| there).
+// A true neighbour j of i has |fpos_j| <= |fpos_i| + radius_scale * h, so the slack of either end of the pair covers
+// the rounding of both.
+__device__ __forceinline__ float prefilter_slack(const float4 &fp, float slack, float dom_extent)
+{
+    const float am = fmaxf(fmaxf(fabsf(fp.x), fabsf(fp.y)), fabsf(fp.z));
+    return am > dom_extent ? fmaxf(slack, am * 3.0e-6f) : slack;
 }
 
 // Record access of the pair kernel.  Default layout: [x y z h | aux...].
@@ -597,8 +611,9 @@ __global__ __launch_bounds__(64 * WPB, Fam::MINB) void k_pair_wave(PairArgs<Fam>
         const int ncs = xb - xa + 2; // fine_start entries needed: bins xa..xb and the end
         const double binw = a.cell_size * (1.0 / SPH_NSUB);
         // fp32 coordinates: grid-relative positions (fpos, rounded once from
-        // fp64) minus this row segment's origin; every value carries at most
-        // 2^-24 * dom_extent of rounding, covered by `slack`
+        // fp64) minus this row segment's origin; inside the grid every value carries at
+        // most 2^-24 * dom_extent of rounding, covered by `slack`; a particle outside the
+        // grid gets a slack of its own (prefilter_slack)
         const float oxf = (float)(binw * xa);
         const float oyf = (float)(a.cell_size * (cyR - 1));
         const float ozf = (float)(a.cell_size * (czR - 1));
@@ -607,7 +622,7 @@ __global__ __launch_bounds__(64 * WPB, Fam::MINB) void k_pair_wave(PairArgs<Fam>
         const float4 fpi = a.fpos[a.d_off + ic];
         const float fxs = fpi.x - oxf, fys = fpi.y - oyf, fzs = fpi.z - ozf;
         const f2 fx = {fxs, fxs}, fy = {fys, fys}, fz = {fzs, fzs};
-        const float hif = (float)hi_r * 1.000001f + slack;
+        const float hif = (float)hi_r * 1.000001f + prefilter_slack(fpi, slack, (float)a.dom_extent);
         const float hi2f = hif * hif;
         const int mycl = max(cx - XWIN, xa) - xa, mych = min(cx + XWIN, xb) + 1 - xa;
 
@@ -636,7 +651,7 @@ __global__ __launch_bounds__(64 * WPB, Fam::MINB) void k_pair_wave(PairArgs<Fam>
                     if (k < tn) {
                         const float4 fj = a.fpos[sd.off + tb + k];
                         vx = fj.x - oxf; vy = fj.y - oyf; vz = fj.z - ozf;
-                        const float hjf = fj.w * 1.000001f + slack;
+                        const float hjf = fj.w * 1.000001f + (UH ? slack : prefilter_slack(fj, slack, (float)a.dom_extent));
                         vw = hjf * hjf;
                     }
                     tx[k] = vx; ty[k] = vy; tz[k] = vz;
@@ -848,7 +863,7 @@ __global__ __launch_bounds__(64, Fam::MINB) void k_pair_rowlds(PairArgs<Fam> a)
             const float slack = (float)(L * 1.5e-6);
             const float fxs = fpi.x - oxf, fys = fpi.y - oyf, fzs = fpi.z - ozf;
             const f2 fx = {fxs, fxs}, fy = {fys, fys}, fz = {fzs, fzs};
-            const float hif = (float)hi_r * 1.000001f + slack;
+            const float hif = (float)hi_r * 1.000001f + prefilter_slack(fpi, slack, (float)a.dom_extent);
             const float hi2f = hif * hif;
             const int mycl = max(cx - XWIN, xa) - xa, mych = min(cx + XWIN, xb) + 1 - xa;
             for (int st = 0; st < 9; st++) {

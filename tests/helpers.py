@@ -1,5 +1,7 @@
 """Shared builders for the parity tests (equation sets named like the
 reference's schemes)."""
+import os
+
 import numpy as np
 
 from pysph_amd import kernels as K
@@ -195,3 +197,191 @@ def device_add(pa, prop, delta, n=None):
     t += torch.from_numpy(np.ascontiguousarray(delta[:n], dtype=np.float64)).to(t.device)
     torch.cuda.synchronize()
     pa.properties[prop][:n] += delta[:n]
+
+
+# ---------------------------------------------------------------------------
+# Device-function probes (tests/probes/device_functions.hip) and their
+# high-precision reference
+# ---------------------------------------------------------------------------
+_TESTS = os.path.dirname(os.path.abspath(__file__))
+_REPO = os.path.dirname(_TESTS)
+PROBE_SRC = os.path.join(_TESTS, 'probes', 'device_functions.hip')
+KERNEL_NAMES = {1: 'CubicSpline', 2: 'WendlandQuintic', 3: 'QuinticSpline', 4: 'Gaussian'}
+KERNEL_SUPPORT = {1: 2.0, 2: 2.0, 3: 3.0, 4: 3.0}
+KERNEL_KNOTS = {1: (1.0,), 2: (), 3: (1.0, 2.0), 4: ()}
+PAIR_OUT = ('rij', 'rinv', 'hij', 'h1', 'q', 'fac', 'eps', 'w', 'gradfac', 'gradh')
+
+
+def _probe_command(out):
+    """hipcc with exactly the CXXFLAGS of pysph_amd/csrc/Makefile (read from it, so that the probe is optimised and
+    contracted like the product) + -shared."""
+    import re
+    csrc = os.path.join(_REPO, 'pysph_amd', 'csrc')
+    flags = None
+    with open(os.path.join(csrc, 'Makefile')) as f:
+        for line in f:
+            m = re.match(r'CXXFLAGS\s*=\s*(.*)', line)
+            if m:
+                flags = m.group(1).split()
+                break
+    assert flags, 'no CXXFLAGS in pysph_amd/csrc/Makefile'
+    flags = [x.replace('$(ARCH)', 'gfx950') for x in flags]
+    flags = ['-I' + os.path.normpath(os.path.join(csrc, x[2:])) if x.startswith('-I') else x for x in flags]
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    return [hipcc] + flags + ['-I' + csrc, '-shared', PROBE_SRC, '-o', out]
+
+
+def probe_library_path():
+    """content-addressed: the probe's own source, everything srchash covers (csrc/, include/) and the command line"""
+    import hashlib
+    import sys
+    sys.path.insert(0, os.path.join(_REPO, 'pysph_amd', 'csrc'))
+    import srchash
+    from pysph_amd import codegen
+    h = hashlib.sha256()
+    with open(PROBE_SRC, 'rb') as f:
+        h.update(f.read())
+    h.update(srchash.source_hash().encode())
+    h.update(' '.join(_probe_command('')[1:]).encode())
+    return os.path.join(codegen.GEN_DIR, 'probe_device_functions_%s.so' % h.hexdigest()[:16])
+
+
+def build_probe_library():
+    """The probe library next to the generated families' shared objects (built by tests/prebuild_generated.py, so it
+    travels with the tree); compiled here when it is missing.  No hipcc and no library is an error, not a skip."""
+    import shutil
+    import subprocess
+    so = os.environ.get('SPH_PROBE_LIBRARY') or probe_library_path()      # like SPH_LIBRARY: one built elsewhere
+    if os.path.exists(so):
+        return so
+    cmd = _probe_command(so + '.tmp%d' % os.getpid())
+    if not (os.path.isfile(cmd[0]) or shutil.which(cmd[0])):
+        raise RuntimeError('%s is missing and there is no hipcc (%s) to build it' % (so, cmd[0]))
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    subprocess.check_call(cmd)
+    os.replace(cmd[-1], so)
+    return so
+
+
+_PROBE = []
+
+
+def probe_library():
+    import ctypes as C
+    if not _PROBE:
+        lib = C.CDLL(build_probe_library())
+        vp, i, d = C.c_void_p, C.c_int, C.c_double
+        lib.probe_kernel.argtypes = [i, i, i, i, vp, vp, vp, vp]
+        lib.probe_rcp.argtypes = [i, i, vp, vp]
+        lib.probe_sqrt_rsqrt.argtypes = [i, i, vp, vp, vp]
+        lib.probe_pair.argtypes = [i, i, i, i, vp, vp, vp, d, i, d, d, d, d, vp]
+        _PROBE.append(lib)
+    return _PROBE[0]
+
+
+def _vp(a):
+    return a.ctypes.data
+
+
+def probe_kernel(kk, insup, q):
+    """device SphKernel<kk>::w/dw/dwq<insup>(q); the dtype of q (float64 / float32) selects the arithmetic"""
+    q = np.ascontiguousarray(q)
+    out = [np.empty_like(q) for _ in range(3)]
+    rc = probe_library().probe_kernel(kk, int(insup), int(q.dtype == np.float32), q.size, _vp(q), *map(_vp, out))
+    assert rc == 0, 'probe_kernel: HIP error %d' % rc
+    return out
+
+
+def probe_rcp(x):
+    x = np.ascontiguousarray(x)
+    r = np.empty_like(x)
+    rc = probe_library().probe_rcp(int(x.dtype == np.float32), x.size, _vp(x), _vp(r))
+    assert rc == 0, 'probe_rcp: HIP error %d' % rc
+    return r
+
+
+def probe_sqrt_rsqrt(x):
+    x = np.ascontiguousarray(x)
+    s, rs = np.empty_like(x), np.empty_like(x)
+    rc = probe_library().probe_sqrt_rsqrt(int(x.dtype == np.float32), x.size, _vp(x), _vp(s), _vp(rs))
+    assert rc == 0, 'probe_sqrt_rsqrt: HIP error %d' % rc
+    return s, rs
+
+
+def probe_pair(kk, uh, r2, hi, hj, sigma, dim, uniform=(0.0, 0.0, 0.0, 0.0)):
+    """device pair_geom<kk, uh> + pair_w / pair_gradfac / pair_gradh; dict of the PAIR_OUT arrays"""
+    r2 = np.ascontiguousarray(r2)
+    hi = np.ascontiguousarray(hi, dtype=r2.dtype)
+    hj = np.ascontiguousarray(hj, dtype=r2.dtype)
+    assert hi.size == r2.size and hj.size == r2.size
+    out = np.empty((len(PAIR_OUT), r2.size), dtype=r2.dtype)
+    rc = probe_library().probe_pair(kk, int(uh), int(r2.dtype == np.float32), r2.size, _vp(r2), _vp(hi), _vp(hj),
+                                    float(sigma), int(dim), *[float(u) for u in uniform], _vp(out))
+    assert rc == 0, 'probe_pair: HIP error %d' % rc
+    return dict(zip(PAIR_OUT, out))
+
+
+def mp_kernel(kk, q):
+    """(W(q), dW/dq(q)) without the normalisation, at mpmath's working precision, from the formulas and branch
+    conditions of the reference's pysph/base/kernels.py (CubicSpline.kernel/dwdq, WendlandQuintic, QuinticSpline,
+    Gaussian) -- NOT from pysph_amd/kernels.py -- with ITS operations in ITS order (Python evaluates a * b * c as
+    (a * b) * c).  At 50 digits the order is immaterial; at a working precision of 53 bits mpmath rounds every
+    operation to nearest like IEEE double, and the same lines then retrace the reference's own fp64 evaluation
+    rounding by rounding -- which is how the formulas are pinned against tests/golden/kernels.npz before anything is
+    judged by them.  q: an mpf (a double or float converts exactly).  The reference's rij > 1e-12 guard of dwdq
+    belongs to the caller (it tests rij, not q)."""
+    import mpmath as mp
+    q = mp.mpf(q)
+    f = mp.mpf
+    if kk == 1:
+        tmp2 = 2 - q
+        if q > 2:
+            return f(0), f(0)
+        if q > 1:
+            return f(0.25) * tmp2 * tmp2 * tmp2, f(-0.75) * tmp2 * tmp2
+        return 1 - f(1.5) * q * q * (1 - f(0.5) * q), f(-3) * q * (1 - f(0.75) * q)
+    if kk == 2:
+        tmp = 1 - f(0.5) * q
+        if q < 2:
+            return tmp * tmp * tmp * tmp * (2 * q + 1), f(-5) * q * tmp * tmp * tmp
+        return f(0), f(0)
+    if kk == 3:
+        tmp3, tmp2, tmp1 = 3 - q, 2 - q, 1 - q
+        if q > 3:
+            return f(0), f(0)
+        w = tmp3 * tmp3 * tmp3 * tmp3 * tmp3
+        dw = f(-5) * tmp3 * tmp3 * tmp3 * tmp3
+        if q <= 2:
+            w -= f(6) * tmp2 * tmp2 * tmp2 * tmp2 * tmp2
+            dw += f(30) * tmp2 * tmp2 * tmp2 * tmp2
+        if q <= 1:
+            w += f(15) * tmp1 * tmp1 * tmp1 * tmp1 * tmp1
+            dw -= f(75) * tmp1 * tmp1 * tmp1 * tmp1
+        return w, dw
+    if kk == 4:
+        if q < 3:
+            return mp.exp(-q * q), f(-2) * q * mp.exp(-q * q)
+        return f(0), f(0)
+    raise KeyError(kk)
+
+
+def mp_kernel_wdw(kk, r, h, sigma, dim, xij=None):
+    """the reference's kernel(rij, h) and dwdq(rij, h) -- and, with xij, gradient(xij, rij, h) -- at mpmath's working
+    precision, operation by operation as the reference writes them (fac = self.fac * h1 * h1 * h1, val * fac,
+    wdash * h1 / rij * xij).  Its h1 = 1 / h and q = rij * h1 are formed in the arithmetic of the inputs' type: that
+    rounding is the reference's definition of q, not an error of W."""
+    import mpmath as mp
+    one = type(r)(1)
+    h1 = one / h
+    q = r * h1
+    w, dw = mp_kernel(kk, q)
+    fac = mp.mpf(float(sigma))
+    for _ in range(dim):
+        fac = fac * mp.mpf(h1)
+    if not r > 1e-12:
+        dw = mp.mpf(0)
+    w, dw = w * fac, dw * fac
+    if xij is None:
+        return w, dw
+    tmp = dw * mp.mpf(h1) / mp.mpf(r) if r > 1e-12 else mp.mpf(0)
+    return w, dw, [tmp * mp.mpf(float(c)) for c in xij]

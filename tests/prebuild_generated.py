@@ -131,3 +131,6 @@ if __name__ == '__main__':
     main()
     print('compiled in parallel:', codegen.build_deferred())
     print('generated families built:', main())
+    # the device-function probes of tests/test_device_functions.py (tests/probes/device_functions.hip)
+    from helpers import build_probe_library
+    print('probe library:', os.path.relpath(build_probe_library(), os.path.dirname(HERE)))
