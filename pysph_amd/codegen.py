@@ -31,6 +31,51 @@ built, like equation.py:885-892 does), ``d_<prop>[d_idx]``,
 VIJ R2IJ RIJ HIJ RHOIJ RHOIJ1 EPS WIJ DWIJ WI WJ DWI DWJ WDP t dt``
 (equation.py:188-297).  Anything else raises ``CodegenError`` -- the equation
 then has to be hand-written or simplified; there is no silent fallback.
+
+What a translated body computes is what CPython computes when it runs the same
+body on floats (tests/test_codegen_semantics.py compares the two construct by
+construct on an MI355X):
+
+=====================================  ========================================
+bit-identical to CPython               + - * / (``/`` is a true division also of
+(with ``_fp_contract_ = False``,       two integers), ``%`` (sign of the divisor,
+else up to which products the          float_rem), comparisons and chains,
+compiler fuses into an fma)            ``and / or`` as values (an operand, not
+                                       0 / 1) and in conditions, ``not``,
+                                       conditional expressions, ``max / min``
+                                       (the first of equal arguments, signed
+                                       zeros included), ``abs fabs sqrt fmod``,
+                                       ``floor / ceil`` (``math``: a zero result
+                                       is +0, as the int Python returns;
+                                       ``np``: the sign is kept),
+                                       integer locals and counters (a declared
+                                       counter keeps its last value after the
+                                       loop, ``range`` takes its bounds once),
+                                       ``i ** k`` with a literal k <= 8, tuple
+                                       assignment, helpers, constants, ``self.*``
+device libm, worst error measured on   ``x ** 2`` (a product) 0.50, pow / ``**``
+an MI355X in ulp of the result         1.11, exp 0.73, log 0.50, log10 0.45, sin
+                                       0.57, cos 0.57, tan 0.61, tanh 0.55, asin
+                                       0.61, acos 0.68, atan 0.73, sinh 0.51,
+                                       cosh 0.51, erf 0.74, atan2 1.16
+                                       (the tests hold each to 4)
+raises ``CodegenError``                ``k /= ..``, ``k += <float>``, ``k =
+                                       <float expression>`` on a declared int
+                                       (Python would keep the float); a value
+                                       use of an int read from a property
+                                       (``idx = d_orig_idx[d_idx]`` serves as an
+                                       index only); an assignment to the
+                                       counter of a running loop; a negative
+                                       subscript; ``//``, ``while``, ...
+differs by design                      where CPython raises (division by zero,
+                                       sqrt / log of a negative number, pow
+                                       overflow, a non-integral index) the
+                                       device code gives C's inf / NaN / cast;
+                                       integers are 32-bit
+=====================================  ========================================
+
+``max`` / ``min`` follow Python also for a NaN argument (it is kept or dropped
+by its position); the tests hold no NaN inputs.
 """
 import ast
 import ctypes as C
@@ -174,6 +219,7 @@ class _Body(object):
         self.loop_vars = set()
         self.unrolled = {}          # loop variables of statically unrolled loops -> value
         self.affine_ints = {}       # int locals with a known value a*d_idx + b*s_idx + c
+        self.index_only = set()     # int locals read from a (double) property: usable as an index only
         self.where = '%s.%s' % (type(eq).__name__, kind)
         self.lines = []
         fam._writes = set()
@@ -306,6 +352,82 @@ class _Body(object):
                         changed = True
         return out
 
+    # -- Python / C types of expressions --------------------------------------
+    def _int_name(self, n):
+        return isinstance(n, ast.Name) and n.id not in self.unrolled and (
+            n.id in self.loop_vars or self.locals.get(n.id, ('',))[0] == 'int'
+            or (n.id == 'N_NBRS' and self.all_nbrs))
+
+    def _py_int(self, n):
+        """CPython evaluates `n` to an int (or bool) whatever the particle data"""
+        if isinstance(n, ast.Constant):
+            return isinstance(n.value, int)
+        if isinstance(n, ast.Name):
+            return self._int_name(n) or n.id in self.unrolled or n.id in ('d_idx', 's_idx')
+        if isinstance(n, ast.Attribute):
+            return isinstance(n.value, ast.Name) and n.value.id == 'self' and self.eq is not None \
+                and isinstance(getattr(self.eq, n.attr, None), int)
+        if isinstance(n, ast.Subscript):
+            return isinstance(n.value, ast.Name) and n.value.id == 'NBRS' and self.all_nbrs
+        if isinstance(n, ast.Compare):
+            return True
+        if isinstance(n, ast.UnaryOp):
+            return isinstance(n.op, ast.Not) or self._py_int(n.operand)
+        if isinstance(n, ast.BinOp):
+            if isinstance(n.op, (ast.Add, ast.Sub, ast.Mult, ast.Mod)):
+                return self._py_int(n.left) and self._py_int(n.right)
+            if isinstance(n.op, ast.Pow):
+                return self._py_int(n.left) and isinstance(n.right, ast.Constant) and \
+                    isinstance(n.right.value, int) and n.right.value >= 0
+            return False
+        if isinstance(n, ast.IfExp):
+            return self._py_int(n.body) and self._py_int(n.orelse)
+        if isinstance(n, ast.BoolOp):
+            return all(self._py_int(v) for v in n.values)
+        return False
+
+    def _small_power(self, n):
+        """``x ** 2``, and ``i ** k`` of an integer with a literal k in 1..8 (exact, as Python's integer
+        power is): written as a product"""
+        k = n.right.value if isinstance(n.right, ast.Constant) else None
+        if isinstance(k, bool) or not isinstance(k, (int, float)):
+            return False
+        if k == 2:                          # 2.0 as well
+            return True
+        return isinstance(k, int) and 1 <= k <= 8 and self._py_int(n.left)
+
+    def _c_int(self, n):
+        """the text `expr(n)` emits has an integral C type (int or bool)"""
+        if isinstance(n, ast.Name):
+            return self._int_name(n)
+        if isinstance(n, ast.Subscript):
+            return isinstance(n.value, ast.Name) and n.value.id == 'NBRS' and self.all_nbrs
+        if isinstance(n, ast.Compare):
+            return True
+        if isinstance(n, ast.UnaryOp):
+            return isinstance(n.op, ast.Not) or self._c_int(n.operand)
+        if isinstance(n, ast.BinOp):
+            if isinstance(n.op, (ast.Add, ast.Sub, ast.Mult)):
+                return self._c_int(n.left) and self._c_int(n.right)
+            if isinstance(n.op, ast.Pow):
+                return self._small_power(n) and self._c_int(n.left)
+            return False
+        if isinstance(n, ast.IfExp):
+            return self._c_int(n.body) and self._c_int(n.orelse)
+        if isinstance(n, ast.BoolOp):
+            return all(self._c_int(v) for v in n.values)
+        return False
+
+    def cond(self, n):
+        """`n` where only its truth matters (if / conditional-expression tests,
+        the operand of ``not``): and / or / not are the C operators"""
+        if isinstance(n, ast.BoolOp):
+            op = ' && ' if isinstance(n.op, ast.And) else ' || '
+            return '(' + op.join('(%s)' % self.cond(v) for v in n.values) + ')'
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, ast.Not):
+            return '(!(%s))' % self.cond(n.operand)
+        return self.expr(n)
+
     # -- expressions -------------------------------------------------------
     def expr(self, n):
         if isinstance(n, ast.Constant):
@@ -334,26 +456,38 @@ class _Body(object):
             if isinstance(n.op, ast.Mult):
                 return '(%s * %s)' % (a, b)
             if isinstance(n.op, ast.Div):
+                # true division: an operand C types as an integer goes through the arithmetic type
+                if self._c_int(n.left):
+                    a = '(double)%s' % a
+                if self._c_int(n.right):
+                    b = '(double)%s' % b
                 return '(%s / %s)' % (a, b)
             if isinstance(n.op, ast.Mod):
-                return 'fmod(%s, %s)' % (a, b)
+                self.fam.pyfuncs.add('mod')
+                return 'gen_pymod(%s, %s)' % (a, b)      # sign of the divisor (CPython float_rem)
             if isinstance(n.op, ast.Pow):
-                if isinstance(n.right, ast.Constant) and n.right.value == 2:
-                    return '(%s * %s)' % (a, a)
+                if self._small_power(n):
+                    return '(%s)' % ' * '.join([a] * int(n.right.value))
                 return 'pow(%s, %s)' % (a, b)
             self.err(n, 'operator %s' % type(n.op).__name__)
         if isinstance(n, ast.UnaryOp):
+            if isinstance(n.op, ast.Not):
+                return self.cond(n)
             v = self.expr(n.operand)
             if isinstance(n.op, ast.USub):
                 return '(-%s)' % v
             if isinstance(n.op, ast.UAdd):
                 return v
-            if isinstance(n.op, ast.Not):
-                return '(!(%s))' % v
             self.err(n, 'unary operator')
         if isinstance(n, ast.BoolOp):
-            op = ' && ' if isinstance(n.op, ast.And) else ' || '
-            return '(' + op.join('(%s)' % self.expr(v) for v in n.values) + ')'
+            # as a VALUE: ``a or b`` is a if a is true else b, ``a and b`` is b if a is true else a
+            # (expressions have no side effects: the operand's text is repeated); conditions go through cond()
+            out = self.expr(n.values[-1])
+            for v in reversed(n.values[:-1]):
+                x = self.expr(v)
+                out = '(%s ? (%s) : %s)' % (x, out, x) if isinstance(n.op, ast.And) else \
+                    '(%s ? %s : (%s))' % (x, x, out)
+            return out
         if isinstance(n, ast.Compare):
             ops = {ast.Lt: '<', ast.Gt: '>', ast.LtE: '<=', ast.GtE: '>=',
                    ast.Eq: '==', ast.NotEq: '!='}
@@ -366,7 +500,7 @@ class _Body(object):
                 left = right
             return '(' + ' && '.join(parts) + ')'
         if isinstance(n, ast.IfExp):
-            return '((%s) ? (%s) : (%s))' % (self.expr(n.test), self.expr(n.body),
+            return '((%s) ? (%s) : (%s))' % (self.cond(n.test), self.expr(n.body),
                                              self.expr(n.orelse))
         if isinstance(n, ast.Call):
             return self.call(n)
@@ -435,12 +569,17 @@ class _Body(object):
         if n.keywords:
             self.err(n, 'call %s' % ast.dump(f))
         args = [self.expr(a) for a in n.args]
+        if fname in ('floor', 'ceil') and len(args) == 1 and not (
+                isinstance(f, ast.Attribute) and f.value.id in ('np', 'numpy')):
+            # math.floor / math.ceil give an int: a zero result has no sign (np.floor keeps it)
+            return '(%s(%s) + 0.0)' % (fname, args[0])
         if fname in MATH_1 and len(args) == 1:
             return '%s(%s)' % (MATH_1[fname], args[0])
         if fname in MATH_2 and len(args) == 2:
             return '%s(%s, %s)' % (MATH_2[fname], args[0], args[1])
         if fname in ('max', 'min') and len(args) >= 2:
-            fn = 'fmax' if fname == 'max' else 'fmin'
+            fn = 'gen_pymax' if fname == 'max' else 'gen_pymin'   # the FIRST of equal arguments, as Python
+            self.fam.pyfuncs.add(fname)
             out = args[0]
             for a in args[1:]:
                 out = '%s(%s, %s)' % (fn, out, a)
@@ -455,6 +594,9 @@ class _Body(object):
             return repr(float(self.unrolled[v]))
         if v in self.loop_vars:
             return _cn(v)
+        if v in self.index_only:
+            self.err(n, 'int local %s holds a property value truncated to an index: it may only be '
+                        'used as an index' % v)
         if v in self.locals:
             return _cn(v)
         if v == 'N_NBRS' and self.all_nbrs:
@@ -503,6 +645,24 @@ class _Body(object):
             op = {ast.Add: '+', ast.Sub: '-', ast.Mult: '*'}[type(n.op)]
             return '(%s %s %s)' % (self.index(n.left), op, self.index(n.right))
         self.err(n, 'array index must be an integer literal or a loop variable')
+
+    def _bound(self, n):
+        """a range() bound: an index expression, which may also be negative (``range(-3, n)``).  Subscripts
+        do not come through here: a negative subscript counts from the end in Python"""
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, ast.USub):
+            return '(-%s)' % self._bound(n.operand)
+        if isinstance(n, ast.BinOp) and isinstance(n.op, (ast.Add, ast.Sub, ast.Mult)):
+            op = {ast.Add: '+', ast.Sub: '-', ast.Mult: '*'}[type(n.op)]
+            return '(%s %s %s)' % (self._bound(n.left), op, self._bound(n.right))
+        return self.index(n)
+
+    def _read_outside_its_loops(self, var):
+        """the counter `var` is read somewhere that is not inside a loop over it (reads inside a loop over the
+        same counter see that loop's values)"""
+        inside = set(id(x) for f_ in ast.walk(self.fdef) if isinstance(f_, ast.For)
+                     and isinstance(f_.target, ast.Name) and f_.target.id == var for x in ast.walk(f_))
+        return any(isinstance(x, ast.Name) and x.id == var and isinstance(x.ctx, ast.Load) and id(x) not in inside
+                   for x in ast.walk(self.fdef))
 
     def _strided(self, sl, idx_name):
         """``<idx>*S + K`` / ``S*<idx> + K`` with literal S, K -> (S, K): one
@@ -702,6 +862,10 @@ class _Body(object):
                     for t_, d in zip(tgt.elts, decl):
                         self._declare(t_, d, st)
                     return
+                for t_, v in zip(tgt.elts, st.value.elts):
+                    if isinstance(t_, ast.Name) and self.locals.get(t_.id, ('',))[0] == 'int' \
+                            and not self._py_int(v):
+                        self.err(st, 'non-integer expression assigned to the declared int %s' % t_.id)
                 vals = [self.expr(v) for v in st.value.elts]
                 tmp = ['_t%d_%d' % (st.lineno, i) for i in range(len(vals))]
                 for tn, v in zip(tmp, vals):
@@ -714,7 +878,10 @@ class _Body(object):
                 self._declare(tgt, d, st)
                 return
             if isinstance(tgt, ast.Name) and self.locals.get(tgt.id, ('',))[0] == 'int':
+                if tgt.id in self.loop_vars:
+                    self.err(st, 'assignment to %s, the counter of a running loop' % tgt.id)
                 self.affine_ints.pop(tgt.id, None)
+                self.index_only.discard(tgt.id)
                 aff = self._affine(st.value)
                 if aff is not None and not (set(aff[0]) - {'d_idx', 's_idx'}) and \
                         (self._assign_counts().get(tgt.id, 0) == 1 or self.unrolled):
@@ -732,8 +899,18 @@ class _Body(object):
                     try:
                         rhs = self.index(st.value)
                     except CodegenError:
-                        # idx = d_orig_idx[d_idx]: an index held in a (double) property
-                        rhs = '(int)(%s)' % self.expr(st.value)
+                        if self._py_int(st.value):
+                            rhs = '(int)(%s)' % self.expr(st.value)
+                        elif isinstance(st.value, ast.Subscript) and isinstance(st.value.value, ast.Name) \
+                                and st.value.value.id[:2] in ('d_', 's_'):
+                            # idx = d_orig_idx[d_idx]: an index held in a (double) property.  Python keeps
+                            # the property's value, so the local serves as an index only (where CPython
+                            # raises for a non-integral value)
+                            rhs = '(int)(%s)' % self.expr(st.value)
+                            self.index_only.add(tgt.id)
+                        else:
+                            self.err(st, 'non-integer expression assigned to the declared int %s '
+                                         '(Python would keep the float)' % tgt.id)
                 self._emit(ind, '%s = %s;' % (_cn(tgt.id), rhs))
                 return
             rhs = self.expr(st.value)
@@ -743,12 +920,22 @@ class _Body(object):
             ops = {ast.Add: '+=', ast.Sub: '-=', ast.Mult: '*=', ast.Div: '/='}
             if type(st.op) not in ops:
                 self.err(st, 'augmented operator')
+            if isinstance(st.target, ast.Name) and self.locals.get(st.target.id, ('',))[0] == 'int':
+                if st.target.id in self.loop_vars:
+                    self.err(st, 'assignment to %s, the counter of a running loop' % st.target.id)
+                if isinstance(st.op, ast.Div) or not self._py_int(st.value):
+                    self.err(st, 'non-integer augmented assignment to the declared int %s '
+                                 '(Python would keep the float)' % st.target.id)
+                self.affine_ints.pop(st.target.id, None)
+                self._emit(ind, '%s %s (int)(%s);' % (self._target(st.target, st, aug=True),
+                                                      ops[type(st.op)], self.expr(st.value)))
+                return
             rhs = self.expr(st.value)
             self._emit(ind, '%s %s %s;' % (self._target(st.target, st, aug=True),
                                            ops[type(st.op)], rhs))
             return
         if isinstance(st, ast.If):
-            self._emit(ind, 'if (%s) {' % self.expr(st.test))
+            self._emit(ind, 'if (%s) {' % self.cond(st.test))
             self._emit_block(st.body, ind + 1)
             if st.orelse:
                 self._emit(ind, '} else {')
@@ -776,6 +963,8 @@ class _Body(object):
                     self._emit_block(st.body, ind + 1)
                     self._emit(ind, '}')
                 self._runtime_loops = outer_loops
+                if chi > clo and self.locals.get(var, ('',))[0] == 'int' and self._read_outside_its_loops(var):
+                    self._emit(ind, '%s = %d;' % (_cn(var), chi - 1))   # the value Python leaves behind
                 if saved is None:
                     self.unrolled.pop(var, None)
                 else:
@@ -783,12 +972,27 @@ class _Body(object):
                 for nm in self._depends_on(var):
                     self.affine_ints.pop(nm, None)
                 return
-            lo, hi = ('0', self.index(it.args[0])) if len(it.args) == 1 else \
-                (self.index(it.args[0]), self.index(it.args[1]))
+            lo, hi = ('0', self._bound(it.args[0])) if len(it.args) == 1 else \
+                (self._bound(it.args[0]), self._bound(it.args[1]))
             fresh = var not in self.loop_vars
             self.loop_vars.add(var)
             cv = _cn(var)
-            self._emit(ind, 'for (int %s = %s; %s < %s; %s++) {' % (cv, lo, cv, hi, cv))
+            # range() takes its bounds once: a bound the body assigns to is read before the loop
+            stored = set(x.id for b_ in st.body for x in ast.walk(b_)
+                         if isinstance(x, ast.Name) and isinstance(x.ctx, ast.Store))
+            once = bool(stored & set(x.id for a_ in it.args for x in ast.walk(a_) if isinstance(x, ast.Name)))
+            if self.locals.get(var, ('',))[0] == 'int' and self._read_outside_its_loops(var):
+                # a declared counter that is read outside its loop keeps its last value (none for an empty range)
+                it_ = '%s_it%d' % (var, st.lineno)
+            else:
+                it_ = cv
+            if once:
+                self._emit(ind, 'for (int %s = %s, %s_end = %s; %s < %s_end; %s++) {' % (
+                    it_, lo, it_, hi, it_, it_, it_))
+            else:
+                self._emit(ind, 'for (int %s = %s; %s < %s; %s++) {' % (it_, lo, it_, hi, it_))
+            if it_ != cv:
+                self._emit(ind + 1, '%s = %s;' % (cv, it_))
             self._runtime_loops = getattr(self, '_runtime_loops', 0) + 1
             self._emit_block(st.body, ind + 1)
             self._runtime_loops -= 1
@@ -855,8 +1059,9 @@ class _HelperBody(_Body):
     """A module-level Python function called from an equation/stepper body,
     emitted as a ``__device__`` function of doubles."""
 
-    def __init__(self, fam, fn, name):
+    def __init__(self, fam, fn, name, strict=False):
         self.fam = fam
+        self.strict = strict
         self.eq = None
         self.k = -1
         self.kind = 'helper'
@@ -895,6 +1100,7 @@ class _HelperBody(_Body):
         self.loop_vars = set()
         self.unrolled = {}
         self.affine_ints = {}
+        self.index_only = set()
         self.lines = []
         self._emit_block(fdef.body, 1)
         self.writes = set()
@@ -906,6 +1112,8 @@ class _HelperBody(_Body):
         ctype = {'double': 'double ', 'int': 'int ', 'array': 'double *'}
         out = ['__device__ __forceinline__ double %s(%s)' % (
             self.cname, ', '.join(ctype[t] + _cn(n) for n, t in zip(self.argnames, self.argtypes))), '{']
+        if self.strict:
+            out.append('    #pragma clang fp contract(off)')
         for name, (kind, n) in sorted(self.locals.items()):
             if name in self.argnames:
                 continue
@@ -1029,6 +1237,7 @@ class GeneratedFamily(object):
                 self.src_flags[s] |= 1 << k
         self.abs_src_pos = False
         self.helpers = OrderedDict()    # name -> _HelperBody, in dependency order
+        self.pyfuncs = set()            # 'mod' / 'max' / 'min': the gen_py* device functions the bodies call
         self.sym_written = set()        # pair symbols some equation assigns to
         self.raw_dest = set()           # destination properties also read at a run-time index
         self.state = []                 # [(equation index, attribute)] assigned by device code
@@ -1173,7 +1382,10 @@ class GeneratedFamily(object):
         if fn is None:
             return None
         saved = getattr(self, '_writes', None)
-        h = _HelperBody(self, fn, fname)       # may pull in further helpers first
+        # a helper first called from a body that rounds every operation on its own does so too
+        strict = getattr(owner, '_fp_contract_', True) is False if owner is not None \
+            else getattr(body, 'strict', False)
+        h = _HelperBody(self, fn, fname, strict)       # may pull in further helpers first
         self._writes = saved
         self.helpers[fname] = h
         return h
@@ -1248,6 +1460,23 @@ class GeneratedFamily(object):
         A('    grad[0] = tmp * xij[0]; grad[1] = tmp * xij[1]; grad[2] = tmp * xij[2];')
         A('}')
         A('')
+        # Python semantics of % (the sign of the divisor: CPython float_rem) and of max / min (the first of equal
+        # arguments, whatever the sign of a zero; an argument that compares false with everything is kept or dropped
+        # by its position, as in Python): emitted for the families that use them
+        if 'mod' in self.pyfuncs:
+            A('__device__ __forceinline__ double gen_pymod(double x, double y)')
+            A('{')
+            A('    double r = fmod(x, y);')
+            A('    if (r != 0.0) { if ((y < 0.0) != (r < 0.0)) r += y; }')
+            A('    else r = y < 0.0 ? -0.0 : 0.0;')
+            A('    return r;')
+            A('}')
+        if 'max' in self.pyfuncs:
+            A('__device__ __forceinline__ double gen_pymax(double x, double y) { return y > x ? y : x; }')
+        if 'min' in self.pyfuncs:
+            A('__device__ __forceinline__ double gen_pymin(double x, double y) { return y < x ? y : x; }')
+        if self.pyfuncs:
+            A('')
         for h in self.helpers.values():
             L.extend(h.definition().split('\n'))
             A('')

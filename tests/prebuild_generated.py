@@ -120,6 +120,8 @@ def main():
     n += RI.prebuild_golden_steppers()
     n += RI.prebuild_multi_stage()
     n += plan([RI.make_pa()], [RI.SHM(dest='fluid', sources=None)], K.CubicSpline(dim=1))
+    import test_codegen_semantics as CS     # the construct corpus and the float build of its "flow" family
+    n += CS.prebuild(plan)
     return n
 
 

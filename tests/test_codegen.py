@@ -140,8 +140,9 @@ def test_translation_details():
 
     fam = GeneratedFamily('fluid', [E('fluid', ['fluid'])], _arrays(), 2, 'cg_det')
     src = fam.source
-    assert 'fmin(fmin(RIJ, 1.0), PAR[0])' in src
-    assert '(fmin(fmin(RIJ, 1.0), PAR[0]) * fmin(fmin(RIJ, 1.0), PAR[0]))' in src   # **2 -> product
+    # min() keeps the first of equal arguments, as Python does: gen_pymin, not fmin
+    assert 'gen_pymin(gen_pymin(RIJ, 1.0), PAR[0])' in src and 'fmin(' not in src
+    assert '(gen_pymin(gen_pymin(RIJ, 1.0), PAR[0]) * gen_pymin(gen_pymin(RIJ, 1.0), PAR[0]))' in src   # **2 -> product
     assert '&&' in src and '||' in src and '!(' in src and '?' in src
     assert 'D.d_au +=' in src and 's_m = s[0]' in src
     assert [p[0][2] for p in fam.params] == ['k', 'on'] and fam.param_values() == [2.5, 1.0]
