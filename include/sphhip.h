@@ -335,6 +335,12 @@ typedef struct sph_gen_args {
     double par[SPH_GEN_MAX_PAR];
     double *state;                /* device copy of sph_gen_family.state (equation attributes the bodies write) */
     int row_mod3, norm_masks;     /* the context options of the same names (row order / hit-mask normalisation of the pair kernel) */
+    /* transposed (scatter) families: per source its sorted -> original permutation and the range [src_lo, src_hi) of
+     * ORIGINAL indices whose rows may act as neighbours (the rows the forward loop visits as destinations); the
+     * generated pair() drops every other hit.  src_filter 0: the range covers the whole array, nothing is looked up */
+    const uint32_t *src_perm[SPH_MAX_ARRAYS];
+    uint32_t src_lo[SPH_MAX_ARRAYS], src_hi[SPH_MAX_ARRAYS];
+    int src_filter;
 } sph_gen_args;
 
 typedef int (*sph_gen_launch_fn)(const sph_gen_args *);
@@ -364,6 +370,13 @@ typedef struct sph_gen_family {
     sph_gen_launch_fn launch_f32; /* the same family compiled with float arithmetic (fp32 records, fp32 accumulators),
                                   * or NULL: taken for the pair launch under option arith_f32 -- the fp32 mode of the
                                   * reference's generated GPU code (acceleration_eval_gpu_helper.py:281-283,437-441) */
+    int transposed;              /* 1: the companion of a family whose loop bodies add to SOURCE properties
+                                  * (s_fx[s_idx] += ...): `dest` is that source array, every row of it in the neighbour grid
+                                  * is a destination row (real / start_idx / stop_idx are not looked at), src[0] is the
+                                  * original destination array, and of its rows only those of the ORIGINAL group's range
+                                  * act as neighbours:                                                       */
+    int t_real;                  /*   Group(real=...) of the original group                                   */
+    long t_start_idx, t_stop_idx; /*  its start_idx / stop_idx; <0: None                                      */
 } sph_gen_family;
 
 /* initialize -> no-source loops -> per-source pair loops -> post_loop of one

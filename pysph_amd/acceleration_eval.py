@@ -162,6 +162,11 @@ def make_acceleration_evals(particle_arrays, equations, kernel, mode='serial',
             for g in groups]
 
 
+# the hand-written kernels' tables list every property an equation touches on its destination, inputs included:
+# these never change
+_NEVER_WRITTEN = ('x', 'y', 'z', 'h', 'm', 'u', 'v', 'w', 'uhat', 'vhat', 'what')
+
+
 def is_builtin(eq):
     """hand-written kernel available (matched by class name, as
     ``resolve_equation`` does)?"""
@@ -243,14 +248,21 @@ class _GeneratedUnit(object):
     ``sph_eval_generated``."""
 
     def __init__(self, group, dest, eqs, array_ids, arrays, kernel_kind, owner,
-                 skip_initialize=()):
+                 skip_initialize=(), also_written=()):
         from .codegen import GeneratedFamily
         self.group = group
         self.eqs = eqs
         self.fam = GeneratedFamily(dest, eqs, arrays, kernel_kind,
                                    name='%s_%s' % (group.name, dest),
-                                   skip_initialize=skip_initialize)
-        f = self.fam
+                                   skip_initialize=skip_initialize, also_written=also_written)
+        self._describe(array_ids, owner)
+        # loop bodies that add to properties of their SOURCE arrays: per such array the transposed family, run
+        # directly behind this unit
+        self.scatter_units = [_ScatterUnit(group, c, array_ids, arrays, owner) for c in self.fam.companions]
+
+    def _describe(self, array_ids, owner):
+        group, f = self.group, self.fam
+        dest = f.dest
         lib = f.load()
         self.cf = dev.SphGenFamily()
         self.cf.launch = C.cast(lib.sphgen_launch, C.c_void_p).value
@@ -285,6 +297,9 @@ class _GeneratedUnit(object):
             self.cf.par[k] = v
         self.cf.start_idx, self.cf.stop_idx = start, stop
 
+    def _check(self, ev):
+        pass
+
     def _float_build(self, ev):
         """option arith_f32: the pair launch of this family runs its float build
         (codegen.source_f32), compiled / loaded the first time the option is seen"""
@@ -300,6 +315,7 @@ class _GeneratedUnit(object):
 
     def run(self, ev, t, dt):
         f = self.fam
+        self._check(ev)
         self._float_build(ev)
         for k, v in enumerate(f.state_values()):
             self.cf.state[k] = v
@@ -307,6 +323,38 @@ class _GeneratedUnit(object):
             ev.ctx._h, C.addressof(ev.ckernel), C.addressof(self.cf), t, dt))
         if f.state:
             f.store_state([self.cf.state[k] for k in range(len(f.state))])
+
+
+class _ScatterUnit(_GeneratedUnit):
+    """The transposed companion of a generated family (``s_fx[s_idx] += ...`` in a loop body): its destination is
+    the SOURCE array the bodies add to, every row of it that is in the neighbour grid; its neighbours are the rows of
+    the original destination that the forward loop visits (Group.real / start_idx / stop_idx of the original group).
+    The properties added to are inputs AND outputs of that source array."""
+
+    def __init__(self, group, fam, array_ids, arrays, owner):
+        self.group = group
+        self.eqs = fam.equations
+        self.fam = fam
+        self._arrays = arrays
+        self.scatter_units = []
+        self._describe(array_ids, owner)
+        self.cf.transposed = 1
+        self.cf.real = 0
+        self.cf.t_real = 1 if group.real else 0
+
+    def refresh(self, start, stop):
+        for k, v in enumerate(self.fam.param_values()):
+            self.cf.par[k] = v
+        self.cf.start_idx, self.cf.stop_idx = 0, -1
+        self.cf.t_start_idx, self.cf.t_stop_idx = start, stop
+
+    def _check(self, ev):
+        for name in (self.fam.dest, self.fam.transposed):
+            if getattr(self._arrays.get(name), 'slab_decomposed', False):
+                raise NotImplementedError(
+                    "equations that add to a source property (family '%s') are not supported in a slab-decomposed "
+                    "run: what a rank adds to a Remote row of '%s' never reaches the rank that owns it"
+                    % (self.fam.name, self.fam.dest))
 
 
 class _CGroup(object):
@@ -358,8 +406,10 @@ class _CGroup(object):
                                 'after the hand-written pass; put it in its own '
                                 'group' % (dest, type(eq).__name__))
                         skip.append(eq)
-                self.units.append(_GeneratedUnit(group, dest, custom, array_ids,
-                                                 arrays, kernel_kind, self, skip))
+                unit = _GeneratedUnit(group, dest, custom, array_ids, arrays, kernel_kind, self, skip,
+                                      also_written=reset_by_builtin - set(_NEVER_WRITTEN))
+                self.units.append(unit)
+                self.units.extend(unit.scatter_units)
 
     def _combined_group(self):
         """ONE sph_group holding the equations of every (hand-written) unit: a
@@ -706,7 +756,7 @@ class HipAccelerationEval(object):
     def pull_outputs(self):
         # the hand-written kernels' tables list every property an equation
         # touches on its destination, inputs included: those never change
-        never_written = ('x', 'y', 'z', 'h', 'm', 'u', 'v', 'w', 'uhat', 'vhat', 'what')
+        never_written = _NEVER_WRITTEN
         for name in set(self.outputs) | set(self.outputs_exact):
             pa = self.arrays[name]
             props = set(p for p in self.outputs.get(name, ()) if p not in never_written)

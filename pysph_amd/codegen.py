@@ -27,9 +27,13 @@ arrays, augmented assignment, bare ``return``, the libm calls compyle maps
 ``M_PI``/``pi``, ``self.<scalar attribute>`` (copied by value when the family is
 built, like equation.py:885-892 does), ``d_<prop>[d_idx]``,
 ``s_<prop>[s_idx]``, components of strided properties ``d_<prop>[d_idx*S + k]``,
-``d_<constant>[k]`` and the precomputed symbols ``XIJ
+``d_<constant>[k]``, ``s_<constant>[k]`` (in an equation with exactly one source)
+and the precomputed symbols ``XIJ
 VIJ R2IJ RIJ HIJ RHOIJ RHOIJ1 EPS WIJ DWIJ WI WJ DWI DWJ WDP t dt``
-(equation.py:188-297).  Anything else raises ``CodegenError`` -- the equation
+(equation.py:188-297), and in a ``loop`` body ``s_<prop>[s_idx] += expr`` /
+``-= expr``: such a family gets a transposed companion per source array written
+to, run as a second launch of the same skeleton (``GeneratedFamily.companions``,
+DESIGN.md section 7c).  Anything else raises ``CodegenError`` -- the equation
 then has to be hand-written or simplified; there is no silent fallback.
 
 What a translated body computes is what CPython computes when it runs the same
@@ -712,6 +716,8 @@ class _Body(object):
         sl = n.slice
         if isinstance(sl, ast.Index):      # py<3.9
             sl = sl.value
+        if self.fam.transposed and base[:2] in ('d_', 's_') and base not in self.locals:
+            return self._subscript_transposed(n, base, sl, store)
         if base.startswith('d_'):
             prop = base[2:]
             if isinstance(sl, ast.Name) and sl.id == 'd_idx':
@@ -767,6 +773,14 @@ class _Body(object):
             if sk is not None:
                 self.fam.note_stride(prop, sk[0], self, n)
                 return self.fam.src_prop('%s__%d' % (prop, sk[1]))
+            srcs = self.eq.sources or []
+            if isinstance(sl, ast.Constant) and isinstance(sl.value, int) and len(srcs) == 1 and \
+                    self.fam.is_array_constant(srcs[0], prop):
+                # a constant of the (one) source array: a scalar parameter, read at every compute
+                return self.fam.param(('aconst', srcs[0], prop, sl.value), None)
+            if len(srcs) > 1 and all(self.fam.is_array_constant(s_, prop) for s_ in srcs):
+                self.err(n, 'constant %s of a source array can only be read by an equation with exactly one source '
+                            '(it is a scalar parameter of the family)' % base)
             self.err(n, '%s must be indexed with s_idx' % base)
         if base in VEC_SYMBOLS:
             if store and self.pair:
@@ -782,6 +796,113 @@ class _Body(object):
         if base in self.locals and self.locals[base][0] in ('array', 'arrayarg'):
             return '%s[%s]' % (_cn(base), self.index(sl))
         self.err(n, 'subscript of unknown array %r' % base)
+
+    def _subscript_transposed(self, n, base, sl, store):
+        """a property access in the body of a TRANSPOSED family: the lane is a row of the source array (``s_*[s_idx]``
+        are its own loads, the scattered properties its accumulators), the neighbour a row of the original destination
+        (``d_*[d_idx]`` come from its packed record; stores to them are the forward family's and are dropped)"""
+        fam, prop = self.fam, base[2:]
+        idx = base[0] + '_idx'
+        owner = fam.transposed if base[0] == 'd' else fam.dest
+        if isinstance(sl, ast.Name) and sl.id == idx:
+            sk = (1, 0)
+        else:
+            sk = self._strided(sl, idx) or self._component(sl, idx)
+        if sk is None:
+            if fam.is_array_constant(owner, prop) and isinstance(sl, ast.Constant) and isinstance(sl.value, int):
+                if store:
+                    self.err(n, 'constants are read-only here')
+                return fam.param(('aconst', owner, prop, sl.value), None)
+            self.err(n, '%s must be indexed with %s' % (base, idx))
+        name = prop
+        if sk[0] != 1:
+            fam.note_stride(prop, sk[0], self, n)
+            name = '%s__%d' % (prop, sk[1])
+        if base[0] == 'd':
+            return None if store else fam.src_prop(name)
+        if name in ('x', 'y', 'z', 'h'):
+            if store:
+                self.err(n, 'source arrays are read-only (gather formulation)')
+            if name != 'h':
+                fam.abs_src_pos = True
+            return {'x': 'pi.x', 'y': 'pi.y', 'z': 'pi.z', 'h': 'l_h'}[name]
+        return fam.dest_prop(name, store)
+
+    def _scatter_store(self, st):
+        """``s_<prop>[s_idx] += expr`` / ``-=`` in a pair loop: in the forward family the statement is the
+        transposed companion's (recorded, not emitted: True); everything else about source stores stays refused"""
+        tgt = st.target
+        if not (isinstance(tgt, ast.Subscript) and isinstance(tgt.value, ast.Name) and tgt.value.id.startswith('s_')
+                and tgt.value.id not in self.locals and self.pair and not self.raw_src
+                and isinstance(st.op, (ast.Add, ast.Sub))):
+            return False
+        prop, sl = tgt.value.id[2:], tgt.slice
+        if isinstance(sl, ast.Name) and sl.id == 's_idx':
+            sk = (1, 0)
+        else:
+            sk = self._strided(sl, 's_idx') or self._component(sl, 's_idx')
+        if sk is None or any(self.fam.is_array_constant(s_, prop) for s_ in (self.eq.sources or [])):
+            return False                # a run-time index, a constant: refused where the store is translated
+        name = prop if sk[0] == 1 else '%s__%d' % (prop, sk[1])
+        if sk[0] != 1:
+            self.fam.note_stride(prop, sk[0], self, tgt)
+        if self.fam.transposed:
+            return False                # translated: the lane's accumulator
+        self.fam.scatter.append((self, st, name))
+        return True
+
+    def _dropped_store(self, tgt):
+        """transposed family: a store to ``d_<prop>[..]`` belongs to the forward family"""
+        return bool(self.fam.transposed) and isinstance(tgt, ast.Subscript) and isinstance(tgt.value, ast.Name) \
+            and tgt.value.id.startswith('d_') and tgt.value.id not in self.locals \
+            and self.subscript(tgt, store=True) is None
+
+    def scatter_deps(self, st):
+        """(d_ properties, names) the value added by the source store `st` depends on: through the locals its
+        expression reads (flow-insensitive: every assignment to them anywhere in the body), the conditions around the
+        store and around those assignments, and the conditions of every early exit of the body"""
+        parents = {}
+        for node in ast.walk(self.fdef):
+            for ch in ast.iter_child_nodes(node):
+                parents[ch] = node
+
+        def around(node):
+            out, p_ = [], parents.get(node)
+            while p_ is not None:
+                if isinstance(p_, ast.If):
+                    out.append(p_.test)
+                elif isinstance(p_, ast.For):
+                    out.append(p_.iter)
+                p_ = parents.get(p_)
+            return out
+        defs, exits = {}, []
+        for node in ast.walk(self.fdef):
+            if isinstance(node, (ast.Assign, ast.AugAssign)):
+                for t_ in (node.targets if isinstance(node, ast.Assign) else [node.target]):
+                    for e in (t_.elts if isinstance(t_, ast.Tuple) else [t_]):
+                        if isinstance(e, ast.Name):
+                            defs.setdefault(e.id, []).extend([node.value] + around(node))
+                        elif isinstance(e, ast.Subscript) and isinstance(e.value, ast.Name):
+                            defs.setdefault(e.value.id, []).extend([node.value, e.slice] + around(node))
+            elif isinstance(node, ast.For) and isinstance(node.target, ast.Name):
+                defs.setdefault(node.target.id, []).extend([node.iter] + around(node))
+            elif isinstance(node, ast.Call):
+                for a in node.args:                     # a helper may write the arrays it is handed
+                    if isinstance(a, ast.Name):
+                        defs.setdefault(a.id, []).extend([x for x in node.args if x is not a] + around(node))
+            elif isinstance(node, (ast.Return, ast.Break, ast.Continue)):
+                exits += around(node)
+        work = [st.value, st.target.slice] + around(st) + exits
+        names, dreads = set(), set()
+        while work:
+            for x in ast.walk(work.pop()):
+                if isinstance(x, ast.Subscript) and isinstance(x.value, ast.Name) and x.value.id.startswith('d_') \
+                        and x.value.id not in self.locals and isinstance(x.ctx, ast.Load):
+                    dreads.add(x.value.id[2:])
+                if isinstance(x, ast.Name) and x.id not in names:
+                    names.add(x.id)
+                    work.extend(defs.get(x.id, []))
+        return dreads, names
 
     # -- statements --------------------------------------------------------
     def _emit(self, ind, text):
@@ -871,11 +992,14 @@ class _Body(object):
                 for tn, v in zip(tmp, vals):
                     self._emit(ind, 'const double %s = %s;' % (tn, v))
                 for t_, tn in zip(tgt.elts, tmp):
-                    self._emit(ind, '%s = %s;' % (self._target(t_, st), tn))
+                    if not self._dropped_store(t_):
+                        self._emit(ind, '%s = %s;' % (self._target(t_, st), tn))
                 return
             d = self._declare_call(st.value)
             if d is not None:
                 self._declare(tgt, d, st)
+                return
+            if self._dropped_store(tgt):
                 return
             if isinstance(tgt, ast.Name) and self.locals.get(tgt.id, ('',))[0] == 'int':
                 if tgt.id in self.loop_vars:
@@ -920,6 +1044,8 @@ class _Body(object):
             ops = {ast.Add: '+=', ast.Sub: '-=', ast.Mult: '*=', ast.Div: '/='}
             if type(st.op) not in ops:
                 self.err(st, 'augmented operator')
+            if self._dropped_store(st.target) or self._scatter_store(st):
+                return
             if isinstance(st.target, ast.Name) and self.locals.get(st.target.id, ('',))[0] == 'int':
                 if st.target.id in self.loop_vars:
                     self.err(st, 'assignment to %s, the counter of a running loop' % st.target.id)
@@ -1209,7 +1335,11 @@ class GeneratedFamily(object):
     """All equations of one group acting on one destination, generated."""
 
     def __init__(self, dest, equations, arrays, kernel_kind, name=None,
-                 skip_initialize=()):
+                 skip_initialize=(), also_written=(), transposed=None):
+        """`also_written`: destination properties a hand-written unit of the same destination and group writes.
+        `transposed`: this is the companion of the family of destination `transposed` whose loop bodies add to
+        properties of the source array `dest` (``s_fx[s_idx] += ...``): the same loop bodies with the roles swapped
+        -- a lane is a row of `dest`, its neighbours are rows of `transposed`"""
         if len(equations) > 32:
             raise CodegenError('more than 32 equations on one destination')
         self.dest = dest
@@ -1225,6 +1355,9 @@ class GeneratedFamily(object):
         self.params = []        # [(key, value)]
         self.sources = []       # first-appearance order (acceleration_eval.py:136-151)
         self.src_flags = {}
+        self.transposed = transposed
+        self.scatter = []       # [(body, statement, property)]: the stores to source properties of the loop bodies
+        self.companions = []    # per source array written to: the transposed family
         for k, eq in enumerate(self.equations):
             for m in UNSUPPORTED_METHODS:
                 if callable(getattr(type(eq), m, None)):
@@ -1235,6 +1368,11 @@ class GeneratedFamily(object):
                     self.sources.append(s)
                     self.src_flags[s] = 0
                 self.src_flags[s] |= 1 << k
+        if transposed is not None:
+            # one source, the original destination; equation k acts iff it loops over `dest` in the forward family
+            self.sources = [transposed]
+            self.src_flags = {transposed: sum(1 << k for k, eq in enumerate(self.equations)
+                                              if dest in (eq.sources or []))}
         self.abs_src_pos = False
         self.helpers = OrderedDict()    # name -> _HelperBody, in dependency order
         self.pyfuncs = set()            # 'mod' / 'max' / 'min': the gen_py* device functions the bodies call
@@ -1249,6 +1387,8 @@ class GeneratedFamily(object):
                 fdef = _method_ast(eq, m)
                 if fdef is None or (m == 'initialize' and eq in skip_initialize):
                     continue
+                if transposed is not None and (m != 'loop' or dest not in (eq.sources or [])):
+                    continue            # no initialize, no post_loop: those are the forward family's
                 b = _Body(self, eq, k, m, fdef)
                 if m == 'loop' and self.is_no_source(eq):
                     self.nosrc_loops.append(b)
@@ -1287,7 +1427,18 @@ class GeneratedFamily(object):
             raise CodegenError('more than 48 destination properties in one family')
         if len(self.params) > 64:
             raise CodegenError('more than 64 scalar parameters in one family')
+        if self.scatter:
+            self._check_scatter(also_written)
         self.source = self._emit_source()
+        if self.scatter:
+            written_to = []
+            for b, _, _ in self.scatter:
+                for s in b.eq.sources:
+                    if s not in written_to:
+                        written_to.append(s)
+            for s in written_to:
+                self.companions.append(GeneratedFamily(s, self.equations, arrays, kernel_kind,
+                                                       name='%s_to_%s' % (self.name, s), transposed=dest))
         # content address: the generated struct AND the skeleton it is compiled
         # against (a changed sph_pair.h must not pick up a stale binary)
         self.hash = hashlib.sha1((self.source + _skeleton_digest()).encode()).hexdigest()[:16]
@@ -1301,6 +1452,54 @@ class GeneratedFamily(object):
     def is_dest_constant(self, name):
         pa = self.arrays.get(self.dest)
         return pa is not None and name in getattr(pa, 'constants', {})
+
+    def is_array_constant(self, array, name):
+        pa = self.arrays.get(array)
+        return pa is not None and name in getattr(pa, 'constants', {})
+
+    def _check_scatter(self, also_written):
+        """Source stores the transposed launch cannot reproduce: the reference adds, pair by pair in the order of
+        its loops, a value that the same loops are still changing -- the device keeps no such order."""
+        def base(p):
+            return p.split('__')[0]
+
+        def where(b, st, prop):
+            return '%s line %d: s_%s[s_idx] %s= ...' % (b.where, st.lineno, prop,
+                                                        '+' if isinstance(st.op, ast.Add) else '-')
+        written = set(base(p) for p in self.dwritten) | set(base(p) for p in also_written)
+        sread = set(base(p) for p in self.sprops) | {'x', 'y', 'z', 'h'}
+        dtouched = set(base(p) for p in self.dprops) | set(base(p) for p in also_written)
+        for b, st, prop in self.scatter:
+            # an equation attribute assigned by the loop (self.x = ...): every pair sees what the pairs before it left
+            for x in ast.walk(b.fdef):
+                if isinstance(x, ast.Attribute) and isinstance(x.ctx, ast.Store) and isinstance(x.value, ast.Name) \
+                        and x.value.id == 'self':
+                    raise CodegenError(
+                        '%s: the same loop assigns self.%s (line %d): the state an equation carries from pair to pair '
+                        'depends on the order of the reference\'s loops, which the device does not keep'
+                        % (where(b, st, prop), x.attr, x.lineno))
+            dreads, names = b.scatter_deps(st)
+            if names & self.sym_written:
+                # a pair symbol an equation of the family rewrites: whatever the loop bodies read goes into it
+                for ob in self.bodies['loop']:
+                    for x in ast.walk(ob.fdef):
+                        if isinstance(x, ast.Subscript) and isinstance(x.value, ast.Name) and isinstance(x.ctx, ast.Load) \
+                                and x.value.id.startswith('d_') and x.value.id not in ob.locals:
+                            dreads.add(x.value.id[2:])
+            bad = sorted(dreads & written)
+            if bad:
+                raise CodegenError(
+                    '%s depends on d_%s, which the equations of destination %r write in the same group: what the '
+                    'reference adds depends on the order of its loops, which the device does not keep'
+                    % (where(b, st, prop), bad[0], self.dest))
+            if base(prop) in sread:
+                raise CodegenError(
+                    '%s: s_%s is also read by the equations of destination %r in the same group (the reference reads '
+                    'a partly accumulated value there)' % (where(b, st, prop), base(prop), self.dest))
+            if self.dest in (b.eq.sources or []) and base(prop) in dtouched:
+                raise CodegenError(
+                    '%s: destination and source are the same array %r and d_%s is used in the same group'
+                    % (where(b, st, prop), self.dest, base(prop)))
 
     def dest_prop(self, prop, store):
         if prop not in self.dprops:
@@ -1418,6 +1617,8 @@ class GeneratedFamily(object):
         for key, val in self.params:
             if key[0] == 'const':
                 out.append(float(get_npy(self.arrays[self.dest], key[1])[key[2]]))
+            elif key[0] == 'aconst':
+                out.append(float(get_npy(self.arrays[key[1]], key[2])[key[3]]))
             else:
                 out.append(val)
         return out
@@ -1487,6 +1688,9 @@ class GeneratedFamily(object):
         A('    static constexpr uint32_t CF0 = 0;         // equation flags are run-time values')
         A('    static constexpr int NA = %d;' % na)
         A('    static constexpr int NR = 4 + NA;')
+        T_ = self.transposed is not None
+        if T_:
+            A('    static constexpr bool PAIR_INDEX = true;   // pair() takes the neighbour\'s packed position (range filter)')
         A('    struct Params {')
         A('        const double *din[%d];' % max(len(din), 1))
         A('        double *dout[%d];' % max(len(dout), 1))
@@ -1494,6 +1698,10 @@ class GeneratedFamily(object):
         A('        const uint32_t *csr_start[SPH_MAX_ARRAYS], *csr_nbrs[SPH_MAX_ARRAYS];   // loop_all')
         A('        double *state;   // equation attributes assigned by the bodies')
         A('        const double *sraw[SPH_MAX_ARRAYS][%d];' % max(len(self.sprops), 1))
+        if T_:
+            A('        const uint32_t *sperm;   // sorted -> original index of the neighbour array')
+            A('        uint32_t slo, shi;       // original indices of the rows that act as neighbours')
+            A('        int sfilter;             // 0: every row does')
         A('    };')
         A('    struct Dest {')
         for p in self.dprops:
@@ -1509,7 +1717,10 @@ class GeneratedFamily(object):
         for i, p in enumerate(din):
             A('        D.d_%s = a.p.din[%d][o];' % (p, i))
         for i, p in enumerate(dout):
-            A('        D.d_%s = a.p.dout[%d][o];' % (p, i))
+            if T_:
+                A('        D.d_%s = 0.0;   // accumulator of s_%s[s_idx] += ...' % (p, p))
+            else:
+                A('        D.d_%s = a.p.dout[%d][o];' % (p, i))
         A('        if (!a.skip_init) {')
         for b in self.bodies['initialize']:
             A(b.code(3))
@@ -1520,20 +1731,36 @@ class GeneratedFamily(object):
         # ---- pair
         A('    template <int KK, bool UH, class A>')
         A('    static __device__ __forceinline__ void pair(Dest &D, const double4 &pi, const double4 &pj, double r2,')
-        A('                                                const double (&s)[NA], uint32_t fl, const A &a)')
+        A('                                                const double (&s)[NA], uint32_t fl, const A &a%s)'
+          % (', uint32_t jg' if T_ else ''))
         A('    {')
+        if T_:
+            # the lane (pi, D) is a row of the SOURCE array, the neighbour (pj, s) a row of the original destination
+            A('        if (a.p.sfilter) {   // wave-uniform: the forward loop does not visit every row of the neighbour array')
+            A('            const uint32_t oj = a.p.sperm[jg - a.src[0].off];')
+            A('            if (oj < a.p.slo || oj >= a.p.shi) return;')
+            A('        }')
         A('        const double *PAR = a.p.par; (void)PAR;')
         A('        const double t = a.t, dt = a.dt; (void)t; (void)dt;')
         A('        PairGeom g;')
         A('        pair_geom<KK, UH>(g, pi, pj, r2, a);')
-        A('        const double XIJ[3] = {g.xij[0], g.xij[1], g.xij[2]}; (void)XIJ;')
+        if T_:
+            # pair symbols keep the orientation destination - source of the forward loop: the negated differences
+            # are the same bits, every other part of the geometry is symmetric
+            A('        const double XIJ[3] = {-g.xij[0], -g.xij[1], -g.xij[2]}; (void)XIJ;')
+            A('        const double l_h = UH ? a.hu : pi.w; (void)l_h;')
+        else:
+            A('        const double XIJ[3] = {g.xij[0], g.xij[1], g.xij[2]}; (void)XIJ;')
         A('        const double R2IJ = r2, RIJ = g.rij, HIJ = g.hij, EPS = g.eps; (void)R2IJ; (void)RIJ; (void)HIJ; (void)EPS;')
         A('        const double s_h = UH ? a.hu : pj.w; (void)s_h;')
         for i, p in enumerate(self.sprops):
             if p not in ('x', 'y', 'z', 'h'):
                 A('        const double s_%s = s[%d];' % (p, i))
         if 'VIJ' in S:
-            A('        const double VIJ[3] = {D.d_u - s_u, D.d_v - s_v, D.d_w - s_w};')
+            if T_:
+                A('        const double VIJ[3] = {s_u - D.d_u, s_v - D.d_v, s_w - D.d_w};')
+            else:
+                A('        const double VIJ[3] = {D.d_u - s_u, D.d_v - s_v, D.d_w - s_w};')
         if S & {'RHOIJ', 'RHOIJ1'}:
             A('        const double RHOIJ = 0.5 * (D.d_rho + s_rho); (void)RHOIJ;')
             A('        const double RHOIJ1 = 1.0 / RHOIJ; (void)RHOIJ1;')
@@ -1550,8 +1777,11 @@ class GeneratedFamily(object):
             # kernels evaluated with h_d / h_s (equation.py:262-297)
             A('        PairGeom gi = g, gj = g;')
             A('        if (!UH) {')
-            A('            gi.hij = pi.w; gi.h1 = 1.0 / pi.w; gi.fac = kernel_norm(a.k.sigma, gi.h1, a.k.dim); gi.q = g.rij * gi.h1;')
-            A('            gj.hij = pj.w; gj.h1 = 1.0 / pj.w; gj.fac = kernel_norm(a.k.sigma, gj.h1, a.k.dim); gj.q = g.rij * gj.h1;')
+            # WI / DWI / GHI take the h of the destination of the FORWARD loop, WJ / DWJ / GHJ that of its source: in a
+            # transposed family those are the neighbour's and the lane's
+            di, dj = ('pj', 'pi') if T_ else ('pi', 'pj')
+            A('            gi.hij = %s.w; gi.h1 = 1.0 / %s.w; gi.fac = kernel_norm(a.k.sigma, gi.h1, a.k.dim); gi.q = g.rij * gi.h1;' % (di, di))
+            A('            gj.hij = %s.w; gj.h1 = 1.0 / %s.w; gj.fac = kernel_norm(a.k.sigma, gj.h1, a.k.dim); gj.q = g.rij * gj.h1;' % (dj, dj))
             A('        }')
             if 'WI' in S:
                 A('        const double WI = pair_w<KK, false>(gi);')
@@ -1587,7 +1817,10 @@ class GeneratedFamily(object):
         A('    template <class A> static __device__ __forceinline__ void store(Dest &D, const A &a, uint32_t o)')
         A('    {')
         for i, p in enumerate(dout):
-            A('        a.p.dout[%d][o] = D.d_%s;' % (i, p))
+            if T_:      # the one read-modify-write of a scattered property
+                A('        a.p.dout[%d][o] = a.p.dout[%d][o] + D.d_%s;' % (i, i, p))
+            else:
+                A('        a.p.dout[%d][o] = D.d_%s;' % (i, p))
         A('    }')
         # ---- loop_all bodies of one source
         A('    template <int KK, class A>')
@@ -1708,6 +1941,9 @@ class GeneratedFamily(object):
         A('    a.skip_init = g->skip_init;')
         A('    a.p.state = g->state;')
         A('    a.skip_post = g->skip_post;')
+        if T_:
+            A('    a.p.sperm = g->src_perm[0]; a.p.slo = g->src_lo[0]; a.p.shi = g->src_hi[0]; a.p.sfilter = g->src_filter;')
+            A('    if (g->nsrc != 1 || g->mode != 0 || (a.p.sfilter && !a.p.sperm)) return -1004;')
         A('    for (int j = 0; j < SPH_MAX_ARRAYS; j++) {')
         A('        a.p.csr_start[j] = g->csr_start[j]; a.p.csr_nbrs[j] = g->csr_nbrs[j];')
         A('        for (int k = 0; k < %d; k++) a.p.sraw[j][k] = g->sraw[j][k];' % max(len(self.sprops), 1))

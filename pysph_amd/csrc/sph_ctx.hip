@@ -403,8 +403,10 @@ static const AbiField ABI_FIELDS[] = {
     ABI_F(sph_gen_family, par), ABI_F(sph_gen_family, real), ABI_F(sph_gen_family, start_idx), ABI_F(sph_gen_family, stop_idx),
     ABI_F(sph_gen_family, split_init), ABI_F(sph_gen_family, loop_all), ABI_F(sph_gen_family, also_pair), ABI_F(sph_gen_family, init_pair),
     ABI_F(sph_gen_family, nstate), ABI_F(sph_gen_family, state), ABI_F(sph_gen_family, launch_f32),
+    ABI_F(sph_gen_family, transposed), ABI_F(sph_gen_family, t_real), ABI_F(sph_gen_family, t_start_idx), ABI_F(sph_gen_family, t_stop_idx),
     ABI_F(sph_gen_args, stream), ABI_F(sph_gen_args, rec), ABI_F(sph_gen_args, mode), ABI_F(sph_gen_args, par), ABI_F(sph_gen_args, state),
-    ABI_F(sph_gen_args, row_mod3),
+    ABI_F(sph_gen_args, row_mod3), ABI_F(sph_gen_args, src_perm), ABI_F(sph_gen_args, src_lo), ABI_F(sph_gen_args, src_hi),
+    ABI_F(sph_gen_args, src_filter),
 };
 #undef ABI_F
 

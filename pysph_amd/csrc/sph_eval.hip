@@ -2478,6 +2478,15 @@ static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_ge
     size_t start = f->start_idx > 0 ? (size_t)f->start_idx : 0;
     size_t stop = f->stop_idx >= 0 ? (size_t)f->stop_idx : (f->real ? D.n_real : D.n);
     if (stop > D.n) stop = D.n;
+    if (f->transposed) {
+        // the companion of a family that adds to source properties: every row of that source array (here: the
+        // destination) which is in the neighbour grid takes part, ghosts included -- the reference writes to them too
+        if (f->nsrc != 1 || f->loop_all || f->init_pair || f->split_init || f->nstate) {
+            sph_set_error("sph_eval_generated: a transposed family has one source and pair loops only");
+            return SPH_ERR_ARG;
+        }
+        start = 0; stop = D.n;
+    }
 
     sph_gen_args g;
     memset(&g, 0, sizeof g);
@@ -2624,6 +2633,7 @@ static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_ge
                 q.src_off[jj] = (uint32_t)off_of[jj];
                 q.src_flags[jj] = f->src_flags[j];
                 q.dflags |= f->src_flags[j];
+                q.src_perm[jj] = c->arr[f->src[j]].perm.as<uint32_t>();
             }
             q.d_off = (uint32_t)d_off;
             q.d_keys = D.keys_sorted.as<uint32_t>();
@@ -2641,6 +2651,19 @@ static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_ge
         const int s = f->src[j];
         if (s < 0 || s >= SPH_MAX_ARRAYS || !c->arr[s].used) { sph_set_error("bad source array %d", s); return SPH_ERR_ARG; }
         for (int i = 0; i < j; i++) if (f->src[i] == s) { sph_set_error("source array %d listed twice", s); return SPH_ERR_ARG; }
+    }
+    if (f->transposed) {
+        // neighbours are the rows the forward loop visits as destinations: [start_idx, stop_idx) of the ORIGINAL group,
+        // n_real under Group(real=True).  The cell tables of that array hold its other rows as well (ghosts of a
+        // periodic domain, rows outside a start/stop range): the generated pair() looks the original index of a hit
+        // up and drops those -- unless the range is the whole array
+        const DevArray &N = c->arr[f->src[0]];
+        size_t lo = f->t_start_idx > 0 ? (size_t)f->t_start_idx : 0;
+        size_t hi = f->t_stop_idx >= 0 ? (size_t)f->t_stop_idx : (f->t_real ? N.n_real : N.n);
+        if (hi > N.n) hi = N.n;
+        if (N.n == 0 || hi <= lo) return SPH_OK; // the forward loop visits no row: nothing to add
+        g.src_lo[0] = (uint32_t)lo; g.src_hi[0] = (uint32_t)hi;
+        g.src_filter = (lo > 0 || hi < N.n) ? 1 : 0;
     }
     if (f->nsrc > 0 && f->init_pair) {
         // initialize_pair (mako :62-75): per source, before that source's loops, one sweep over

@@ -13,7 +13,8 @@
 //   Dest                 per-destination registers (inputs + accumulators)
 //   load(D, s, a, o)     initialize: from the destination's own record `s`
 //                        (and, for generated families, memory at original index o)
-//   pair<KK,UH>(D, pi, pj, r2, s, flags, a)   one neighbour pair
+//   pair<KK,UH>(D, pi, pj, r2, s, flags, a)   one neighbour pair (with PAIR_INDEX = true: ..., a, jg -- the neighbour's
+//                        position in the packed buffers as well)
 //   finish(D, a, o)      post_loop + the single write per output
 // and may specialise load_record<Fam, UH> for a custom record layout.
 #pragma once
@@ -153,6 +154,11 @@ template <class F> struct fam_token<F, decltype((void)F::TOKEN)> { static conste
 // does the family recompute p, cs from rho (64-byte WCSPH records)?
 template <class F, class = void> struct fam_eosf { static constexpr bool value = false; };
 template <class F> struct fam_eosf<F, decltype((void)F::EOSF)> { static constexpr bool value = F::EOSF; };
+
+// does the family's pair() also take the neighbour's position in the packed buffers?  (generated transposed
+// families: a hit whose ORIGINAL index lies outside the forward loop's destination range is dropped there)
+template <class F, class = void> struct fam_pair_index { static constexpr bool value = false; };
+template <class F> struct fam_pair_index<F, decltype((void)F::PAIR_INDEX)> { static constexpr bool value = F::PAIR_INDEX; };
 
 
 // ---------------------------------------------------------------------------
@@ -525,7 +531,10 @@ __global__ __launch_bounds__(64 * WPB, Fam::MINB) void k_pair_wave(PairArgs<Fam>
         T hj2 = hi2;
         if (!UH) { hj2 = (T)a.radius_scale * pj.w; hj2 *= hj2; }
         const T r2 = r2_exact<T>(pi.x - pj.x, pi.y - pj.y, pi.z - pj.z);
-        if (((r2 < hi2) || (r2 < hj2)) && ABLATE(a) != 1) Fam::template pair<KK, UH>(D, pi, pj, r2, sj, flags, a);
+        if (((r2 < hi2) || (r2 < hj2)) && ABLATE(a) != 1) {
+            if constexpr (fam_pair_index<Fam>::value) Fam::template pair<KK, UH>(D, pi, pj, r2, sj, flags, a, jg);
+            else Fam::template pair<KK, UH>(D, pi, pj, r2, sj, flags, a);
+        }
     };
 
     int cq = 0; // slots this lane holds

@@ -215,7 +215,9 @@ class SphGenFamily(C.Structure):
                 ('stop_idx', C.c_long), ('split_init', C.c_int),
                 ('loop_all', C.c_int), ('also_pair', C.c_int),
                 ('init_pair', C.c_int), ('nstate', C.c_int),
-                ('state', C.c_double * 16), ('launch_f32', C.c_void_p)]
+                ('state', C.c_double * 16), ('launch_f32', C.c_void_p),
+                ('transposed', C.c_int), ('t_real', C.c_int),
+                ('t_start_idx', C.c_long), ('t_stop_idx', C.c_long)]
 
 
 class HipContext(object):

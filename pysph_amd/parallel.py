@@ -402,6 +402,9 @@ class SlabHalo(object):
         self.periodic = periodic
         self.period = float(period)
         self.ops = ops or DeviceHaloOps(pa, ctx, props, axis)
+        # what an evaluation adds to a Remote row of this array stays on this rank (acceleration_eval._ScatterUnit refuses)
+        if pa is not None:
+            pa.slab_decomposed = True
         self.last_counts = (0, 0, 0, 0)   # sent lo/hi, received lo/hi
         self.last_migrated = (0, 0, 0, 0)
         self.total_migrated = 0           # particles this rank has handed over since the start
