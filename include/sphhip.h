@@ -630,12 +630,68 @@ int sph_coord_histogram(sph_ctx *ctx, int array_id, int axis, double vmin, doubl
 enum sph_stepper {
     SPH_STEP_WCSPH = 1, /* WCSPHStep            integrator_step.py:38-93  */
     SPH_STEP_TVF = 2,   /* TransportVelocityStep integrator_step.py:257-299 */
-    SPH_STEP_SOLID_MECH = 3 /* SolidMechStep       integrator_step.py:173-255 */
+    SPH_STEP_SOLID_MECH = 3, /* SolidMechStep       integrator_step.py:173-255 */
+    SPH_STEP_RIGID_RK2 = 4,  /* RK2StepRigidBody    pysph/sph/rigid_body.py:718-770 (needs sph_rigid_setup) */
+    SPH_STEP_RIGID_EULER = 5 /* EulerStepRigidBody  pysph/sph/rigid_body.py:695-715 (stage 1 only)          */
 };
 int sph_integrate_stage(sph_ctx *ctx, int array_id, int stepper, int stage, double dt);
 /* min over the first n_real particles of a property (h_minimum,
  * pysph/sph/integrator.py:150-160).                                        */
 int sph_reduce_min(sph_ctx *ctx, int array_id, int prop, double *out);
+
+/* ---------------------------------------------------------------------- */
+/* rigid bodies: moments, motion and steppers of the bodies of an array     */
+/* (RigidBodyMoments / RigidBodyMotion / RK2StepRigidBody,                  */
+/* pysph/sph/rigid_body.py:69-230, 695-771).  The reference keeps the state */
+/* of the bodies in array constants and reduces them on the host; here it   */
+/* is a block of doubles on the device, per field `nbody * width` values in */
+/* the layout of those constants (pysph/base/utils.py:268-286).  The body   */
+/* of a row is the property "body_id" (sph_prop_register), a column of      */
+/* doubles like every other property.  DESIGN.md section 7d.                */
+/* ---------------------------------------------------------------------- */
+enum sph_rigid_field {
+    SPH_RIGID_TOTAL_MASS = 0, /* [nb]     */
+    SPH_RIGID_CM,             /* [3 nb]   */
+    SPH_RIGID_MI,             /* [16 nb]: 0..8 the inertia tensor about cm, row-major; 10..15 as the reference leaves them */
+    SPH_RIGID_FORCE,          /* [3 nb]   */
+    SPH_RIGID_TORQUE,         /* [3 nb]   about cm */
+    SPH_RIGID_VC,             /* [3 nb]   */
+    SPH_RIGID_AC,             /* [3 nb]   */
+    SPH_RIGID_VC0,            /* [3 nb]   */
+    SPH_RIGID_OMEGA,          /* [3 nb]   */
+    SPH_RIGID_OMEGA0,         /* [3 nb]   */
+    SPH_RIGID_OMEGA_DOT,      /* [3 nb]   */
+    SPH_RIGID_FIELD_COUNT
+};
+/* Entries of a body's segment that one wavefront of the moment sums takes. */
+int sph_rigid_chunk(void);
+/* Give the array `nbody` bodies: allocates the (zeroed) state and takes the
+ * body index -- order[n]: the rows sorted by body id, stable; start[nbody + 1]:
+ * where each body's rows begin in `order` (host memory, copied).  order ==
+ * start == NULL: the library builds the index itself when it first needs it,
+ * from the body_id column.  Either way the index is REBUILT from that column
+ * whenever the rows of the array have moved or their number has changed since
+ * (sph_array_permute, sph_nnps_reorder_array, sph_array_resize, appends and
+ * removals, a push of body_id); that costs one pull of the column and a host
+ * sort.  A body id outside [0, nbody), or a body without rows, is SPH_ERR_ARG
+ * wherever the index is built or checked.  Calling it again with the same
+ * nbody keeps the state.                                                    */
+int sph_rigid_setup(sph_ctx *ctx, int array_id, int nbody, const uint32_t *order, const uint32_t *start);
+/* One field of the state, host <-> device; n must be nbody * width.         */
+int sph_rigid_state_push(sph_ctx *ctx, int array_id, int field, const double *host, size_t n);
+int sph_rigid_state_pull(sph_ctx *ctx, int array_id, int field, double *host, size_t n);
+/* RigidBodyMoments.reduce: total_mass, cm, mi, force, ac, torque, omega_dot
+ * of every body from x y z m fx fy fz of ALL rows of the array (ghosts
+ * included, as in the reference) and the bodies' omega.  fp64 whatever the
+ * arithmetic options say.  No device->host traffic while the index is valid;
+ * sums in an order that depends on the order of a body's own rows only.     */
+int sph_rigid_moments(sph_ctx *ctx, int array_id);
+/* RigidBodyMotion.initialize: (u, v, w) = vc + omega x (r - cm) of rows
+ * [start, stop) (stop < 0: to the end; real_only: of the real rows).  Needs no
+ * body index and validates none: a row whose body_id is outside [0, nbody)
+ * keeps its u, v, w; sph_rigid_moments reports it (SPH_ERR_ARG) when it next
+ * builds the index.                                                         */
+int sph_rigid_motion(sph_ctx *ctx, int array_id, int real_only, long start, long stop);
 
 /* options (key, value):
  *   "pair_variant"   6 = one wavefront per 64 destinations, two-phase pair

@@ -48,6 +48,14 @@ def check_equation_array_properties(equation, particle_arrays):
     """acceleration_eval.py:32-73: RuntimeError when a destination/source array
     or one of the properties the equation touches is missing."""
     arrays = dict((pa.name, pa) for pa in particle_arrays)
+    if rigid_kind(equation):
+        dprops, sprops = _RIGID_PROPS[rigid_kind(equation)][0], ()
+    else:
+        dprops, sprops = _equation_properties(equation)
+    _check_properties(equation, arrays, dprops, sprops)
+
+
+def _equation_properties(equation):
     try:
         kind, vals, dprops, sprops = resolve_equation(equation)
     except NotImplementedError:
@@ -55,6 +63,10 @@ def check_equation_array_properties(equation, particle_arrays):
         if not has_python_body(equation):
             raise
         dprops, sprops = method_properties(equation)
+    return dprops, sprops
+
+
+def _check_properties(equation, arrays, dprops, sprops):
     if equation.dest not in arrays:
         raise RuntimeError("ERROR: Equation %s has invalid dest: '%s'" %
                            (equation.name, equation.dest))
@@ -165,6 +177,66 @@ def make_acceleration_evals(particle_arrays, equations, kernel, mode='serial',
 # the hand-written kernels' tables list every property an equation touches on its destination, inputs included:
 # these never change
 _NEVER_WRITTEN = ('x', 'y', 'z', 'h', 'm', 'u', 'v', 'w', 'uhat', 'vhat', 'what')
+
+
+# The two equations of pysph_amd.rigid_body (or the reference's classes of the same names) that run on the per-body
+# state of csrc/sph_rigid.hip: name -> (what they read of the destination, properties and constants; the properties
+# they write; the constants they write)
+_RIGID_PROPS = {
+    'RigidBodyMoments': (('x', 'y', 'z', 'm', 'fx', 'fy', 'fz', 'body_id', 'omega', 'num_body'), (),
+                         ('total_mass', 'cm', 'mi', 'force', 'ac', 'torque', 'omega_dot')),
+    'RigidBodyMotion': (('x', 'y', 'z', 'u', 'v', 'w', 'body_id', 'cm', 'vc', 'omega'), ('u', 'v', 'w'), ()),
+}
+
+
+def rigid_kind(eq):
+    """'RigidBodyMoments' / 'RigidBodyMotion' for the equations that run through ``sph_rigid_*`` (matched by class
+    name, as ``resolve_equation`` does), else None"""
+    name = type(eq).__name__
+    return name if name in _RIGID_PROPS else None
+
+
+class _RigidUnit(object):
+    """A RigidBodyMoments or RigidBodyMotion of one destination.  ``RigidBodyMotion`` runs among the units of its
+    group, where its ``initialize`` would; ``RigidBodyMoments`` behind them, where its ``reduce`` would (the host
+    hook itself is not called)."""
+
+    def __init__(self, group, eq, array_ids, arrays, owner):
+        self.group = group
+        self.eqs = [eq]
+        self.kind = rigid_kind(eq)
+        self.dest = eq.dest
+        self.scatter_units = []
+        self._arrays = arrays
+        reads, writes, state = _RIGID_PROPS[self.kind]
+        for p in reads:
+            if p in arrays[eq.dest].properties:
+                dev.prop_register(p)
+        owner.inputs[eq.dest].update(reads)
+        owner.outputs_exact[eq.dest].update(writes)
+        owner.rigid_arrays.add(eq.dest)
+        self._range = (0, -1)
+
+    def refresh(self, start, stop):
+        self._range = (start, stop)
+
+    def _check(self, ev):
+        pa = self._arrays[self.dest]
+        owner = getattr(ev.helpers[self.dest], 'ghost_owner', None)
+        if getattr(pa, 'slab_decomposed', False) or owner is not None:
+            raise NotImplementedError(
+                "%s on array '%s': rigid bodies are not supported on a slab-decomposed array or one with periodic "
+                "images%s -- a body cut by a slab plane would need an all-reduce of its 16 sums"
+                % (self.kind, self.dest, ' (ghosts managed by %s)' % owner if owner else ''))
+
+    def run(self, ev, t, dt, phase=0):
+        self._check(ev)
+        helper = ev.helpers[self.dest]
+        helper.rigid_setup()
+        if self.kind == 'RigidBodyMoments':
+            helper.rigid_moments()
+        else:
+            helper.rigid_motion(self.group.real, *self._range)
 
 
 def is_builtin(eq):
@@ -375,6 +447,8 @@ class _CGroup(object):
         self.outputs = defaultdict(set)   # array name -> props written (hand-written kernels: a superset)
         self.outputs_exact = defaultdict(set)  # generated families: exactly the written properties
         self.units = []
+        self.rigid_arrays = set()         # arrays whose per-body state the group reads or writes
+        self.moments = {}                 # RigidBodyMoments equation -> its unit: run in place of the reduce hook
         self._arrays = arrays
         dests = []
         for eq in group.equations:
@@ -382,6 +456,12 @@ class _CGroup(object):
                 dests.append(eq.dest)
         for dest in dests:
             eqs = [eq for eq in group.equations if eq.dest == dest]
+            for eq in eqs:
+                if rigid_kind(eq) == 'RigidBodyMotion':      # (initialize: before everything else of the destination)
+                    self.units.append(_RigidUnit(group, eq, array_ids, arrays, self))
+                elif rigid_kind(eq):
+                    self.moments[id(eq)] = _RigidUnit(group, eq, array_ids, arrays, self)
+            eqs = [eq for eq in eqs if not rigid_kind(eq)]
             builtin = [eq for eq in eqs if is_builtin(eq)]
             custom = [eq for eq in eqs if not is_builtin(eq)]
             if builtin:
@@ -438,7 +518,7 @@ class _CGroup(object):
                 return int(get_npy(dest, v)[0])
             return int(v)
         start, stop = resolve(g.start_idx, 0), resolve(g.stop_idx, -1)
-        for u in self.units:
+        for u in list(self.units) + list(self.moments.values()):
             u.refresh(start, stop)
         self._start_stop = (start, stop)
 
@@ -491,7 +571,7 @@ def _plain_leaf(g, cg):
             or g.update_nnps:
         return False
     for eq in g.equations:
-        if hasattr(eq, 'py_initialize') or hasattr(eq, 'reduce'):
+        if hasattr(eq, 'py_initialize') or hasattr(eq, 'reduce') or rigid_kind(eq):
             return False
     return all(isinstance(u, _BuiltinUnit) for u in cg.units)
 
@@ -661,7 +741,9 @@ class HipAccelerationEval(object):
         self.inputs = defaultdict(set)
         self.outputs = defaultdict(set)
         self.outputs_exact = defaultdict(set)
+        self.rigid_arrays = set()
         for cg in self._leaves(self.plan):
+            self.rigid_arrays.update(cg.rigid_arrays)
             for n, p in cg.inputs.items():
                 self.inputs[n].update(p)
             for n, p in cg.outputs.items():
@@ -752,6 +834,9 @@ class HipAccelerationEval(object):
                         or self.helpers[name]._component(p) is not None)
                     and p not in skip]
             self.helpers[name].push(*have)
+        for name in self.rigid_arrays:      # the state of the bodies: the host constants are authoritative, too
+            self.helpers[name].rigid_setup()
+            self.helpers[name].push(*dev.RIGID_FIELDS)
 
     def pull_outputs(self):
         # the hand-written kernels' tables list every property an equation
@@ -765,6 +850,9 @@ class HipAccelerationEval(object):
                    if (p in pa.properties and dev.prop_id(p) >= 0)
                    or self.helpers[name]._component(p) is not None]
             self.helpers[name].pull(*out)
+        for name in self.rigid_arrays:
+            if self.helpers[name].has_body_state():
+                self.helpers[name].pull(*dev.RIGID_FIELDS)
 
     # -- group execution (acceleration_eval_cython.mako:291-363) -------------
     def _run(self, entry, t, dt):
@@ -826,7 +914,9 @@ class HipAccelerationEval(object):
             item.refresh_range()
             item.run(self, t, dt)
             for eq in g.equations:
-                if hasattr(eq, 'reduce'):
+                if id(eq) in item.moments:
+                    item.moments[id(eq)].run(self, t, dt)       # sph_rigid_moments, not the host's reduce
+                elif hasattr(eq, 'reduce'):
                     self._host_hook(eq.reduce, self.arrays[eq.dest], t, dt)
         if g.update_nnps:
             self.nnps.update_domain()

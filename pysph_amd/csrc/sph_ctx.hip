@@ -147,6 +147,7 @@ int sph_ctx_destroy(sph_ctx *c)
     for (auto &H : c->halo)
         for (int s = 0; s < 2; s++) { H.flag[s].release(); H.pos[s].release(); H.list[s].release(); }
     for (auto &I : c->io) I.code.release();
+    for (auto &R : c->rigid) { R.state.release(); R.order.release(); R.chunk.release(); R.chunk_start.release(); R.partial.release(); }
     c->io_counts.release();
     for (DevBuf *b : {&c->dbgc, &c->gapq, &c->cub_tmp, &c->red_part, &c->red_out, &c->posh, &c->aux, &c->fposb, &c->dkeys, &c->dperm,
                       &c->tmp_u32a, &c->tmp_u32b, &c->gen_state, &c->nlbuf, &c->splitcnt, &c->scan_part, &c->bigq, &c->sort_tab, &c->xflag, &c->dom_counts})
@@ -204,7 +205,7 @@ int sph_array_resize(sph_ctx *c, int id, size_t n, size_t n_real)
         }
         A.cap = ncap;
     }
-    if (n != A.n) c->nnps_valid = false;
+    if (n != A.n) { c->nnps_valid = false; A.rows_epoch++; }
     if (n > A.n) A.tflag_valid = false; // new particles (ghosts, migrants): their r_ij were not looked at
     if (n > A.n) sph_mark_grown(A);     // ... nor their h and m
     if (n < A.n) sph_mark_removed(A, n);
@@ -253,6 +254,7 @@ int sph_array_push(sph_ctx *c, int id, int prop, const double *host, size_t offs
     // the grid of the previous update's bounds but looks at the particles first
     if (prop == SPH_X || prop == SPH_Y || prop == SPH_Z) c->lag.valid = false;
     if (prop == SPH_M) A.m_mixed_ghosts = false;
+    if (prop == c->rigid[id].body_prop) A.rows_epoch++; // other bodies in the rows: the body index is rebuilt
     sph_mark_written(A, prop); // h / m: until the next sph_nnps_update has looked at them
     if (prop >= SPH_R00 && prop <= SPH_R22) A.tflag_valid = false;
     return SPH_OK;

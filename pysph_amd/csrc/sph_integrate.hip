@@ -77,6 +77,7 @@ extern "C" int sph_integrate_stage(sph_ctx *c, int id, int stepper, int stage, d
 {
     if (!c || id < 0 || id >= SPH_MAX_ARRAYS || stage < 0 || stage > 2) { sph_set_error("sph_integrate_stage: bad arguments"); return SPH_ERR_ARG; }
     HIP_TRY(hipSetDevice(c->device));
+    if (stepper == SPH_STEP_RIGID_RK2 || stepper == SPH_STEP_RIGID_EULER) return sph_rigid_stage(c, id, stepper, stage, dt); // sph_rigid.hip
     DevArray &A = c->arr[id];
     static const int wc0[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, SPH_RHO0, -1};
     static const int wc1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, SPH_RHO0,

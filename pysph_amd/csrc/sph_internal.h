@@ -97,6 +97,7 @@ struct DevArray {
     double *spare = nullptr;             // one more property-sized buffer: the compaction of sph_halo_remove_selected rotates through it
     size_t spare_cap = 0;                // ... holding this many doubles
     DevBuf slot8;                        // merged order only (sph_ctx::merged): uint8 nnps slot of every particle's array
+    unsigned rows_epoch = 0;             // bumped whenever rows move, arrive or leave: what is indexed by row (RigidState) is stale then
 };
 
 // ghost selection lists of one array (sph_halo.hip)
@@ -115,6 +116,20 @@ struct IoState {
     bool valid = false;
     bool counts_known = false;  // count[] below holds what the device counted
     size_t count[3] = {0, 0, 0};
+};
+
+// rigid bodies of one array (sph_rigid.hip): the state of the bodies in the layout of the reference's
+// constants, and the body index -- the rows sorted by body id, cut into chunks of at most SPH_RIGID_CHUNK entries of ONE body
+struct RigidState {
+    int nb = 0;                 // bodies (0: sph_rigid_setup was not called)
+    int body_prop = -1;         // property id of "body_id"
+    DevBuf state;               // double [44 nb]: field f at rigid_offset(f) * nb
+    DevBuf order;               // uint32 [n]
+    DevBuf chunk, chunk_start;  // uint32 [nchunks][2] (first entry of `order`, entries), [nb + 1] (first chunk of a body)
+    DevBuf partial;             // double [nchunks][16]
+    size_t nchunks = 0;
+    bool index_built = false;   // an index exists ...
+    unsigned index_epoch = 0;   // ... built at this DevArray::rows_epoch: current while the two are equal
 };
 
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
@@ -145,10 +160,11 @@ static inline void sph_mark_written(DevArray &A, int prop)
     if (prop == SPH_M) { A.m_dirty = true; A.m_known = false; A.hm_writes++; }
 }
 // particles with values from outside (other ranks' ghosts, host appends) arrive
-static inline void sph_mark_grown(DevArray &A) { A.h_dirty = A.m_dirty = true; A.m_known = false; }
+static inline void sph_mark_grown(DevArray &A) { A.h_dirty = A.m_dirty = true; A.m_known = false; A.rows_epoch++; }
 // particles leave: a range of ONE value stays what it is while a particle is left, any other range may shrink
 static inline void sph_mark_removed(DevArray &A, size_t n_left)
 {
+    A.rows_epoch++;
     if (!(A.h_seen && A.h_lo == A.h_hi && n_left > 0)) A.h_dirty = true;
     if (!(A.m_seen && A.m_lo == A.m_hi && n_left > 0)) { A.m_dirty = true; A.m_known = false; }
 }
@@ -170,6 +186,7 @@ struct sph_ctx {
     DevArray arr[SPH_MAX_ARRAYS];
     HaloState halo[SPH_MAX_ARRAYS];
     IoState io[SPH_MAX_ARRAYS];
+    RigidState rigid[SPH_MAX_ARRAYS];
     DevBuf io_counts;             // uint32 [SPH_MAX_ARRAYS][4]: the class counts of sph_io_classify, reduced on the device
 
     // grid of the last sph_nnps_update
@@ -323,6 +340,9 @@ int nnps_need_tables(sph_ctx *c); // per-array cell orders / tables of a merged-
 int nnps_build_csr_device(sph_ctx *c, int src, int dst, DevBuf &start, DevBuf &nbrs, size_t *total);
 // eval.hip: the same lists through the wave-tile pair kernel (count pass: start == nullptr; fill pass: start, nbrs)
 int nnps_csr_pair_kernel(sph_ctx *c, int src, int dst, uint32_t *count, const uint32_t *start, uint32_t *nbrs);
+
+// rigid.hip: the stages of SPH_STEP_RIGID_RK2 / SPH_STEP_RIGID_EULER (sph_integrate_stage hands them over)
+int sph_rigid_stage(sph_ctx *c, int id, int stepper, int stage, double dt);
 
 // eval.hip helpers
 static inline unsigned div_up(size_t a, unsigned b) { return (unsigned)((a + b - 1) / b); }

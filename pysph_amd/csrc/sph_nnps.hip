@@ -2188,6 +2188,7 @@ extern "C" int sph_array_permute(sph_ctx *c, int id, const uint32_t *indices, si
     }
     A.perm_n = 0;
     A.perm_direct_n = 0; A.unordered = false; // another memory order
+    A.rows_epoch++;
     c->io[id].valid = false;                  // (a selection of sph_io_classify describes the rows as they lay)
     c->nnps_valid = false;
     return sph_array_resize(c, id, n_new, n_real_new);
@@ -2228,6 +2229,7 @@ extern "C" int sph_nnps_reorder_array(sph_ctx *c, int id)
     HIP_TRY(hipFree(tmp));
     A.perm_n = 0;
     A.perm_direct_n = 0; A.unordered = false; // the array lies in cell order now
+    A.rows_epoch++;
     c->io[id].valid = false;
     c->nnps_valid = false;
     return SPH_OK;

@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .particle_array import get_npy
+from .particle_array import RIGID_BODY_CONSTANTS, get_npy
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SPH_LIBRARY: another build of the same sources, for A/B measurements of compile-time switches)
@@ -135,11 +135,20 @@ SIGNATURES = {
     'sph_reduce_min': (C.c_int, [_P, C.c_int, C.c_int, _PD]),
     'sph_integrate_stage': (C.c_int, [_P, C.c_int, C.c_int, C.c_int,
                                       C.c_double]),
+    'sph_rigid_chunk': (C.c_int, []),
+    'sph_rigid_setup': (C.c_int, [_P, C.c_int, C.c_int, _PU, _PU]),
+    'sph_rigid_state_push': (C.c_int, [_P, C.c_int, C.c_int, _PD, C.c_size_t]),
+    'sph_rigid_state_pull': (C.c_int, [_P, C.c_int, C.c_int, _PD, C.c_size_t]),
+    'sph_rigid_moments': (C.c_int, [_P, C.c_int]),
+    'sph_rigid_motion': (C.c_int, [_P, C.c_int, C.c_int, C.c_long, C.c_long]),
     'sph_set_option': (C.c_int, [_P, C.c_char_p, C.c_long]),
     'sph_timer_enable': (C.c_int, [_P, C.c_int]),
     'sph_timer_reset': (C.c_int, [_P]),
     'sph_timer_get': (C.c_int, [_P, C.c_char_p, _PD, C.POINTER(C.c_long)]),
 }
+
+# the per-body constants of a rigid-body array in the order of enum sph_rigid_field
+RIGID_FIELDS = tuple(name for name, _ in RIGID_BODY_CONSTANTS)
 
 _LIB = None
 
@@ -413,6 +422,12 @@ class HipDeviceHelper(object):
         # True when the device holds extra (ghost) particles the host array
         # does not have: sizes are then managed by the halo exchange
         self.managed = False
+        if 'body_id' in pa.properties and 'num_body' in getattr(pa, 'constants', {}):
+            # a rigid-body array: the columns its moments read are user properties; known from the start, so that
+            # every bare push() / pull() carries them
+            for p in ('body_id', 'fx', 'fy', 'fz'):
+                if p in pa.properties:
+                    prop_register(p)
         self.resize(pa.get_number_of_particles())
 
     def get_number_of_particles(self, real=False):
@@ -462,7 +477,12 @@ class HipDeviceHelper(object):
         self._sync_size()
         if not props:
             props = [p for p in pa.properties if prop_id(p) >= 0]
+            if self.has_body_state():
+                props = props + list(RIGID_FIELDS)
         for p in props:
+            if p in RIGID_FIELDS and p not in pa.properties and self.has_body_state():
+                self._body_state(p, push=True)      # a per-body constant of a rigid-body array
+                continue
             if p in pa.properties and get_npy(pa, p).dtype != np.float64 and prop_id(p) < 0:
                 continue              # tag / pid / gid: host-resident metadata
             comp = self._component(p)
@@ -488,7 +508,12 @@ class HipDeviceHelper(object):
         pa = self._pa
         if not props:
             props = [p for p in pa.properties if prop_id(p) >= 0]
+            if self.has_body_state():
+                props = props + list(RIGID_FIELDS)
         for p in props:
+            if p in RIGID_FIELDS and p not in pa.properties and self.has_body_state():
+                self._body_state(p, push=False)
+                continue
             if p in pa.properties and get_npy(pa, p).dtype != np.float64 and prop_id(p) < 0:
                 continue              # tag / pid / gid: host-resident metadata
             comp = self._component(p)
@@ -517,6 +542,51 @@ class HipDeviceHelper(object):
             _check(self.lib.sph_array_pull(
                 self.ctx._h, self.array_id, pid, arr.ctypes.data_as(_PD), 0,
                 min(arr.size, self.get_number_of_particles())))
+
+    # -- rigid bodies: the per-body constants live on the device (csrc/sph_rigid.hip) ---------------------------
+    def has_body_state(self):
+        return self.__dict__.get('_rigid_nb', 0) > 0
+
+    def rigid_setup(self):
+        """Give the device array its bodies: ``num_body`` blocks of state, created once; the host constants are
+        pushed when the state is created (there is nothing on the device to overwrite then).  No particle column
+        is touched: the device's body_id column says which body a row belongs to -- it has followed every reorder
+        of the device array -- and the library builds the body index from it when the moments first need it."""
+        pa = self._pa
+        consts = getattr(pa, 'constants', {})
+        if 'body_id' not in pa.properties or 'num_body' not in consts:
+            raise SphError("array '%s' has no bodies (body_id / num_body): see get_particle_array_rigid_body"
+                           % pa.name)
+        missing = [k for k in RIGID_FIELDS if k not in consts]
+        if missing:
+            raise SphError("array '%s' lacks the body constants %s" % (pa.name, missing))
+        nb = int(get_npy(pa, 'num_body')[0])
+        if self.__dict__.get('_rigid_nb', 0) == nb:
+            return
+        if prop_register('body_id') not in self.device_props():
+            raise SphError("array '%s' has no body_id column on the device: push it (pa.gpu.push()) before the "
+                           "first evaluation or stage" % pa.name)
+        _check(self.lib.sph_rigid_setup(self.ctx._h, self.array_id, nb, None, None))
+        self._rigid_nb = nb
+        self.push(*RIGID_FIELDS)
+
+    def _body_state(self, name, push):
+        host = get_npy(self._pa, name)
+        if host.dtype != np.float64 or not host.flags.c_contiguous:
+            raise SphError('body constant %s: the host array must be contiguous fp64' % name)
+        fn = self.lib.sph_rigid_state_push if push else self.lib.sph_rigid_state_pull
+        _check(fn(self.ctx._h, self.array_id, RIGID_FIELDS.index(name), host.ctypes.data_as(_PD), host.size))
+
+    def rigid_moments(self):
+        try:
+            _check(self.lib.sph_rigid_moments(self.ctx._h, self.array_id))
+        except SphError as e:
+            if 'body index of array' in str(e):      # a bad id / an empty body found when the index was rebuilt
+                raise ValueError(str(e))
+            raise
+
+    def rigid_motion(self, real_only=False, start=0, stop=-1):
+        _check(self.lib.sph_rigid_motion(self.ctx._h, self.array_id, int(bool(real_only)), int(start), int(stop)))
 
     def pull_into(self, prop, out):
         """device -> a caller-provided fp64 buffer (first out.size values)."""

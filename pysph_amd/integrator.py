@@ -47,7 +47,12 @@ class TransportVelocityStep(IntegratorStep):
     _kind = STEP_TVF
 
 
-_STEP_KINDS = {'WCSPHStep': STEP_WCSPH, 'TransportVelocityStep': STEP_TVF}
+STEP_RIGID_RK2 = 4
+STEP_RIGID_EULER = 5
+
+# (the two rigid-body steppers are classes of pysph_amd.rigid_body; their stages need the array's body state)
+_STEP_KINDS = {'WCSPHStep': STEP_WCSPH, 'TransportVelocityStep': STEP_TVF,
+               'RK2StepRigidBody': STEP_RIGID_RK2, 'EulerStepRigidBody': STEP_RIGID_EULER}
 
 
 def stepper_kind(step):
@@ -374,6 +379,8 @@ class HipIntegrator(object):
             if kind is not None:
                 if auto:
                     helper.push()
+                if kind in (STEP_RIGID_RK2, STEP_RIGID_EULER):
+                    helper.rigid_setup()        # (once: the bodies' state, behind the columns now on the device)
                 dev._check(self.lib.sph_integrate_stage(self.ctx._h, helper.array_id, kind,
                                                         stage, self.dt))
                 if auto:

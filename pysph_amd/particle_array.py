@@ -126,8 +126,11 @@ class ParticleArray(object):
         if stride != 1:
             self.stride[name] = stride
 
-    def add_constant(self, name, data):
-        self.constants[name] = np.atleast_1d(np.asarray(data, dtype=float)).copy()
+    def add_constant(self, name, data, type=None):
+        """a constant is an array of doubles unless `type` ('int', 'long', ... as for add_property) says otherwise"""
+        dtype = float if type is None else {'double': np.float64, 'float': np.float32, 'int': np.int32,
+                                            'unsigned int': np.uint32, 'long': np.int64}[type]
+        self.constants[name] = np.atleast_1d(np.asarray(data, dtype=dtype)).copy()
 
     def get_carray(self, name):
         if name in self.properties:
@@ -270,4 +273,32 @@ def get_particle_array_tvf_fluid(constants=None, **props):
                             additional_props=TVF_FLUID_PROPS, **props)
     pa.set_output_arrays(['x', 'y', 'z', 'u', 'v', 'w', 'rho', 'p', 'h', 'm',
                           'au', 'av', 'aw', 'V', 'vmag2', 'pid', 'gid', 'tag'])
+    return pa
+
+
+RIGID_BODY_PROPS = ['au', 'av', 'aw', 'V', 'fx', 'fy', 'fz', 'x0', 'y0', 'z0',
+                    'tang_disp_x', 'tang_disp_y', 'tang_disp_z', 'tang_disp_x0', 'tang_disp_y0', 'tang_disp_z0',
+                    'tang_velocity_x', 'tang_velocity_y', 'rad_s', 'tang_velocity_z', 'nx', 'ny', 'nz']
+
+# per-body constants: name -> doubles per body, in the order of enum sph_rigid_field (include/sphhip.h) -- the ONE
+# Python statement of the layout of the device state of csrc/sph_rigid.hip (device.RIGID_FIELDS and the tests read it)
+RIGID_BODY_CONSTANTS = (('total_mass', 1), ('cm', 3), ('mi', 16), ('force', 3), ('torque', 3), ('vc', 3), ('ac', 3),
+                        ('vc0', 3), ('omega', 3), ('omega0', 3), ('omega_dot', 3))
+
+
+def get_particle_array_rigid_body(constants=None, **props):
+    """utils.py ``get_particle_array_rigid_body`` (:238-295): the integer property ``body_id`` says which body a
+    particle belongs to (ids 0 .. nb - 1; one body when it is absent), the constants hold the state of the bodies --
+    ``num_body`` (an integer) and ``total_mass[nb]``, ``cm[3 nb]``, ``mi[16 nb]``, ``force``, ``torque``, ``vc``,
+    ``ac``, ``vc0``, ``omega``, ``omega0``, ``omega_dot`` (3 nb each)."""
+    body_id = props.pop('body_id', None)
+    nb = 1 if body_id is None else int(np.max(body_id)) + 1
+    consts = dict((name, np.zeros(width * nb)) for name, width in RIGID_BODY_CONSTANTS)
+    if constants:
+        consts.update(constants)
+    pa = get_particle_array(constants=consts, additional_props=RIGID_BODY_PROPS, **props)
+    pa.add_constant('num_body', nb, type='int')
+    pa.add_property('body_id', type='int', data=body_id)
+    pa.set_output_arrays(['x', 'y', 'z', 'u', 'v', 'w', 'rho', 'h', 'm', 'p', 'pid', 'au', 'av', 'aw', 'tag', 'gid',
+                          'V', 'fx', 'fy', 'fz', 'body_id'])
     return pa

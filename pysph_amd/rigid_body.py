@@ -28,10 +28,185 @@ are written from the papers' formulae:
   ``-m_b (p_b / rho_b^2 + p_i / rho_i^2) grad W_ib`` with the body particles
   carrying a pressure and density of their own (``LiuFluidForce``).
 
-The moments, the motion and the collisions of the bodies are not part of this
-module.
+The bodies move, too.  ``RigidBodyMoments`` (:69) sums mass, centre of mass,
+inertia, force and torque of every body and solves Euler's equation for the
+angular acceleration; ``RigidBodyMotion`` (:215) gives every body particle the
+velocity ``vc + omega x (r - cm)``; ``RK2StepRigidBody`` (:718) and
+``EulerStepRigidBody`` (:695) advance the particles and the bodies' ``vc`` and
+``omega``.  On the device these four are hand-written kernels over a block of
+per-body state (csrc/sph_rigid.hip) that
+``AccelerationEval`` and ``HipIntegrator`` call through the C-ABI; the method
+bodies below are their host twins -- plain Python over the arrays and constants
+of ``get_particle_array_rigid_body`` -- written from the formulae:
+
+* ``M = sum m``, ``cm = sum m r / M``; inertia about the origin ``sum m (|r|^2 1
+  - r r^T)`` moved to ``cm`` by the parallel-axis theorem ``I = I_0 - M (|cm|^2
+  1 - cm cm^T)``; ``F = sum f``, ``tau = sum r x f - cm x F``;
+* Euler's equation ``I omega_dot = tau - omega x (I omega)``, solved with the
+  adjugate of the symmetric ``I`` over its determinant.
+
+The collisions of the bodies (``RigidBodyCollision``, ``RigidBodyWallCollision``,
+``RigidBodyForceGPUGems``) are not part of this module.
 """
+import numpy as np
+
 from .equations import Equation
+from .integrator import IntegratorStep
+
+def body_index(body_id, nbody):
+    """(order, start): the rows sorted by body id, stable in row order, and where each body's rows begin in
+    `order` (start[nbody] = n).  An id outside [0, nbody) or a body without particles is a ValueError (in the
+    reference: an index error or a division by zero)."""
+    ids = np.asarray(body_id)
+    nbody = int(nbody)
+    if ids.size and (np.any(ids < 0) or np.any(ids >= nbody) or np.any(ids != np.floor(ids))):
+        bad = ids[(ids < 0) | (ids >= nbody) | (ids != np.floor(ids))][0]
+        raise ValueError('body_id %r is outside [0, %d)' % (bad, nbody))
+    ids = ids.astype(np.int64)
+    counts = np.bincount(ids, minlength=nbody)
+    if nbody < 1 or np.any(counts == 0):
+        empty = int(np.nonzero(counts == 0)[0][0]) if nbody >= 1 else 0
+        raise ValueError('body %d of %d has no particles' % (empty, nbody))
+    order = np.argsort(ids, kind='stable').astype(np.uint32)
+    start = np.zeros(nbody + 1, dtype=np.uint32)
+    start[1:] = np.cumsum(counts)
+    return order, start
+
+
+def solve_symmetric3(ixx, iyy, izz, ixy, ixz, iyz, rx, ry, rz):
+    """``I^-1 r`` for the symmetric ``I``: adjugate over determinant"""
+    a00 = iyy * izz - iyz * iyz
+    a01 = ixz * iyz - ixy * izz
+    a02 = ixy * iyz - ixz * iyy
+    a11 = ixx * izz - ixz * ixz
+    a12 = ixy * ixz - ixx * iyz
+    a22 = ixx * iyy - ixy * ixy
+    rdet = 1.0 / (ixx * a00 + ixy * a01 + ixz * a02)
+    return ((a00 * rx + a01 * ry + a02 * rz) * rdet,
+            (a01 * rx + a11 * ry + a12 * rz) * rdet,
+            (a02 * rx + a12 * ry + a22 * rz) * rdet)
+
+
+class RigidBodyMoments(Equation):
+    """total_mass, cm, mi (the inertia tensor about cm in mi[0..8]), force, ac, torque and omega_dot of every body,
+    from x y z m fx fy fz of ALL rows of the array and the bodies' omega.  On the device: ``sph_rigid_moments``, run
+    where this ``reduce`` would run (the hook itself is then not called)."""
+
+    def reduce(self, dst, t, dt):
+        nbody = int(dst.num_body[0])
+        order, start = body_index(dst.body_id, nbody)
+        mi = dst.mi
+        for b in range(nbody):
+            rows = order[start[b]:start[b + 1]]
+            m, x, y, z = dst.m[rows], dst.x[rows], dst.y[rows], dst.z[rows]
+            fx, fy, fz = dst.fx[rows], dst.fy[rows], dst.fz[rows]
+            mass = np.sum(m)
+            cx, cy, cz = np.sum(m * x) / mass, np.sum(m * y) / mass, np.sum(m * z) / mass
+            # about the origin, then to the centre of mass (parallel-axis theorem)
+            ixx = np.sum(m * (y * y + z * z)) - (cy * cy + cz * cz) * mass
+            iyy = np.sum(m * (x * x + z * z)) - (cx * cx + cz * cz) * mass
+            izz = np.sum(m * (x * x + y * y)) - (cx * cx + cy * cy) * mass
+            myz = np.sum(m * y * z)
+            ixy = cx * cy * mass - np.sum(m * x * y)
+            ixz = cx * cz * mass - np.sum(m * x * z)
+            iyz = cy * cz * mass - myz
+            force = (np.sum(fx), np.sum(fy), np.sum(fz))
+            origin = (np.sum(y * fz - z * fy), np.sum(z * fx - x * fz), np.sum(x * fy - y * fx))
+            torque = (origin[0] - (cy * force[2] - cz * force[1]),
+                      origin[1] - (cz * force[0] - cx * force[2]),
+                      origin[2] - (cx * force[1] - cy * force[0]))
+            dst.total_mass[b] = mass
+            dst.cm[3 * b:3 * b + 3] = (cx, cy, cz)
+            mi[16 * b:16 * b + 9] = (ixx, ixy, ixz, ixy, iyy, iyz, ixz, iyz, izz)
+            # (slots 9..15: what the reference's temporaries leave there)
+            mi[16 * b + 9] = -myz
+            mi[16 * b + 10:16 * b + 13] = force
+            mi[16 * b + 13:16 * b + 16] = origin
+            dst.force[3 * b:3 * b + 3] = force
+            dst.ac[3 * b:3 * b + 3] = (force[0] / mass, force[1] / mass, force[2] / mass)
+            dst.torque[3 * b:3 * b + 3] = torque
+            wx, wy, wz = dst.omega[3 * b:3 * b + 3]
+            lx = ixx * wx + ixy * wy + ixz * wz
+            ly = ixy * wx + iyy * wy + iyz * wz
+            lz = ixz * wx + iyz * wy + izz * wz
+            dst.omega_dot[3 * b:3 * b + 3] = solve_symmetric3(
+                ixx, iyy, izz, ixy, ixz, iyz,
+                torque[0] - (wy * lz - wz * ly), torque[1] - (wz * lx - wx * lz), torque[2] - (wx * ly - wy * lx))
+
+
+class RigidBodyMotion(Equation):
+    """``(u, v, w) = vc + omega x (r - cm)`` of the particle's body.  On the device: ``sph_rigid_motion``."""
+
+    def initialize(self, d_idx, d_x, d_y, d_z, d_u, d_v, d_w,
+                   d_cm, d_vc, d_ac, d_omega, d_body_id):
+        base = 3 * int(d_body_id[d_idx])
+        wx = d_omega[base]
+        wy = d_omega[base + 1]
+        wz = d_omega[base + 2]
+        rx = d_x[d_idx] - d_cm[base]
+        ry = d_y[d_idx] - d_cm[base + 1]
+        rz = d_z[d_idx] - d_cm[base + 2]
+        d_u[d_idx] = d_vc[base] + wy * rz - wz * ry
+        d_v[d_idx] = d_vc[base + 1] + wz * rx - wx * rz
+        d_w[d_idx] = d_vc[base + 2] + wx * ry - wy * rx
+
+
+def _advance_bodies(d_idx, d_num_body, new, old, rate, f):
+    """``new = old + f rate`` for the 3 nb components of a per-body vector, once per stage (particle 0)"""
+    if d_idx == 0:
+        for k in range(3 * int(d_num_body[0])):
+            new[k] = old[k] + f * rate[k]
+
+
+class EulerStepRigidBody(IntegratorStep):
+    """forward Euler for the bodies and their particles (one stage; for tests)"""
+
+    def initialize(self):
+        pass
+
+    def stage1(self, d_idx, d_u, d_v, d_w, d_x, d_y, d_z,
+               d_omega, d_omega_dot, d_vc, d_ac, d_num_body,
+               dt=0.0):
+        _advance_bodies(d_idx, d_num_body, d_vc, d_vc, d_ac, dt)
+        _advance_bodies(d_idx, d_num_body, d_omega, d_omega, d_omega_dot, dt)
+        d_x[d_idx] += dt * d_u[d_idx]
+        d_y[d_idx] += dt * d_v[d_idx]
+        d_z[d_idx] += dt * d_w[d_idx]
+
+
+class RK2StepRigidBody(IntegratorStep):
+    """midpoint rule: positions, vc and omega from their values at the start of the step (x0, vc0, omega0) and the
+    velocities / accelerations of the latest evaluation -- half a step in stage 1, the whole step in stage 2"""
+
+    def initialize(self, d_idx, d_x, d_y, d_z, d_x0, d_y0, d_z0,
+                   d_omega, d_omega0, d_vc, d_vc0, d_num_body):
+        if d_idx == 0:
+            for k in range(3 * int(d_num_body[0])):
+                d_vc0[k] = d_vc[k]
+                d_omega0[k] = d_omega[k]
+        d_x0[d_idx] = d_x[d_idx]
+        d_y0[d_idx] = d_y[d_idx]
+        d_z0[d_idx] = d_z[d_idx]
+
+    def _advance(self, f, d_idx, d_u, d_v, d_w, d_x, d_y, d_z, d_x0, d_y0, d_z0,
+                 d_omega, d_omega_dot, d_vc, d_ac, d_omega0, d_vc0, d_num_body):
+        _advance_bodies(d_idx, d_num_body, d_vc, d_vc0, d_ac, f)
+        _advance_bodies(d_idx, d_num_body, d_omega, d_omega0, d_omega_dot, f)
+        d_x[d_idx] = d_x0[d_idx] + f * d_u[d_idx]
+        d_y[d_idx] = d_y0[d_idx] + f * d_v[d_idx]
+        d_z[d_idx] = d_z0[d_idx] + f * d_w[d_idx]
+
+    def stage1(self, d_idx, d_u, d_v, d_w, d_x, d_y, d_z, d_x0, d_y0, d_z0,
+               d_omega, d_omega_dot, d_vc, d_ac, d_omega0, d_vc0, d_num_body,
+               dt=0.0):
+        self._advance(0.5 * dt, d_idx, d_u, d_v, d_w, d_x, d_y, d_z, d_x0, d_y0, d_z0,
+                      d_omega, d_omega_dot, d_vc, d_ac, d_omega0, d_vc0, d_num_body)
+
+    def stage2(self, d_idx, d_u, d_v, d_w, d_x, d_y, d_z, d_x0, d_y0, d_z0,
+               d_omega, d_omega_dot, d_vc, d_ac, d_omega0, d_vc0, d_num_body,
+               dt=0.0):
+        self._advance(dt, d_idx, d_u, d_v, d_w, d_x, d_y, d_z, d_x0, d_y0, d_z0,
+                      d_omega, d_omega_dot, d_vc, d_ac, d_omega0, d_vc0, d_num_body)
 
 
 class BodyForce(Equation):
