@@ -1356,8 +1356,10 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     EosArgs a;
     a.kind = e.kind;
     memcpy(a.par, e.par, sizeof a.par);
-    SPH_TRY(need_prop(c, e.dest, SPH_RHO, "EOS"));
-    SPH_TRY(sph_array_ensure_prop(c, e.dest, SPH_P));
+    if (e.kind != SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE) { // (reads v_ij, s_ij and G only: alone in a group, rho and p are not on the device)
+        SPH_TRY(need_prop(c, e.dest, SPH_RHO, "EOS"));
+        SPH_TRY(sph_array_ensure_prop(c, e.dest, SPH_P));
+    }
     a.rho = A.prop[SPH_RHO];
     a.p = A.prop[SPH_P];
     a.cs = nullptr;

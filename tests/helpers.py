@@ -385,3 +385,266 @@ def mp_kernel_wdw(kk, r, h, sigma, dim, xij=None):
         return w, dw
     tmp = dw * mp.mpf(h1) / mp.mpf(r) if r > 1e-12 else mp.mpf(0)
     return w, dw, [tmp * mp.mpf(float(c)) for c in xij]
+
+
+# ---------------------------------------------------------------------------
+# Equations without sources (k_nosrc): high-precision restatements of the reference's bodies, each with the
+# condition scale of every output element, and numpy restatements of the DEVICE arithmetic (for mutation runs)
+# ---------------------------------------------------------------------------
+U53 = 2.0 ** -53      # unit roundoff of fp64
+S6 = ('s00', 's01', 's02', 's11', 's12', 's22')
+R6 = ('r00', 'r01', 'r02', 'r11', 'r12', 'r22')
+AS6 = ('as00', 'as01', 'as02', 'as11', 'as12', 'as22')
+V9 = ('v00', 'v01', 'v02', 'v10', 'v11', 'v12', 'v20', 'v21', 'v22')
+_IJ6 = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+
+
+def _dps50(fn):
+    """run fn at 50 significant digits (mpf values keep the precision they were made with; operations round to the
+    working precision in force)"""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(*a, **k):
+        import mpmath as mp
+        with mp.workdps(50):
+            return fn(*a, **k)
+    return wrapped
+
+
+@_dps50
+def mp_tait(rho, rho0, c0, gamma, p0=0.0, hg=False):
+    """TaitEOS (wc/basic.py:60-65) or, with hg, TaitEOSHGCorrection (:118-126) at mpmath's working precision from the
+    fp64 inputs: {'rho': written-back density, 'p': (value, scale), 'cs': (value, scale)} with lists over rho.
+    Scale of p: B(|tmp| + 1) + |p0|; of cs (a single product): |c0 ratio^gamma1|."""
+    import mpmath as mp
+    f = mp.mpf
+    rho0, c0, gamma, p0 = f(float(rho0)), f(float(c0)), f(float(gamma)), f(float(p0))
+    rho01, gamma1, B = 1 / rho0, (gamma - 1) / 2, rho0 * c0 * c0 / gamma
+    out = {'rho': [], 'p': ([], []), 'cs': ([], [])}
+    for r in rho:
+        r = f(float(r))
+        if hg and r < rho0:
+            r = rho0
+        ratio = r * rho01
+        tmp = mp.power(ratio, gamma)
+        out['rho'].append(r)
+        out['p'][0].append(p0 + B * (tmp - 1))
+        out['p'][1].append(B * (abs(tmp) + 1) + abs(p0))
+        cs = c0 * mp.power(ratio, gamma1)
+        out['cs'][0].append(cs)
+        out['cs'][1].append(abs(cs))
+    return out
+
+
+@_dps50
+def mp_state_equation(rho, p0, rho0, b):
+    """transport_velocity.py:215-216: p0 (rho / rho0 - b); scale |p0| (|rho / rho0| + |b|)"""
+    import mpmath as mp
+    f = mp.mpf
+    p0, rho0, b = f(float(p0)), f(float(rho0)), f(float(b))
+    val = [p0 * (f(float(r)) / rho0 - b) for r in rho]
+    return {'p': (val, [abs(p0) * (abs(f(float(r)) / rho0) + abs(b)) for r in rho])}
+
+
+@_dps50
+def mp_isothermal(rho, rho0, c0, p0):
+    """basic_equations.py:175-176: p0 + c0^2 (rho - rho0); with p0 = 0 also solid_mech/basic.py:100-101
+    (c0_ref c0_ref (rho - rho_ref)).  Scale |p0| + c0^2 |rho - rho0|: the terms as the formula writes them."""
+    import mpmath as mp
+    f = mp.mpf
+    rho0, c0, p0 = f(float(rho0)), f(float(c0)), f(float(p0))
+    val = [p0 + c0 * c0 * (f(float(r)) - rho0) for r in rho]
+    return {'p': (val, [abs(p0) + c0 * c0 * abs(f(float(r)) - rho0) for r in rho])}
+
+
+@_dps50
+def mp_artificial_stress(rho, p, s6, eps):
+    """solid_mech/basic.py:170-242 with the eigen-decomposition of mpmath.eigsy: R = sum over lambda_k > 0 of
+    (-eps lambda_k / rho^2) v_k v_k^T of S = s - p I (formed exactly from the fp64 inputs).  Returns ({r00..r22:
+    (values, scales)}, eigenvalues per particle); the scale of all six components of a particle is eps |S|_F / rho^2."""
+    import mpmath as mp
+    f = mp.mpf
+    eps = f(float(eps))
+    out = dict((k, ([], [])) for k in R6)
+    lams = []
+    for i in range(len(rho)):
+        S = mp.zeros(3, 3)
+        for k, (a, b) in zip(S6, _IJ6):
+            S[a, b] = S[b, a] = f(float(s6[k][i]))
+        for a in range(3):
+            S[a, a] -= f(float(p[i]))
+        rho21 = 1 / (f(float(rho[i])) ** 2)
+        fro = mp.sqrt(sum(S[a, b] ** 2 for a in range(3) for b in range(3)))
+        if fro == 0:
+            E, Q = [f(0)] * 3, mp.eye(3)
+        else:
+            E, Q = mp.eigsy(S / fro)            # scaled like the reference: mpmath's iteration then sees O(1) entries
+            # an exact zero eigenvalue comes back as +-1e-50: below 1e-40 (ten digits above eigsy's own error at this
+            # precision, 24 below fp64's) it IS zero
+            E = [(e if abs(e) > mp.mpf(10) ** -40 else f(0)) * fro for e in E]
+        R = mp.zeros(3, 3)
+        for k in range(3):
+            if E[k] > 0:
+                rd = -eps * E[k] * rho21
+                for a in range(3):
+                    for b in range(a, 3):
+                        R[a, b] += Q[a, k] * rd * Q[b, k]
+        lams.append(list(E))
+        for k, (a, b) in zip(R6, _IJ6):
+            out[k][0].append(R[a, b])
+            out[k][1].append(eps * fro * rho21)
+    return out, lams
+
+
+@_dps50
+def mp_hooke(v9, s6, G, termwise=False):
+    """solid_mech/basic.py:418-505: as_ij = 2G (eps_ij - delta_ij trace) + sum_k s_ik omega_jk + sum_k s_kj omega_ik,
+    eps = (v + v^T)/2, omega = (v - v^T)/2, trace = (eps00 + eps11 + eps22)/3.  Scale of a component: |2G eps_ij|,
+    |2G trace| on the diagonal, and every |s omega| product of its two sums; with termwise the trace enters by ITS
+    terms, 2G (|eps00| + |eps11| + |eps22|) / 3 (a trace that cancels carries the roundings of its sum)."""
+    import mpmath as mp
+    f = mp.mpf
+    G2 = 2 * f(float(G))
+    out = dict((k, ([], [])) for k in AS6)
+    for n in range(len(v9['v00'])):
+        v = [[f(float(v9['v%d%d' % (a, b)][n])) for b in range(3)] for a in range(3)]
+        s = [[f(0)] * 3 for _ in range(3)]
+        for k, (a, b) in zip(S6, _IJ6):
+            s[a][b] = s[b][a] = f(float(s6[k][n]))
+        e = [[(v[a][b] + v[b][a]) / 2 for b in range(3)] for a in range(3)]
+        w = [[(v[a][b] - v[b][a]) / 2 for b in range(3)] for a in range(3)]
+        trace = (e[0][0] + e[1][1] + e[2][2]) / 3
+        for k, (i, j) in zip(AS6, _IJ6):
+            val = G2 * (e[i][j] - (trace if i == j else 0))
+            tr = (abs(e[0][0]) + abs(e[1][1]) + abs(e[2][2])) / 3 if termwise else abs(trace)
+            scale = abs(G2 * e[i][j]) + (abs(G2) * tr if i == j else 0)
+            for m in range(3):
+                val += s[i][m] * w[j][m] + s[m][j] * w[i][m]
+                scale += abs(s[i][m] * w[j][m]) + abs(s[m][j] * w[i][m])
+            out[k][0].append(val)
+            out[k][1].append(scale)
+    return out
+
+
+@_dps50
+def k_measure(got, ref):
+    """max over the elements of |got - ref| / (u scale), evaluated in mpmath so that the reference is never rounded;
+    an element of scale 0 (every term of its formula is zero) must be exact.  got: {name: fp64 array}, ref: {name:
+    (values, scales)}.  Returns (K, (name, index) of the worst element)."""
+    import mpmath as mp
+    worst, where = 0.0, None
+    u = mp.mpf(U53)
+    for name, (vals, scales) in ref.items():
+        g = got[name]
+        assert len(g) == len(vals), (name, len(g), len(vals))
+        for i in range(len(vals)):
+            d = abs(mp.mpf(float(g[i])) - vals[i])
+            if d == 0:
+                continue
+            k = float(d / (u * scales[i])) if scales[i] != 0 else float('inf')
+            if not k <= worst:
+                worst, where = k, (name, i)
+    return worst, where
+
+
+def np_jacobi_eigen3(S, max_sweeps=12, tol=1e-18):
+    """numpy restatement of the device's jacobi_eigen3 (pysph_amd/csrc/sph_eval.hip), statement by statement, without
+    fma contraction; max_sweeps / tol are the knobs the mutation runs turn"""
+    A = np.array(S, dtype=float)
+    V = np.eye(3)
+    for sweep in range(max_sweeps):
+        off = abs(A[0, 1]) + abs(A[0, 2]) + abs(A[1, 2])
+        diag = abs(A[0, 0]) + abs(A[1, 1]) + abs(A[2, 2])
+        if off <= 1e-300 or off <= tol * diag:
+            break
+        for p, q in ((0, 1), (0, 2), (1, 2)):
+            apq = A[p, q]
+            if apq == 0.0:
+                continue
+            with np.errstate(all='ignore'):
+                theta = (A[q, q] - A[p, p]) / (2.0 * apq)
+                t = (1.0 if theta >= 0 else -1.0) / (abs(theta) + np.sqrt(theta * theta + 1.0))
+            c = 1.0 / np.sqrt(t * t + 1.0)
+            s = t * c
+            A[p, p] -= t * apq
+            A[q, q] += t * apq
+            A[p, q] = A[q, p] = 0.0
+            r = 3 - p - q
+            arp, arq = A[r, p], A[r, q]
+            A[r, p] = A[p, r] = c * arp - s * arq
+            A[r, q] = A[q, r] = s * arp + c * arq
+            for k in range(3):
+                vkp, vkq = V[k, p], V[k, q]
+                V[k, p] = c * vkp - s * vkq
+                V[k, q] = s * vkp + c * vkq
+    return np.diag(A).copy(), V
+
+
+def np_artificial_stress(rho, p, s6, eps, mutation=None):
+    """numpy restatement of k_nosrc's SPH_EQ_MONAGHAN_ART_STRESS case (Gershgorin shortcut, scaling, Jacobi, the
+    lam > 0 selection, R diag(rd) R^T); returns {r00..r22: array}.  mutation: None, 'sweeps' (the Jacobi iteration
+    stops after two sweeps), ('gershgorin', r, c) (the term |S_rc| of row r's bound enters with the wrong sign) or 'ge'
+    (lam >= 0 in place of lam > 0)."""
+    n = len(rho)
+    out = dict((k, np.zeros(n)) for k in R6)
+    for i in range(n):
+        S = np.zeros((3, 3))
+        for k, (a, b) in zip(S6, _IJ6):
+            S[a, b] = S[b, a] = s6[k][i]
+        for a in range(3):
+            S[a, a] -= p[i]
+        rhoi21 = 1.0 / (rho[i] * rho[i])
+        sgn = np.ones((3, 3))
+        if isinstance(mutation, tuple) and mutation[0] == 'gershgorin':
+            sgn[mutation[1], mutation[2]] = -1.0
+        g0 = S[0, 0] + sgn[0, 1] * abs(S[0, 1]) + sgn[0, 2] * abs(S[0, 2])
+        g1 = S[1, 1] + sgn[1, 0] * abs(S[0, 1]) + sgn[1, 2] * abs(S[1, 2])
+        g2 = S[2, 2] + sgn[2, 0] * abs(S[0, 2]) + sgn[2, 1] * abs(S[1, 2])
+        if max(g0, g1, g2) <= 0.0:
+            continue
+        sc = 0.0
+        for a in range(3):
+            for b in range(3):
+                sc += abs(S[a, b])
+        if sc == 0.0:
+            lam, R = np.zeros(3), np.eye(3)
+        else:
+            lam, R = np_jacobi_eigen3(S / sc, max_sweeps=2 if mutation == 'sweeps' else 12)
+            lam = lam * sc
+        rd = np.zeros(3)
+        for k in range(3):
+            if (lam[k] >= 0 if mutation == 'ge' else lam[k] > 0):
+                rd[k] = -eps * lam[k] * rhoi21
+        for key, (a, b) in zip(R6, _IJ6):
+            t = 0.0
+            for k in range(3):
+                t += R[a, k] * rd[k] * R[b, k]
+            out[key][i] = t
+    return out
+
+
+def np_tait(rho, rho0, c0, gamma, p0=0.0, hg=False, mutation=None):
+    """numpy restatement of k_nosrc's two Tait cases (rho (1 / rho0); powers by multiplication for gamma in 1, 3, 5, 7
+    as tait_powers forms them, pow otherwise); mutation 'short': the power of gamma = 2 gk + 1 one multiplication
+    short"""
+    rho = np.array(rho, dtype=float)
+    if hg:
+        rho = np.where(rho < rho0, rho0, rho)
+    ratio = rho * (1.0 / rho0)
+    gk = {7.0: 3, 5.0: 2, 3.0: 1, 1.0: 0}.get(float(gamma), -1)
+    r2 = ratio * ratio
+    if gk == 3:
+        rk = r2 * ratio
+        rg = (r2 * r2) * (r2 if mutation == 'short' else rk)
+    elif gk == 2:
+        rk = r2
+        rg = (r2 * r2) if mutation == 'short' else (r2 * r2) * ratio
+    elif gk == 1:
+        rk = ratio
+        rg = r2 if mutation == 'short' else r2 * ratio
+    elif gk == 0:
+        rk, rg = np.ones_like(ratio), ratio
+    else:
+        rg, rk = np.power(ratio, gamma), np.power(ratio, 0.5 * (gamma - 1.0))
+    return {'rho': rho, 'p': p0 + (rho0 * c0 * c0 / gamma) * (rg - 1.0), 'cs': c0 * rk}
