@@ -61,8 +61,17 @@ enum sph_kernel_kind {
     SPH_K_CUBIC_SPLINE = 1,     /* kernels.py:29 */
     SPH_K_WENDLAND_QUINTIC = 2, /* kernels.py:274 */
     SPH_K_QUINTIC_SPLINE = 3,   /* kernels.py:1050 */
-    SPH_K_GAUSSIAN = 4          /* kernels.py:830 */
+    SPH_K_GAUSSIAN = 4,         /* kernels.py:830 */
+    SPH_K_WENDLAND_QUINTIC_C2_1D = 5, /* kernels.py:166   dim 1 only */
+    SPH_K_WENDLAND_QUINTIC_C4 = 6,    /* kernels.py:493   dim 2, 3 */
+    SPH_K_WENDLAND_QUINTIC_C4_1D = 7, /* kernels.py:383   dim 1 only */
+    SPH_K_WENDLAND_QUINTIC_C6 = 8,    /* kernels.py:719   dim 2, 3 */
+    SPH_K_WENDLAND_QUINTIC_C6_1D = 9, /* kernels.py:606   dim 1 only */
+    SPH_K_SUPER_GAUSSIAN = 10         /* kernels.py:944   the shape depends on dim */
 };
+/* A kind outside 1..10, or one with a dimension its class does not support,
+ * makes sph_eval_group / sph_eval_generated / sph_interpolate return
+ * SPH_ERR_UNSUPPORTED before anything is launched.                        */
 
 /* Kernel object fields copied by value, as the generated Cython does
  * (acceleration_eval_cython_helper.py:240-245).                          */

@@ -1641,22 +1641,25 @@ class GeneratedFamily(object):
         A('#include "sph_pair.h"')
         A('#include <cstring>')
         A('')
+        # SphKernel<KK>::w / dw take the dimension as a trailing argument that only the SuperGaussian (id 10) reads
+        # and has no default for: the other kernels keep the one-argument call, and with it their source text
+        kdim, gdim = (', a.k.dim', ', g.dim') if self.kernel_kind == 10 else ('', '')
         A('// kernel functions by (r, h) for loop_all bodies: SPH_KERNEL.kernel / gradient / dwdq')
         A('template <int KK, class A> __device__ __forceinline__ double gen_kernel_w(double rij, double h, const A &a)')
         A('{')
         A('    const double h1 = 1.0 / h;')
-        A('    return kernel_norm(a.k.sigma, h1, a.k.dim) * SphKernel<KK>::template w<false>(rij * h1);')
+        A('    return kernel_norm(a.k.sigma, h1, a.k.dim) * SphKernel<KK>::template w<false>(rij * h1%s);' % kdim)
         A('}')
         A('template <int KK, class A> __device__ __forceinline__ double gen_kernel_dwdq(double rij, double h, const A &a)')
         A('{')
         A('    const double h1 = 1.0 / h;')
-        A('    return kernel_norm(a.k.sigma, h1, a.k.dim) * SphKernel<KK>::template dw<false>(rij * h1);')
+        A('    return kernel_norm(a.k.sigma, h1, a.k.dim) * SphKernel<KK>::template dw<false>(rij * h1%s);' % kdim)
         A('}')
         A('template <int KK, class A>')
         A('__device__ __forceinline__ void gen_kernel_gradient(const double *xij, double rij, double h, double *grad, const A &a)')
         A('{')
         A('    const double h1 = 1.0 / h;')
-        A('    const double wdash = kernel_norm(a.k.sigma, h1, a.k.dim) * SphKernel<KK>::template dw<false>(rij * h1);')
+        A('    const double wdash = kernel_norm(a.k.sigma, h1, a.k.dim) * SphKernel<KK>::template dw<false>(rij * h1%s);' % kdim)
         A('    const double tmp = rij > 1e-12 ? wdash * h1 / rij : 0.0;     // kernels.py:126-137')
         A('    grad[0] = tmp * xij[0]; grad[1] = tmp * xij[1]; grad[2] = tmp * xij[2];')
         A('}')
@@ -1767,7 +1770,7 @@ class GeneratedFamily(object):
         if 'WIJ' in S:
             A('        const double WIJ = pair_w<KK, UH>(g);')
         if 'WDP' in S:   # KERNEL(XIJ, DELTAP*HIJ, HIJ), equation.py:243-246
-            A('        const double WDP = SphKernel<KK>::template w<false>((a.k.deltap * g.hij) * g.h1) * g.fac;')
+            A('        const double WDP = SphKernel<KK>::template w<false>((a.k.deltap * g.hij) * g.h1%s) * g.fac;' % gdim)
         if 'DWIJ' in S:
             A('        const double tg_ = pair_gradfac<KK, UH>(g);')
             A('        const double DWIJ[3] = {tg_ * XIJ[0], tg_ * XIJ[1], tg_ * XIJ[2]};')

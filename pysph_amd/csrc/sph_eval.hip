@@ -34,6 +34,15 @@
 #include <cmath>
 #include <type_traits>
 
+// 0: the primary compile (everything; pair kernels of SphKernel<1..4>).  5..10: a kernel unit -- the pair kernels of
+// that one smoothing kernel behind externally linked launch functions, nothing else (see launch_pair_k below)
+#ifndef SPH_KERNEL_UNIT
+#define SPH_KERNEL_UNIT 0
+#endif
+#define SPH_PRIMARY_UNIT (SPH_KERNEL_UNIT == 0)
+
+#if SPH_PRIMARY_UNIT
+
 // ---------------------------------------------------------------------------
 // equations without sources (elementwise)
 // ---------------------------------------------------------------------------
@@ -197,6 +206,8 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
     }
     }
 }
+
+#endif // SPH_PRIMARY_UNIT
 
 // ---------------------------------------------------------------------------
 // equation families
@@ -503,7 +514,7 @@ template <class T> struct FamWCSPH_T {
     {
         PairGeomT<T> g;
         // (one transcendental per pair where the momentum equation acts: pair_geom_mom)
-        constexpr bool MRG = SPH_MERGED_RSQ && sizeof(T) == 8 && KK != 4;
+        constexpr bool MRG = SPH_MERGED_RSQ && sizeof(T) == 8 && !SphKernel<KK>::CUTOFF;
         T tt_m = T(0.0);
         if constexpr (MRG) {
             if (fl & F_MOM) tt_m = pair_geom_mom<KK, UH>(g, pi, pj, r2, T(0.5) * (D.rho + s[4]), a);
@@ -541,7 +552,7 @@ template <class T> struct FamWCSPH_T {
                 if (fl & F_TENSILE) {
                     // WDP = KERNEL(XIJ, DELTAP*HIJ, HIJ)  equation.py:243-246
                     const T qd = (a.k.deltap * g.hij) * g.h1;
-                    const T wdp = SphKernel<KK>::w(qd) * g.fac;
+                    const T wdp = SphKernel<KK>::w(qd, g.dim) * g.fac;
                     T fij = wij * fast_rcp(wdp);
                     fij = fij * fij;
                     fij = fij * fij;
@@ -763,7 +774,7 @@ template <class T> struct FamWCSPHM_T : FamWCSPHE_T<T, true> {
                                                 const T (&s)[8], uint32_t ct, const A &a, bool pass = true)
     {
         PairGeomT<T> g;
-        constexpr bool MRG = SPH_MERGED_RSQ && sizeof(T) == 8 && KK != 4;
+        constexpr bool MRG = SPH_MERGED_RSQ && sizeof(T) == 8 && !SphKernel<KK>::CUTOFF;
         T tt_m = T(0.0);
         if constexpr (MRG) tt_m = pair_geom_mom<KK, UH>(g, pi, pj, r2, T(0.5) * (D.rho + s[4]), a);
         else pair_geom<KK, UH>(g, pi, pj, r2, a);
@@ -1333,6 +1344,7 @@ template <class Fam, int KK, bool UH> __global__ __launch_bounds__(256) void k_p
 // ---------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------
+#if SPH_PRIMARY_UNIT
 static bool is_nosrc_kind(int k)
 {
     return k == SPH_EQ_TAIT_EOS || k == SPH_EQ_TAIT_EOS_HG || k == SPH_EQ_TVF_STATE_EQUATION ||
@@ -1607,9 +1619,16 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
     return SPH_OK;
 }
 
-template <class Fam> static int launch_pair(sph_ctx *c, int kk, const PairArgs<Fam> &a)
+#endif // SPH_PRIMARY_UNIT
+
+// ---------------------------------------------------------------------------
+// launch entry points, one smoothing kernel each.  The pair kernels of SphKernel<1..4> are instantiated by the primary
+// compile of this file; those of SphKernel<5..10> by one further compile per id (-DSPH_KERNEL_UNIT=<id>, Makefile),
+// which emits nothing but the externally linked *_ext functions below for the families listed at the end of the
+// file.  The primary compile only declares them and forwards ids 5..10.
+// ---------------------------------------------------------------------------
+template <class Fam, int K> static int launch_pair_k(sph_ctx *c, const PairArgs<Fam> &a)
 {
-    if (a.nd == 0) return SPH_OK;
     const bool uh = c->uniform_h && c->use_uniform_h;
     constexpr bool FP32 = sizeof(typename Fam::Real) == 4;
     if (c->pair_variant == 6) {
@@ -1618,20 +1637,12 @@ template <class Fam> static int launch_pair(sph_ctx *c, int kk, const PairArgs<F
         uint32_t cf = a.src[0].flags;
         for (int j = 1; j < a.nsrc; j++) if (a.src[j].flags != cf) cf = 0;
         if (c->const_flags == 0) cf = 0;
-#define LAUNCH6F(K, UHV, F32V, CFV) hipLaunchKernelGGL((k_pair_wave<Fam, K, UHV, F32V, CFV>), g2, b2, (size_t)c->lds_pad, c->stream, a)
-#define LAUNCH6U(K, F32V)                                                                                 \
-        if (uh) { if (cf == Fam::CF0) LAUNCH6F(K, true, F32V, Fam::CF0); else LAUNCH6F(K, true, F32V, 0); }  \
-        else { if (cf == Fam::CF0) LAUNCH6F(K, false, F32V, Fam::CF0); else LAUNCH6F(K, false, F32V, 0); }
-#define LAUNCH6(K)                                                       \
-        if constexpr (FP32) { LAUNCH6U(K, true) }                        \
-        else { if (c->record_f32) { LAUNCH6U(K, true) } else { LAUNCH6U(K, false) } }
-        switch (kk) {
-        case 1: LAUNCH6(1); break;
-        case 2: LAUNCH6(2); break;
-        case 3: LAUNCH6(3); break;
-        case 4: LAUNCH6(4); break;
-        }
-#undef LAUNCH6
+#define LAUNCH6F(UHV, F32V, CFV) hipLaunchKernelGGL((k_pair_wave<Fam, K, UHV, F32V, CFV>), g2, b2, (size_t)c->lds_pad, c->stream, a)
+#define LAUNCH6U(F32V)                                                                              \
+        if (uh) { if (cf == Fam::CF0) LAUNCH6F(true, F32V, Fam::CF0); else LAUNCH6F(true, F32V, 0); }  \
+        else { if (cf == Fam::CF0) LAUNCH6F(false, F32V, Fam::CF0); else LAUNCH6F(false, F32V, 0); }
+        if constexpr (FP32) { LAUNCH6U(true) }
+        else { if (c->record_f32) { LAUNCH6U(true) } else { LAUNCH6U(false) } }
 #undef LAUNCH6U
 #undef LAUNCH6F
         return SPH_OK;
@@ -1641,24 +1652,15 @@ template <class Fam> static int launch_pair(sph_ctx *c, int kk, const PairArgs<F
         return SPH_ERR_UNSUPPORTED;
     } else {
         dim3 gd(div_up(a.nd, 256)), bd(256);
-#define LAUNCH(K)                                                                                \
-        if (uh) hipLaunchKernelGGL((k_pair_direct<Fam, K, true>), gd, bd, 0, c->stream, a);      \
-        else hipLaunchKernelGGL((k_pair_direct<Fam, K, false>), gd, bd, 0, c->stream, a)
-        switch (kk) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        case 4: LAUNCH(4); break;
-        }
-#undef LAUNCH
+        if (uh) hipLaunchKernelGGL((k_pair_direct<Fam, K, true>), gd, bd, 0, c->stream, a);
+        else hipLaunchKernelGGL((k_pair_direct<Fam, K, false>), gd, bd, 0, c->stream, a);
         return SPH_OK;
     }
 }
 
 // the EOS-fused WCSPH family: uniform h, variant 6 only (sph_eval_group checks)
-template <class Fam, bool UHV = true> static int launch_pair_fused(sph_ctx *c, int kk, const PairArgs<Fam> &a)
+template <class Fam, bool UHV, int K> static int launch_pair_fused_k(sph_ctx *c, const PairArgs<Fam> &a)
 {
-    if (a.nd == 0) return SPH_OK;
     constexpr bool FP32 = sizeof(typename Fam::Real) == 4;
     dim3 g2(div_up(4 * div_up(a.nd, 256), WPB)), b2(64 * WPB);
     uint32_t cf = a.src[0].flags;
@@ -1667,31 +1669,115 @@ template <class Fam, bool UHV = true> static int launch_pair_fused(sph_ctx *c, i
     if constexpr (fam_rowlds<Fam>::value && UHV) {
         if (c->row_lds && !a.nl_mode && !a.face_mode) { // the experiment of round 6: source records of a row tile in LDS
             dim3 g1(4 * div_up(a.nd, 256)), b1(64);
-#define LAUNCHL(K)                                                                                              \
-            if (cf == Fam::CF0) hipLaunchKernelGGL((k_pair_rowlds<Fam, K, Fam::CF0>), g1, b1, 0, c->stream, a); \
-            else hipLaunchKernelGGL((k_pair_rowlds<Fam, K, 0>), g1, b1, 0, c->stream, a)
-            switch (kk) {
-            case 1: LAUNCHL(1); break;
-            case 2: LAUNCHL(2); break;
-            case 3: LAUNCHL(3); break;
-            case 4: LAUNCHL(4); break;
-            }
-#undef LAUNCHL
+            if (cf == Fam::CF0) hipLaunchKernelGGL((k_pair_rowlds<Fam, K, Fam::CF0>), g1, b1, 0, c->stream, a);
+            else hipLaunchKernelGGL((k_pair_rowlds<Fam, K, 0>), g1, b1, 0, c->stream, a);
             c->timers[T_N_ROWLDS].count++;
             return SPH_OK;
         }
     }
-#define LAUNCHE(K)                                                                                                              \
-    if (cf == Fam::CF0) hipLaunchKernelGGL((k_pair_wave<Fam, K, UHV, FP32, Fam::CF0>), g2, b2, (size_t)c->lds_pad, c->stream, a); \
-    else hipLaunchKernelGGL((k_pair_wave<Fam, K, UHV, FP32, 0>), g2, b2, (size_t)c->lds_pad, c->stream, a)
-    switch (kk) {
-    case 1: LAUNCHE(1); break;
-    case 2: LAUNCHE(2); break;
-    case 3: LAUNCHE(3); break;
-    case 4: LAUNCHE(4); break;
-    }
-#undef LAUNCHE
+    if (cf == Fam::CF0) hipLaunchKernelGGL((k_pair_wave<Fam, K, UHV, FP32, Fam::CF0>), g2, b2, (size_t)c->lds_pad, c->stream, a);
+    else hipLaunchKernelGGL((k_pair_wave<Fam, K, UHV, FP32, 0>), g2, b2, (size_t)c->lds_pad, c->stream, a);
     return SPH_OK;
+}
+
+template <class T> struct FamWCSPHMV_T;
+// the merged multi-array WCSPH family (eval_group_merged)
+template <class Fm, int K> static int launch_pair_merged_k(sph_ctx *c, const PairArgs<Fm> &a)
+{
+    constexpr bool FP32 = sizeof(typename Fm::Real) == 4;
+    dim3 g2(div_up(4 * div_up(a.nd, 256), WPB)), b2(64 * WPB);
+    constexpr bool UHM = !std::is_base_of<FamWCSPHMV_T<typename Fm::Real>, Fm>::value; // uniform h unless the family carries h
+    hipLaunchKernelGGL((k_pair_wave<Fm, K, UHM, FP32, Fm::CF0>), g2, b2, (size_t)c->lds_pad, c->stream, a);
+    return SPH_OK;
+}
+
+// the interpolator's families (sph_interp.h): fp64, run-time equation flags
+template <class Fam, int K> static int launch_interp_k(sph_ctx *c, const PairArgs<Fam> &a)
+{
+    const bool uh = c->uniform_h && c->use_uniform_h;
+    dim3 g2(div_up(4 * div_up(a.nd, 256), WPB)), b2(64 * WPB);
+    if (uh) hipLaunchKernelGGL((k_pair_wave<Fam, K, true, false, 0>), g2, b2, 0, c->stream, a);
+    else hipLaunchKernelGGL((k_pair_wave<Fam, K, false, false, 0>), g2, b2, 0, c->stream, a);
+    return SPH_OK;
+}
+
+template <class Fam, int K> int launch_pair_ext(sph_ctx *c, const PairArgs<Fam> &a);
+template <class Fam, bool UHV, int K> int launch_pair_fused_ext(sph_ctx *c, const PairArgs<Fam> &a);
+template <class Fm, int K> int launch_pair_merged_ext(sph_ctx *c, const PairArgs<Fm> &a);
+template <class Fam, int K> int launch_interp_ext(sph_ctx *c, const PairArgs<Fam> &a);
+
+#if SPH_KERNEL_UNIT == 0
+static int bad_kernel_kind(const char *who, int kk)
+{
+    sph_set_error("%s: unknown smoothing kernel kind %d (1..10, sphhip.h enum sph_kernel_kind)", who, kk);
+    return SPH_ERR_UNSUPPORTED;
+}
+// kind and dimension, checked once per entry point: the 1-D Wendlands exist in one dimension only, the 2-D / 3-D
+// ones not in one (kernels.py raises ValueError for these)
+static int check_kernel(const char *who, const sph_kernel *K)
+{
+    const int kk = K->kind;
+    if (kk < 1 || kk > 10) return bad_kernel_kind(who, kk);
+    if (K->dim < 1 || K->dim > 3) { sph_set_error("%s: kernel dimension %d (1..3)", who, K->dim); return SPH_ERR_UNSUPPORTED; }
+    const bool only1 = kk == SPH_K_WENDLAND_QUINTIC_C2_1D || kk == SPH_K_WENDLAND_QUINTIC_C4_1D || kk == SPH_K_WENDLAND_QUINTIC_C6_1D;
+    const bool not1 = kk == SPH_K_WENDLAND_QUINTIC_C4 || kk == SPH_K_WENDLAND_QUINTIC_C6;
+    if ((only1 && K->dim != 1) || (not1 && K->dim == 1)) {
+        sph_set_error("%s: smoothing kernel kind %d: Dim %d not supported", who, kk, K->dim);
+        return SPH_ERR_UNSUPPORTED;
+    }
+    return SPH_OK;
+}
+
+// SPH_KERNEL_SWITCH(kk, who, F): F<1..4> from this compile, F<5..10> from the kernel units
+#define SPH_KERNEL_SWITCH(KK, WHO, LOCAL, EXT)                        \
+    switch (KK) {                                                     \
+    case 1: return LOCAL(1);                                          \
+    case 2: return LOCAL(2);                                          \
+    case 3: return LOCAL(3);                                          \
+    case 4: return LOCAL(4);                                          \
+    case 5: return EXT(5);                                            \
+    case 6: return EXT(6);                                            \
+    case 7: return EXT(7);                                            \
+    case 8: return EXT(8);                                            \
+    case 9: return EXT(9);                                            \
+    case 10: return EXT(10);                                          \
+    default: return bad_kernel_kind(WHO, KK);                         \
+    }
+
+template <class Fam> static int launch_pair(sph_ctx *c, int kk, const PairArgs<Fam> &a)
+{
+    if (a.nd == 0) return SPH_OK;
+#define L_(K) launch_pair_k<Fam, K>(c, a)
+#define E_(K) launch_pair_ext<Fam, K>(c, a)
+    SPH_KERNEL_SWITCH(kk, "pair loop", L_, E_)
+#undef L_
+#undef E_
+}
+template <class Fam, bool UHV = true> static int launch_pair_fused(sph_ctx *c, int kk, const PairArgs<Fam> &a)
+{
+    if (a.nd == 0) return SPH_OK;
+#define L_(K) launch_pair_fused_k<Fam, UHV, K>(c, a)
+#define E_(K) launch_pair_fused_ext<Fam, UHV, K>(c, a)
+    SPH_KERNEL_SWITCH(kk, "fused pair loop", L_, E_)
+#undef L_
+#undef E_
+}
+template <class Fm> static int launch_pair_merged(sph_ctx *c, int kk, const PairArgs<Fm> &a)
+{
+#define L_(K) launch_pair_merged_k<Fm, K>(c, a)
+#define E_(K) launch_pair_merged_ext<Fm, K>(c, a)
+    SPH_KERNEL_SWITCH(kk, "merged pair loop", L_, E_)
+#undef L_
+#undef E_
+}
+template <class Fam> static int interp_launch(sph_ctx *c, int kk, const PairArgs<Fam> &a)
+{
+    if (a.nd == 0) return SPH_OK;
+#define L_(K) launch_interp_k<Fam, K>(c, a)
+#define E_(K) launch_interp_ext<Fam, K>(c, a)
+    SPH_KERNEL_SWITCH(kk, "sph_interpolate", L_, E_)
+#undef L_
+#undef E_
 }
 
 template <class Fam>
@@ -1983,18 +2069,7 @@ static int eval_group_merged(sph_ctx *c, const sph_kernel *K, const sph_group *g
             }
             if (all_real) use_dest_list(c, a, M);
         }
-        constexpr bool FP32 = sizeof(typename Fm::Real) == 4;
-        dim3 g2(div_up(4 * div_up(a.nd, 256), WPB)), b2(64 * WPB);
-        constexpr bool UHM = !std::is_base_of<FamWCSPHMV_T<typename Fm::Real>, Fm>::value; // uniform h unless the family carries h
-#define LAUNCHM(KV) hipLaunchKernelGGL((k_pair_wave<Fm, KV, UHM, FP32, Fm::CF0>), g2, b2, (size_t)c->lds_pad, c->stream, a)
-        switch (K->kind) {
-        case 1: LAUNCHM(1); break;
-        case 2: LAUNCHM(2); break;
-        case 3: LAUNCHM(3); break;
-        case 4: LAUNCHM(4); break;
-        }
-#undef LAUNCHM
-        return SPH_OK;
+        return launch_pair_merged<Fm>(c, K->kind, a);
     };
     if (vh) SPH_TRY(f32 ? run(FamWCSPHMV_T<float>()) : run(FamWCSPHMV_T<double>()));
     else SPH_TRY(f32 ? run(FamWCSPHM_T<float>()) : run(FamWCSPHM_T<double>()));
@@ -2008,7 +2083,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
     if (!c || !K || !g) { sph_set_error("sph_eval_group: NULL argument"); return SPH_ERR_ARG; }
     c->cur_dt = dt;
     if (g->neq > SPH_MAX_EQS) { sph_set_error("sph_eval_group: too many equations"); return SPH_ERR_ARG; }
-    if (K->kind < 1 || K->kind > 4) { sph_set_error("sph_eval_group: unknown kernel kind %d", K->kind); return SPH_ERR_UNSUPPORTED; }
+    SPH_TRY(check_kernel("sph_eval_group", K));
     HIP_TRY(hipSetDevice(c->device));
     if (!c->pack_group) c->pack_epoch++; // packed records are reused between the destinations of ONE group only (option pack_group)
     {
@@ -2465,7 +2540,7 @@ extern "C" int sph_eval_generated(sph_ctx *c, const sph_kernel *K, sph_gen_famil
 static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_gen_family *f, double t, double dt, double *d_state)
 {
     if (!c || !K || !f || !f->launch) { sph_set_error("sph_eval_generated: NULL argument"); return SPH_ERR_ARG; }
-    if (K->kind < 1 || K->kind > 4) { sph_set_error("sph_eval_generated: unknown kernel kind %d", K->kind); return SPH_ERR_UNSUPPORTED; }
+    SPH_TRY(check_kernel("sph_eval_generated", K));
     if (f->dest < 0 || f->dest >= SPH_MAX_ARRAYS || !c->arr[f->dest].used) { sph_set_error("sph_eval_generated: bad dest array %d", f->dest); return SPH_ERR_ARG; }
     if (f->nsrc < 0 || f->nsrc > SPH_MAX_ARRAYS || f->n_sprops < 0 || f->n_sprops > SPH_GEN_MAX_SPROPS || f->n_sprops > MAX_AUX ||
         f->n_din < 0 || f->n_din > SPH_GEN_MAX_PROPS || f->n_dout < 0 || f->n_dout > SPH_GEN_MAX_PROPS || f->npar < 0 ||
@@ -2733,7 +2808,45 @@ static int reduce_minmax(sph_ctx *c, int id, int prop, double *out, bool want_ma
     return SPH_OK;
 }
 
+#endif // SPH_KERNEL_UNIT == 0
+
 // ---------------------------------------------------------------------------
 // interpolation of particle fields onto points (sph_interpolate)
 // ---------------------------------------------------------------------------
 #include "sph_interp.h"
+
+// ---------------------------------------------------------------------------
+// a kernel unit: the *_ext launch functions of ONE smoothing kernel, for every family the primary compile forwards
+// (a family missing here is an undefined symbol when libsphhip.so is linked: the Makefile links with -z defs)
+// ---------------------------------------------------------------------------
+#if !SPH_PRIMARY_UNIT
+template <class Fam, int K> int launch_pair_ext(sph_ctx *c, const PairArgs<Fam> &a) { return launch_pair_k<Fam, K>(c, a); }
+template <class Fam, bool UHV, int K> int launch_pair_fused_ext(sph_ctx *c, const PairArgs<Fam> &a) { return launch_pair_fused_k<Fam, UHV, K>(c, a); }
+template <class Fm, int K> int launch_pair_merged_ext(sph_ctx *c, const PairArgs<Fm> &a) { return launch_pair_merged_k<Fm, K>(c, a); }
+template <class Fam, int K> int launch_interp_ext(sph_ctx *c, const PairArgs<Fam> &a) { return launch_interp_k<Fam, K>(c, a); }
+
+#define UNIT_PAIR(F) template int launch_pair_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
+#define UNIT_FUSED(F, UHV) template int launch_pair_fused_ext<F, UHV, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
+#define UNIT_MERGED(F) template int launch_pair_merged_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
+#define UNIT_INTERP(F) template int launch_interp_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
+#define UNIT_BOTH(M, F) M(F<double>); M(F<float>)
+UNIT_BOTH(UNIT_PAIR, FamWCSPH_T);
+UNIT_BOTH(UNIT_PAIR, FamDensity_T);
+UNIT_BOTH(UNIT_PAIR, FamTVF_T);
+UNIT_BOTH(UNIT_PAIR, FamVGrad_T);
+UNIT_BOTH(UNIT_PAIR, FamElastic_T);
+#define UNIT_FUSED_UH(F) UNIT_FUSED(F, true)
+#define UNIT_FUSED_VH(F) UNIT_FUSED(F, false)
+typedef FamWCSPHE_T<double, false> UnitE_d; typedef FamWCSPHE_T<double, true> UnitEU_d;
+typedef FamWCSPHE_T<float, false> UnitE_f; typedef FamWCSPHE_T<float, true> UnitEU_f;
+typedef FamWCSPHEG_T<double, false> UnitEG_d; typedef FamWCSPHEG_T<double, true> UnitEGU_d;
+typedef FamWCSPHEG_T<float, false> UnitEG_f; typedef FamWCSPHEG_T<float, true> UnitEGU_f;
+UNIT_FUSED_UH(UnitE_d); UNIT_FUSED_UH(UnitEU_d); UNIT_FUSED_UH(UnitE_f); UNIT_FUSED_UH(UnitEU_f);
+UNIT_FUSED_UH(UnitEG_d); UNIT_FUSED_UH(UnitEGU_d); UNIT_FUSED_UH(UnitEG_f); UNIT_FUSED_UH(UnitEGU_f);
+UNIT_BOTH(UNIT_FUSED_VH, FamWCSPHV_T);
+UNIT_BOTH(UNIT_FUSED_UH, FamTVFE_T);
+UNIT_BOTH(UNIT_FUSED_UH, FamElasticU_T);
+UNIT_BOTH(UNIT_MERGED, FamWCSPHM_T);
+UNIT_BOTH(UNIT_MERGED, FamWCSPHMV_T);
+UNIT_INTERP(FamInterpSum); UNIT_INTERP(FamInterpMom); UNIT_INTERP(FamInterpRhs);
+#endif

@@ -210,6 +210,7 @@ struct FamInterpRhs {
     }
 };
 
+#if SPH_PRIMARY_UNIT   // the host side and its element-wise kernel: the primary compile of sph_eval.hip only
 // m / rho per particle (original order): the v of the records
 __global__ __launch_bounds__(256) void k_interp_vol(const double *__restrict__ m, const double *__restrict__ rho, double *__restrict__ out, size_t n)
 {
@@ -243,29 +244,14 @@ static int interp_pack(sph_ctx *c, int id, size_t off, int na, const double *con
     return SPH_OK;
 }
 
-template <class Fam> static void interp_launch(sph_ctx *c, int kk, const PairArgs<Fam> &a)
-{
-    if (a.nd == 0) return;
-    const bool uh = c->uniform_h && c->use_uniform_h;
-    dim3 g2(div_up(4 * div_up(a.nd, 256), WPB)), b2(64 * WPB);
-#define LAUNCHI(K)                                                                                 \
-    if (uh) hipLaunchKernelGGL((k_pair_wave<Fam, K, true, false, 0>), g2, b2, 0, c->stream, a);    \
-    else hipLaunchKernelGGL((k_pair_wave<Fam, K, false, false, 0>), g2, b2, 0, c->stream, a)
-    switch (kk) {
-    case 1: LAUNCHI(1); break;
-    case 2: LAUNCHI(2); break;
-    case 3: LAUNCHI(3); break;
-    case 4: LAUNCHI(4); break;
-    }
-#undef LAUNCHI
-}
+// interp_launch: sph_eval.hip, with the other kernel-kind switches
 
 extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int dest, int nsrc, const int *srcs,
                                int nprops, const int *props, const int *out_props, double *host_out, size_t n_pull)
 {
     if (!c || !K || !srcs || !props || (!out_props && !host_out)) { sph_set_error("sph_interpolate: NULL argument"); return SPH_ERR_ARG; }
     if (method < SPH_INTERP_SHEPARD || method > SPH_INTERP_SPLASH_NORM) { sph_set_error("sph_interpolate: unknown method %d", method); return SPH_ERR_ARG; }
-    if (K->kind < 1 || K->kind > 4) { sph_set_error("sph_interpolate: unknown kernel kind %d", K->kind); return SPH_ERR_ARG; }
+    SPH_TRY(check_kernel("sph_interpolate", K));
     if (dest < 0 || dest >= SPH_MAX_ARRAYS || !c->arr[dest].used) { sph_set_error("sph_interpolate: bad destination array %d", dest); return SPH_ERR_ARG; }
     if (nsrc < 1 || nsrc + 1 > SPH_MAX_ARRAYS) { sph_set_error("sph_interpolate: %d source arrays (1..%d)", nsrc, SPH_MAX_ARRAYS - 1); return SPH_ERR_ARG; }
     for (int j = 0; j < nsrc; j++) {
@@ -395,7 +381,7 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
             a.p.mom = c->interp_mom.as<double>();
             {
                 ScopedTimer tm(c, T_PAIR);
-                interp_launch<FamInterpMom>(c, K->kind, a);
+                SPH_TRY(interp_launch<FamInterpMom>(c, K->kind, a));
             }
             c->timers[T_N_INTERP_MOM].count++;
             mc.valid = true; mc.epoch = c->nnps_epoch; mc.dest = dest; mc.nsrc = nsrc; mc.kind = K->kind; mc.dim = K->dim;
@@ -456,13 +442,13 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
             a.p.mom = c->interp_mom.as<double>();
             for (int k = 0; k < np; k++)
                 for (int r = 0; r < 4; r++) a.p.out[k][r] = out_ptr[4 * (p0 + k) + r];
-            interp_launch<FamInterpRhs>(c, K->kind, a);
+            SPH_TRY(interp_launch<FamInterpRhs>(c, K->kind, a));
         } else {
             PairArgs<FamInterpSum> a;
             memset(&a, 0, sizeof a);
             common(a, FamInterpSum::NR, flags);
             for (int k = 0; k < np; k++) a.p.out[k] = out_ptr[p0 + k];
-            interp_launch<FamInterpSum>(c, K->kind, a);
+            SPH_TRY(interp_launch<FamInterpSum>(c, K->kind, a));
         }
         c->timers[T_N_INTERP_SWEEP].count++;
     }
@@ -474,3 +460,4 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
     }
     return SPH_OK;
 }
+#endif // SPH_PRIMARY_UNIT

@@ -8,6 +8,11 @@
 // the gradient (the reference recomputes them in every method).
 // INSUP = true: the caller guarantees q < radius_scale (uniform-h pairs that
 // passed the neighbour criterion), so the support test is dropped.
+// Every function takes the dimension as a trailing argument; only the
+// SuperGaussian, whose shape depends on it, reads it.  CUTOFF: the kernel is
+// cut off where it is not zero (Gaussian, SuperGaussian).  GRADH_FLIPPED: the
+// reference's gradient_h of this class has the opposite sign of
+// -fac h1 (dw q + w dim), see SphKernel<10>.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,16 +47,16 @@ template <class R> __device__ __forceinline__ R kernel_norm(R sigma, R h1, int d
 }
 
 template <> struct SphKernel<1> { // CubicSpline
-    static constexpr bool HAS_DWQ = false;
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R) { return R(0); }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q)
+    static constexpr bool HAS_DWQ = false, CUTOFF = false, GRADH_FLIPPED = false;
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R, int = 0) { return R(0); }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
     {
         R t2 = R(2) - q;
         R a = R(0.25) * t2 * t2 * t2;
         R b = R(1) - R(1.5) * q * q * (R(1) - R(0.5) * q);
         return (!INSUP && q > R(2)) ? R(0) : (q > R(1) ? a : b);
     }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
     {
         R t2 = R(2) - q;
         R a = R(-0.75) * t2 * t2;
@@ -64,18 +69,19 @@ template <> struct SphKernel<1> { // CubicSpline
 // same value -- and the same bits, sign of the zero included, as INSUP = true, which has no test at all.
 template <> struct SphKernel<2> { // WendlandQuintic
     static constexpr bool HAS_DWQ = true; // dw/q = -5 (1 - q/2)^3: no division by r needed
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q)
+    static constexpr bool CUTOFF = false, GRADH_FLIPPED = false;
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0)
     {
         R t = R(1) - R(0.5) * q;
         return (INSUP || q <= R(2)) ? R(-5) * t * t * t : R(0);
     }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
     {
         R t = R(1) - R(0.5) * q;
         R v = t * t * t * t * (R(2) * q + R(1));
         return (INSUP || q <= R(2)) ? v : R(0);
     }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
     {
         R t = R(1) - R(0.5) * q;
         R v = R(-5) * q * t * t * t;
@@ -84,9 +90,9 @@ template <> struct SphKernel<2> { // WendlandQuintic
 };
 
 template <> struct SphKernel<3> { // QuinticSpline
-    static constexpr bool HAS_DWQ = false;
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R) { return R(0); }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q)
+    static constexpr bool HAS_DWQ = false, CUTOFF = false, GRADH_FLIPPED = false;
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R, int = 0) { return R(0); }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
     {
         // the branches q <= 2, q <= 1 of kernels.py:1120-1140 as max(., 0): a term beyond its knot is exactly zero,
         // so the value is the reference's bit for bit, without two compare-and-select pairs
@@ -96,7 +102,7 @@ template <> struct SphKernel<3> { // QuinticSpline
         v += R(15) * t1 * t1 * t1 * t1 * t1;
         return (!INSUP && q > R(3)) ? R(0) : v;
     }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
     {
         R t3 = R(3) - q, t2 = raw_max(R(2) - q, R(0)), t1 = raw_max(R(1) - q, R(0));
         R v = R(-5) * t3 * t3 * t3 * t3;
@@ -112,10 +118,152 @@ template <> struct SphKernel<3> { // QuinticSpline
 // (the polynomial kernels vanish at their support radius, there INSUP is safe).
 template <> struct SphKernel<4> { // Gaussian
     static constexpr bool HAS_DWQ = true; // dw/q = -2 exp(-q^2)
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q) { return (q < R(3)) ? R(-2) * exp(-q * q) : R(0); }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q) { return (q < R(3)) ? exp(-q * q) : R(0); }
-    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q)
+    static constexpr bool GRADH_FLIPPED = false;
+    static constexpr bool CUTOFF = true;  // not zero at q = 3: exact q, support test kept (sph_pair.h pair_geom)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0) { return (q < R(3)) ? R(-2) * exp(-q * q) : R(0); }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0) { return (q < R(3)) ? exp(-q * q) : R(0); }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
     {
         return (q < R(3)) ? R(-2) * q * exp(-q * q) : R(0);
+    }
+};
+
+// ---------------------------------------------------------------------------
+// The Wendland family beyond C2 (kernels.py: C2_1D :166-272, C4_1D :383-491, C4 :493-604, C6_1D :606-717,
+// C6 :719-828).  All are t^n poly(q) with t = 1 - q/2, and dW/dq = -c q t^(n-1) poly'(q): t is an exact zero at q == 2,
+// so q <= 2 gives the reference's q < 2 bit for bit and INSUP drops the test (as for SphKernel<2>); dw / q has no
+// division.  Powers of t by squaring.
+// ---------------------------------------------------------------------------
+template <> struct SphKernel<5> { // WendlandQuinticC2_1D: t^3 (1.5 q + 1)
+    static constexpr bool HAS_DWQ = true, CUTOFF = false, GRADH_FLIPPED = false; // dw/q = -3 t^2
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q;
+        return (INSUP || q <= R(2)) ? R(-3) * t * t : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q;
+        R v = t * t * t * (R(1.5) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q;
+        R v = R(-3) * q * t * t;
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+};
+
+template <> struct SphKernel<6> { // WendlandQuinticC4 (2-D, 3-D): t^6 (35/12 q^2 + 3 q + 1)
+    static constexpr bool HAS_DWQ = true, CUTOFF = false, GRADH_FLIPPED = false; // dw/q = -14/3 (1 + 2.5 q) t^5
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = R(-14.0 / 3.0) * (R(1) + R(2.5) * q) * (t2 * t2 * t);
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = (t2 * t2 * t2) * ((R(35.0 / 12.0) * q + R(3)) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = R(-14.0 / 3.0) * q * (R(1) + R(2.5) * q) * (t2 * t2 * t);
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+};
+
+template <> struct SphKernel<7> { // WendlandQuinticC4_1D: t^5 (2 q^2 + 2.5 q + 1)
+    static constexpr bool HAS_DWQ = true, CUTOFF = false, GRADH_FLIPPED = false; // dw/q = -3.5 (2 q + 1) t^4
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = R(-3.5) * (R(2) * q + R(1)) * (t2 * t2);
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = (t2 * t2 * t) * ((R(2) * q + R(2.5)) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = R(-3.5) * q * (R(2) * q + R(1)) * (t2 * t2);
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+};
+
+template <> struct SphKernel<8> { // WendlandQuinticC6 (2-D, 3-D): t^8 (4 q^3 + 6.25 q^2 + 4 q + 1)
+    static constexpr bool HAS_DWQ = true, CUTOFF = false, GRADH_FLIPPED = false; // dw/q = -5.5 t^7 (1 + 3.5 q + 4 q^2)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t, t4 = t2 * t2;
+        R v = R(-5.5) * (t4 * t2 * t) * ((R(4) * q + R(3.5)) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t, t4 = t2 * t2;
+        R v = (t4 * t4) * (((R(4) * q + R(6.25)) * q + R(4)) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t, t4 = t2 * t2;
+        R v = R(-5.5) * q * (t4 * t2 * t) * ((R(4) * q + R(3.5)) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+};
+
+template <> struct SphKernel<9> { // WendlandQuinticC6_1D: t^7 (2.625 q^3 + 4.75 q^2 + 3.5 q + 1)
+    static constexpr bool HAS_DWQ = true, CUTOFF = false, GRADH_FLIPPED = false; // dw/q = -0.5 (26.25 q^2 + 27 q + 9) t^6
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = R(-0.5) * ((R(26.25) * q + R(27)) * q + R(9)) * (t2 * t2 * t2);
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t, t4 = t2 * t2;
+        R v = (t4 * t2 * t) * (((R(2.625) * q + R(4.75)) * q + R(3.5)) * q + R(1));
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
+    {
+        R t = R(1) - R(0.5) * q, t2 = t * t;
+        R v = R(-0.5) * q * ((R(26.25) * q + R(27)) * q + R(9)) * (t2 * t2 * t2);
+        return (INSUP || q <= R(2)) ? v : R(0);
+    }
+};
+
+// SuperGaussian (kernels.py:944-1048): exp(-q^2) (1 + dim/2 - q^2), negative beyond q^2 = 1 + dim/2 and cut off at
+// q = 3 where it is -9e-4 of its peak: like the Gaussian it keeps its support test under INSUP and takes the exact q.
+// Its gradient_h (:1027-1047) is a closed form of its own, (-d^2/2 + 2 d q^2 - d - 2 q^4 + 4 q^2) exp(-q^2) times
+// -fac h1 -- which is +fac h1 (dw q + w d), the NEGATIVE of dW/dh and of what every other class returns.  GHIJ / GHI /
+// GHJ of a reference script carry that sign, so pair_gradh reproduces it.
+template <> struct SphKernel<10> {
+    static constexpr bool GRADH_FLIPPED = true;
+    static constexpr bool HAS_DWQ = true, CUTOFF = true; // dw/q = (2 q^2 - dim - 4) exp(-q^2)
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dwq(R q, int dim)
+    {
+        R q2 = q * q;
+        return (q < R(3)) ? (R(2) * q2 - R(dim + 4)) * exp(-q2) : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R w(R q, int dim)
+    {
+        R q2 = q * q;
+        return (q < R(3)) ? exp(-q2) * (R(1) + R(0.5) * R(dim) - q2) : R(0);
+    }
+    template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int dim)
+    {
+        R q2 = q * q;
+        return (q < R(3)) ? q * (R(2) * q2 - R(dim + 4)) * exp(-q2) : R(0);
     }
 };

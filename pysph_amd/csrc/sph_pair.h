@@ -219,6 +219,7 @@ __device__ __forceinline__ void fast_sqrt_rsqrt(float a, float &s, float &rs)
 template <class T> struct PairGeomT {
     T xij[3];
     T r2, rij, rinv, hij, h1, q, fac, eps;
+    int dim; // read by kernels whose shape depends on it (SuperGaussian)
 };
 typedef PairGeomT<double> PairGeom;
 
@@ -234,8 +235,8 @@ __device__ __forceinline__ void pair_geom(PairGeomT<T> &g, const real4<T> &pi, c
     // depending on the last bit of q, so q must be the reference's own
     // q = sqrt(r2) * (1/h) with correctly rounded sqrt and division.  The
     // polynomial kernels vanish at their support radius; the ~1 ulp fast paths
-    // are invisible there.
-    constexpr bool EXACT_Q = (KK == 4);
+    // are invisible there.  The same holds for every kernel with the CUTOFF trait.
+    constexpr bool EXACT_Q = SphKernel<KK>::CUTOFF;
     if (EXACT_Q) {
         g.rij = sqrt(r2);
         g.rinv = g.rij > T(0) ? T(1) / g.rij : T(0);
@@ -251,6 +252,7 @@ __device__ __forceinline__ void pair_geom(PairGeomT<T> &g, const real4<T> &pi, c
         g.eps = T(0.01) * g.hij * g.hij;                                     // EPS  :194
     }
     g.q = g.rij * g.h1;
+    g.dim = a.k.dim;
 }
 // The same with ONE transcendental for the pair (fp64): the momentum equation needs 1 / ((r2 + eps) rhoij) next to
 // r = sqrt(r2) and 1 / r.  With P = (r2 + eps) rhoij:  t = rsqrt(r2 P^2) = 1 / (r P)  =>  1/r = t P,  r = r2 (1/r),
@@ -285,14 +287,16 @@ __device__ __forceinline__ double pair_geom_mom(PairGeomT<double> &g, const doub
     g.rinv = t * P;
     g.rij = r2c * g.rinv;
     g.q = g.rij * g.h1;
+    g.dim = a.k.dim;
     return t * g.rij;               // 1 / P
 }
 
-template <int KK, bool UH, class T> __device__ __forceinline__ T pair_w(const PairGeomT<T> &g) { return SphKernel<KK>::template w<UH>(g.q) * g.fac; }
+template <int KK, bool UH, class T> __device__ __forceinline__ T pair_w(const PairGeomT<T> &g) { return SphKernel<KK>::template w<UH>(g.q, g.dim) * g.fac; }
 // GRADH(XIJ, RIJ, h) = dW/dh (kernels.py gradient_h, e.g. :138-163): -fac*h1*(dw*q + w*dim)
 template <int KK, bool UH, class T> __device__ __forceinline__ T pair_gradh(const PairGeomT<T> &g, int dim)
 {
-    return -g.fac * g.h1 * (SphKernel<KK>::template dw<UH>(g.q) * g.q + SphKernel<KK>::template w<UH>(g.q) * (T)dim);
+    const T v = g.fac * g.h1 * (SphKernel<KK>::template dw<UH>(g.q, dim) * g.q + SphKernel<KK>::template w<UH>(g.q, dim) * (T)dim);
+    return SphKernel<KK>::GRADH_FLIPPED ? v : -v;
 }
 // GRADIENT(XIJ, RIJ, HIJ, DWIJ) (kernels.py:126-137) returns tmp*xij with
 // tmp = dwdq*h1/rij; here tmp only.  dw(q)/rij = dwq(q)*h1 when the kernel has
@@ -300,8 +304,8 @@ template <int KK, bool UH, class T> __device__ __forceinline__ T pair_gradh(cons
 template <int KK, bool UH, class T> __device__ __forceinline__ T pair_gradfac(const PairGeomT<T> &g)
 {
     T t;
-    if (SphKernel<KK>::HAS_DWQ) t = SphKernel<KK>::template dwq<UH>(g.q) * (g.fac * g.h1 * g.h1);
-    else t = SphKernel<KK>::template dw<UH>(g.q) * (g.fac * g.h1) * g.rinv;
+    if (SphKernel<KK>::HAS_DWQ) t = SphKernel<KK>::template dwq<UH>(g.q, g.dim) * (g.fac * g.h1 * g.h1);
+    else t = SphKernel<KK>::template dw<UH>(g.q, g.dim) * (g.fac * g.h1) * g.rinv;
     return g.rij > T(1e-12) ? t : T(0);
 }
 

@@ -13,12 +13,22 @@ conditions, ``get_correction``), never part of the accelerated path.
     WendlandQuintic  kernels.py:274-380    radius_scale 2, deltap 1/2
     QuinticSpline    kernels.py:1050-1210  radius_scale 3, deltap 0.7593...
     Gaussian         kernels.py:830-930    radius_scale 3, deltap 1/sqrt(2)
+    WendlandQuinticC2_1D  kernels.py:166-272   1-D        radius_scale 2, deltap 2/3
+    WendlandQuinticC4     kernels.py:493-604   2-D, 3-D   radius_scale 2, deltap 0.47114274
+    WendlandQuinticC4_1D  kernels.py:383-491   1-D        radius_scale 2, deltap 0.55195628
+    WendlandQuinticC6     kernels.py:719-828   2-D, 3-D   radius_scale 2, deltap 0.4305720757
+    WendlandQuinticC6_1D  kernels.py:606-717   1-D        radius_scale 2, deltap 0.47996698
+    SuperGaussian         kernels.py:944-1048  1-D..3-D   radius_scale 3, deltap by dim
+
+The ids of ``KERNEL_IDS`` are ``enum sph_kernel_kind`` of include/sphhip.h.
 """
 import math
 import numpy as np
 
 KERNEL_IDS = {'CubicSpline': 1, 'WendlandQuintic': 2, 'QuinticSpline': 3,
-              'Gaussian': 4}
+              'Gaussian': 4, 'WendlandQuinticC2_1D': 5, 'WendlandQuinticC4': 6,
+              'WendlandQuinticC4_1D': 7, 'WendlandQuinticC6': 8,
+              'WendlandQuinticC6_1D': 9, 'SuperGaussian': 10}
 
 
 class _Kernel(object):
@@ -127,6 +137,102 @@ class Gaussian(_Kernel):
     @staticmethod
     def _dw(q):
         return np.where(q < 3.0, -2.0 * q * np.exp(-q * q), 0.0)
+
+
+class _Wendland(_Kernel):
+    """t^n poly(q) with t = 1 - q/2 inside q < 2; dW/dq = c q dpoly(q) t^(n-1)"""
+    radius_scale = 2.0
+    _n = 0
+    _poly = staticmethod(lambda q: q)
+    _c = 0.0
+    _dpoly = staticmethod(lambda q: q)
+
+    def _w(self, q):
+        t = 1. - 0.5 * q
+        return np.where(q < 2.0, t ** self._n * self._poly(q), 0.0)
+
+    def _dw(self, q):
+        t = 1. - 0.5 * q
+        return np.where(q < 2.0, self._c * q * self._dpoly(q) * t ** (self._n - 1), 0.0)
+
+
+class WendlandQuinticC2_1D(_Wendland):
+    _sigma = {1: 5.0 / 8.0}
+    _deltap = 2.0 / 3
+    _n = 3
+    _poly = staticmethod(lambda q: 1.5 * q + 1.0)
+    _c = -3.0
+    _dpoly = staticmethod(lambda q: 1.0)
+
+    def __init__(self, dim=1):
+        _Kernel.__init__(self, dim)
+
+
+class WendlandQuinticC4(_Wendland):
+    _sigma = {2: 9.0 * (1.0 / math.pi) / 4.0, 3: (1.0 / math.pi) * 495.0 / 256.0}
+    _deltap = 0.47114274
+    _n = 6
+    _poly = staticmethod(lambda q: (35.0 / 12.0) * q * q + 3.0 * q + 1.0)
+    _c = -14.0 / 3.0
+    _dpoly = staticmethod(lambda q: 1 + 2.5 * q)
+
+
+class WendlandQuinticC4_1D(_Wendland):
+    _sigma = {1: 0.75}
+    _deltap = 0.55195628
+    _n = 5
+    _poly = staticmethod(lambda q: 2 * q * q + 2.5 * q + 1.0)
+    _c = -3.5
+    _dpoly = staticmethod(lambda q: 2 * q + 1)
+
+    def __init__(self, dim=1):
+        _Kernel.__init__(self, dim)
+
+
+class WendlandQuinticC6(_Wendland):
+    _sigma = {2: 78.0 * (1.0 / math.pi) / 28.0, 3: (1.0 / math.pi) * 1365.0 / 512.0}
+    _deltap = 0.4305720757
+    _n = 8
+    _poly = staticmethod(lambda q: 4.0 * q * q * q + 6.25 * q * q + 4.0 * q + 1.0)
+    _c = -5.5
+    _dpoly = staticmethod(lambda q: 1.0 + 3.5 * q + 4 * q * q)
+
+
+class WendlandQuinticC6_1D(_Wendland):
+    _sigma = {1: 55.0 / 64.0}
+    _deltap = 0.47996698
+    _n = 7
+    _poly = staticmethod(lambda q: 2.625 * q * q * q + 4.75 * q * q + 3.5 * q + 1.0)
+    _c = -0.5
+    _dpoly = staticmethod(lambda q: 26.25 * q * q + 27 * q + 9.0)
+
+    def __init__(self, dim=1):
+        _Kernel.__init__(self, dim)
+
+
+class SuperGaussian(_Kernel):
+    """exp(-q^2) (1 + dim/2 - q^2), cut off at q = 3; negative beyond
+    q^2 = 1 + dim/2"""
+    radius_scale = 3.0
+    _sigma = Gaussian._sigma
+    _deltap_dim = {1: 0.584540507426389, 2: 0.6021141014644256, 3: 0.615369528365158}
+
+    def get_deltap(self):
+        return self._deltap_dim[self.dim]
+
+    def _w(self, q):
+        q2 = q * q
+        return np.where(q < 3.0, np.exp(-q2) * (1.0 + self.dim * 0.5 - q2), 0.0)
+
+    def _dw(self, q):
+        q2 = q * q
+        return np.where(q < 3.0, q * (2.0 * q2 - self.dim - 4) * np.exp(-q2), 0.0)
+
+    def gradient_h(self, xij=(0., 0., 0.), rij=1.0, h=1.0):
+        """The reference's own closed form (kernels.py:1027-1047), which is
+        +fac h1 (dw q + w dim): the opposite sign of dW/dh and of every other
+        class's gradient_h.  Kept, since GHIJ of a reference script has it."""
+        return -_Kernel.gradient_h(self, xij, rij, h)
 
 
 def get_correction(kernel, h0):
