@@ -49,6 +49,10 @@ enum sph_prop {
     SPH_AS00, SPH_AS01, SPH_AS02, SPH_AS11, SPH_AS12, SPH_AS22,
     SPH_R00, SPH_R01, SPH_R02, SPH_R11, SPH_R12, SPH_R22,
     SPH_S000, SPH_S010, SPH_S020, SPH_S110, SPH_S120, SPH_S220,
+    /* delta-SPH (WCSPHScheme(delta_sph=True)): the strided m_mat (9) and gradrho (3) of the reference as
+     * component columns "m_mat__0".."m_mat__8", "gradrho__0".."gradrho__2"                                */
+    SPH_MMAT0, SPH_MMAT1, SPH_MMAT2, SPH_MMAT3, SPH_MMAT4, SPH_MMAT5, SPH_MMAT6, SPH_MMAT7, SPH_MMAT8,
+    SPH_GRADRHO0, SPH_GRADRHO1, SPH_GRADRHO2,
     /* user properties: slots named at run time with sph_prop_register (the
      * reference's ParticleArray.add_property for equation-specific arrays,
      * e.g. uf, ug, wij of the TVF wall equations)                           */
@@ -104,7 +108,17 @@ enum sph_eq_kind {
     SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE = 17, /* solid_mech/basic.py:390  par: G (= d_G[0]) */
     SPH_EQ_MOMENTUM_WITH_STRESS = 18, /* solid_mech/basic.py:245  par: wdeltap n (= d_wdeltap[0], d_n[0]) */
     SPH_EQ_MONAGHAN_ART_STRESS = 19,  /* solid_mech/basic.py:104  par: eps */
-    SPH_EQ_SOLID_ISOTHERMAL_EOS = 21  /* solid_mech/basic.py:93   par: c0_ref rho_ref */
+    SPH_EQ_SOLID_ISOTHERMAL_EOS = 21, /* solid_mech/basic.py:93   par: c0_ref rho_ref */
+    /* WCSPHScheme options delta_sph / nu / update_h.  The strided properties m_mat (9) and gradrho (3) are the
+     * columns SPH_MMAT0..8 and SPH_GRADRHO0..2 of enum sph_prop.                                               */
+    SPH_EQ_GRADIENT_CORRECTION_PRESTEP = 22,  /* wc/kernel_correction.py:40  par: dim   (writes m_mat; a group of its own) */
+    SPH_EQ_GRADIENT_CORRECTION = 23,          /* wc/kernel_correction.py:77  par: dim tol   (corrects DWIJ of id 24 behind it) */
+    SPH_EQ_CONTINUITY_DELTA_SPH_PRESTEP = 24, /* wc/basic.py:346   (writes gradrho) */
+    SPH_EQ_CONTINUITY_DELTA_SPH = 25,         /* wc/basic.py:372   par: c0 delta   (with id 3 on the same destination) */
+    SPH_EQ_MOMENTUM_DELTA_SPH = 26,           /* wc/basic.py:272   par: rho0 c0 alpha   (with id 4) */
+    SPH_EQ_LAMINAR_VISCOSITY = 27,            /* wc/viscosity.py:6     par: nu eta   (with id 4) */
+    SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH = 28,  /* wc/viscosity.py:116   par: dim rho0 nu   (with id 4) */
+    SPH_EQ_UPDATE_H_FERRARI = 29              /* wc/basic.py:417   par: dim1 (= 1 / dim) hdx   (no sources; writes h) */
 };
 
 /* One Equation(dest, sources) instance: pysph/sph/equation.py:392-420. */
@@ -779,7 +793,9 @@ int sph_timer_enable(sph_ctx *ctx, int on);
 int sph_timer_reset(sph_ctx *ctx);
 /* keys: "nnps", "pack", "eos", "pair", "stage"; the pair launches once more per
  * equation family: "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad",
- * "pair_elastic"; out: total ms and launches.  Launch counters (ms = 0, counted
+ * "pair_elastic", "pair_wcsph_options" (the rates of a WCSPH destination with
+ * delta-SPH or laminar-viscosity terms), "pair_delta_sph_pre" (moment matrix and
+ * renormalised density gradient); out: total ms and launches.  Launch counters (ms = 0, counted
  * whether or not timing is enabled): "n_eos_fused" (pair launches on the 64-byte
  * EOS-fused records), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group
  * evaluations run as one launch over the merged order), "n_tension_flag" (elastic rate launches that read the tension word), "n_phase2" (pair launches of the second half of a

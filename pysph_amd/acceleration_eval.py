@@ -249,6 +249,19 @@ def is_builtin(eq):
         return False
 
 
+def _columns(pa, props):
+    """property names as the device holds them: a strided property (``m_mat``, stride 9) is its component columns
+    ``m_mat__0`` .. ``m_mat__8`` (device.py: ``_component``; ``enum sph_prop`` SPH_MMAT0.., SPH_GRADRHO0..)"""
+    out = []
+    for p in props:
+        stride = getattr(pa, 'stride', {}).get(p, 1)
+        if stride > 1:
+            out.extend('%s__%d' % (p, k) for k in range(stride))
+        else:
+            out.append(p)
+    return out
+
+
 class _BuiltinUnit(object):
     """Equations of one destination with hand-written kernels, marshalled for
     ``sph_eval_group``."""
@@ -258,8 +271,14 @@ class _BuiltinUnit(object):
         self.eqs = eqs
         self.ceqs = (dev.SphEquation * max(len(eqs), 1))()
         self._const_params = []
+        self.delta_sph_arrays = set()     # arrays whose m_mat / gradrho this unit reads or writes
         for i, eq in enumerate(eqs):
             kind, vals, dprops, sprops = resolve_equation(eq)
+            if kind in _DELTA_SPH_KINDS:
+                self.delta_sph_arrays.update([eq.dest] + list(eq.sources or []))
+            dprops = _columns(arrays[eq.dest], dprops)
+            if kind == _UPDATE_H_KIND:
+                owner.outputs_exact[eq.dest].add('h')      # (the tables' 'h' is an input everywhere else)
             ce = self.ceqs[i]
             ce.kind = kind
             ce.dest = array_ids[eq.dest]
@@ -275,7 +294,7 @@ class _BuiltinUnit(object):
             owner.inputs[eq.dest].update(dprops)
             owner.outputs[eq.dest].update(dprops)
             for s in srcs:
-                owner.inputs[s].update(sprops)
+                owner.inputs[s].update(_columns(arrays[s], sprops))
         self.cg = dev.SphGroup()
         self.cg.real = 1 if group.real else 0
         self.cg.neq = len(eqs)
@@ -305,7 +324,22 @@ class _BuiltinUnit(object):
             self.ceqs[i].par[k] = float(_get(self._arrays[dest], cname)[0])
         self.cg.start_idx, self.cg.stop_idx = start, stop
 
+    def _check(self, ev):
+        """m_mat and gradrho are computed per evaluation for the rows a rank holds; ghost rows (a slab's Remote
+        particles, periodic or mirror images) would need gradrho carried to them between the passes"""
+        for name in sorted(self.delta_sph_arrays):
+            pa = self._arrays[name]
+            owner = getattr(ev.helpers[name], 'ghost_owner', None)
+            if getattr(pa, 'slab_decomposed', False) or owner is not None:
+                raise NotImplementedError(
+                    "delta-SPH equations on array '%s': not supported on a slab-decomposed array or one with periodic "
+                    "/ mirror images%s -- the ghost rows would need gradrho (and m_mat) carried to them between the "
+                    "passes of one evaluation; stale values are not computed with"
+                    % (name, ' (ghosts managed by %s)' % owner if owner else ''))
+
     def run(self, ev, t, dt, phase=0):
+        if self.delta_sph_arrays:
+            self._check(ev)
         self.cg.phase = phase
         try:
             dev._check(ev.lib.sph_eval_group(
@@ -537,6 +571,9 @@ class _CGroup(object):
             for u in self.units:
                 u.run(ev, t, dt)
             return
+        for u in self.units:
+            if u.delta_sph_arrays:
+                u._check(ev)
         if getattr(self, '_combined', None) is None:
             self._combined = self._combined_group()
         cg, ceqs = self._combined
@@ -557,6 +594,8 @@ class _CGroup(object):
             ev.ctx._h, C.byref(ev.ckernel), C.byref(cg), t, dt))
 
 
+_DELTA_SPH_KINDS = (22, 23, 24, 25)   # moment matrix, gradient correction, gradrho pre-step, delta-SPH continuity
+_UPDATE_H_KIND = 29             # SPH_EQ_UPDATE_H_FERRARI
 _TAIT_KINDS = (1, 2)            # SPH_EQ_TAIT_EOS, SPH_EQ_TAIT_EOS_HG
 _WCSPH_PAIR_KINDS = (3, 4, 5)   # SPH_EQ_CONTINUITY, SPH_EQ_MOMENTUM, SPH_EQ_XSPH
 _TVF_DENSITY_KIND = 7           # SPH_EQ_TVF_SUMMATION_DENSITY

@@ -67,7 +67,9 @@ static const char *PROP_NAMES[SPH_USER0] = {
     "s00", "s01", "s02", "s11", "s12", "s22",
     "as00", "as01", "as02", "as11", "as12", "as22",
     "r00", "r01", "r02", "r11", "r12", "r22",
-    "s000", "s010", "s020", "s110", "s120", "s220"};
+    "s000", "s010", "s020", "s110", "s120", "s220",
+    "m_mat__0", "m_mat__1", "m_mat__2", "m_mat__3", "m_mat__4", "m_mat__5", "m_mat__6", "m_mat__7", "m_mat__8",
+    "gradrho__0", "gradrho__1", "gradrho__2"};
 
 extern "C" {
 
@@ -457,6 +459,7 @@ int sph_timer_get(sph_ctx *c, const char *key, double *ms, long *count)
 {
     static const char *names[T_COUNT] = {"nnps", "pack", "eos", "pair", "stage",
                                          "pair_none", "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad", "pair_elastic",
+                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre",
                                          "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep"};
     SPH_TRY(timer_drain(c));
     for (int i = 0; i < T_COUNT; i++)

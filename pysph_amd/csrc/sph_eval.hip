@@ -204,6 +204,9 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
         q[SPH_AS22][i] = tmp * (eps22 - trace) + (s20 * omega20 + s21 * omega21) + (s02 * omega20 + s12 * omega21);
         break;
     }
+    case SPH_EQ_UPDATE_H_FERRARI: // wc/basic.py:459-463; par dim1 (= 1 / dim) hdx
+        a.q[SPH_H][i] = a.par[1] * pow(a.q[SPH_M][i] / a.rho[i], a.par[0]);
+        break;
     }
 }
 
@@ -214,6 +217,8 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
 // ---------------------------------------------------------------------------
 enum { F_VG2 = 1, F_VG3 = 2,                                            // velocity gradient
        F_ECONT = 1, F_ESTRESS = 2, F_EAV = 4, F_EXSPH = 8 };            // elastic rates
+enum { F_DCONT = 16, F_DMOM = 32, F_LAM = 64, F_LAMD = 128,             // WCSPH options (next to the WCSPH flags below)
+       F_MOMENT = 1, F_GRADRHO = 2, F_GCORR = 4 };                      // delta-SPH pre-passes
 enum { F_CONT = 1, F_MOM = 2, F_XSPH = 4, F_TENSILE = 8,               // WCSPH
        F_SD = 1, F_TVFSD = 2,                                           // density
        F_TP = 1, F_TVISC = 2, F_TAV = 4, F_TAS = 8 };                   // TVF force
@@ -880,6 +885,222 @@ __device__ __forceinline__ void load_record_wcsph(const double *__restrict__ rj,
 template <> __device__ __forceinline__ void load_record<FamWCSPH, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[8]) { load_record_wcsph<true>(rj, fl, pj, s); }
 template <> __device__ __forceinline__ void load_record<FamWCSPH, false>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[8]) { load_record_wcsph<false>(rj, fl, pj, s); }
 
+// ---- WCSPHScheme options: delta-SPH, laminar viscosity ---------------------------------
+// The rates group of WCSPHScheme(delta_sph=True and / or nu != 0) in ONE sweep: Continuity / Momentum / XSPH exactly as
+// FamWCSPH_T evaluates them, plus
+//   F_DCONT  ContinuityEquationDeltaSPH   wc/basic.py:400-414   (reads gradrho of destination and source)
+//   F_DMOM   MomentumEquationDeltaSPH     wc/basic.py:326-343
+//   F_LAM    LaminarViscosity             wc/viscosity.py:12-27
+//   F_LAMD   LaminarViscosityDeltaSPH     wc/viscosity.py:134-144
+// per (destination, source) like every other flag.  All terms add into arho / au av aw before finish(), so dt_force sees
+// the summed acceleration as the reference's post_loop does.  Records [x y z h | u v w m rho p/rho^2 cs p] and, with
+// DS (a delta-SPH continuity term acts on this destination), three more values: the source's gradrho.
+// The new terms are the reference's, regrouped as FamWCSPH_T::pair regroups (DWIJ = tg XIJ, reciprocals shared); the
+// one place where terms cancel -- psi = fac XIJ - gradrho_i - gradrho_j -- keeps the reference's order.
+template <class T, bool DS> struct FamWCSPHX_T : FamWCSPH_T<T> {
+    typedef FamWCSPH_T<T> Base;
+    static constexpr uint32_t CF0 = DS ? (F_CONT | F_MOM | F_XSPH | F_DCONT | F_DMOM | F_LAMD) : (F_CONT | F_MOM | F_XSPH | F_LAM);
+    static constexpr int MINB = DS ? 2 : 3; // (the base family's sums and inputs + the extra terms' registers)
+    static constexpr int NA = DS ? 11 : 8;  // Base's eight + gradrho x y z
+    static constexpr int NR = DS ? 16 : 12;
+    struct Params : Base::Params {
+        T nu4, eta;   // LaminarViscosity: 4 nu, eta
+        T lfac;       // LaminarViscosityDeltaSPH: 2 (dim + 2) nu rho0
+        T mfac;       // MomentumEquationDeltaSPH: alpha c0 rho0
+        T dfac;       // ContinuityEquationDeltaSPH: delta c0
+    };
+    struct Dest : Base::Dest { T g0, g1, g2, rho1; };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *s, const A &a, uint32_t o)
+    {
+        Base::load(D, s, a, o);
+        D.g0 = D.g1 = D.g2 = T(0.0);
+        if constexpr (DS) { D.g0 = s[8]; D.g1 = s[9]; D.g2 = s[10]; }
+        D.rho1 = fast_rcp(D.rho);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
+    {
+        Base::template pair<KK, UH>(D, pi, pj, r2, reinterpret_cast<const T (&)[8]>(s), fl, a, pass);
+        if (!(fl & (F_DCONT | F_DMOM | F_LAM | F_LAMD))) return;
+        PairGeomT<T> g;
+        pair_geom<KK, UH>(g, pi, pj, r2, a);
+        const T tg = pair_gradfac<KK, UH>(g); // DWIJ = tg XIJ (0 for r <= 1e-12)
+        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
+        const T vdotx = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
+        const T rhoj = s[4];
+        if (fl & F_LAM) { // tmp = mb 4 nu Fij / ((rhoa + rhob) (R2IJ + eta HIJ^2)),  Fij = DWIJ.XIJ
+            const T fij = tg * (g.xij[0] * g.xij[0] + g.xij[1] * g.xij[1] + g.xij[2] * g.xij[2]);
+            const T den = (D.rho + rhoj) * (r2 + a.p.eta * g.hij * g.hij);
+            const T tmp = pass ? s[3] * a.p.nu4 * fij * fast_rcp(den) : T(0.0);
+            D.au = fma(tmp, vij0, D.au);
+            D.av = fma(tmp, vij1, D.av);
+            D.aw = fma(tmp, vij2, D.aw);
+        }
+        if (fl & (F_DCONT | F_DMOM | F_LAMD)) {
+            const T re1 = fast_rcp(r2 + g.eps);
+            // Vj = mj / rhoj; a candidate outside the criterion adds exactly zero (a select, not a product: a parked
+            // padding row has rho = 0)
+            const T Vj = pass ? s[3] * fast_rcp(rhoj) : T(0.0);
+            if (fl & (F_DMOM | F_LAMD)) { // both are  f piij Vj / rhoi DWIJ  with piij = VIJ.XIJ / (R2IJ + EPS)
+                T f = T(0.0);
+                if (fl & F_DMOM) f = a.p.mfac * g.hij; // alpha HIJ c0 rho0
+                if (fl & F_LAMD) f += a.p.lfac;        // 2 (dim + 2) nu rho0
+                const T ft = f * (vdotx * re1) * Vj * D.rho1 * tg;
+                D.au = fma(ft, g.xij[0], D.au);
+                D.av = fma(ft, g.xij[1], D.av);
+                D.aw = fma(ft, g.xij[2], D.aw);
+            }
+            if constexpr (DS) {
+                if (fl & F_DCONT) {
+                    const T fac = T(-2.0) * (rhoj - D.rho) * re1;
+                    const T px = (fac * g.xij[0] - D.g0) - s[8];
+                    const T py = (fac * g.xij[1] - D.g1) - s[9];
+                    const T pz = (fac * g.xij[2] - D.g2) - s[10];
+                    const T psidot = tg * (px * g.xij[0] + py * g.xij[1] + pz * g.xij[2]);
+                    D.arho = fma(a.p.dfac * g.hij * psidot, Vj, D.arho);
+                }
+            }
+        }
+    }
+};
+
+// ---- delta-SPH pre-passes on [x y z h | m rho] records --------------------------------------------------------
+//   F_MOMENT   GradientCorrectionPreStep          wc/kernel_correction.py:46-74: m_mat[3i+j] = -sum V_b DWIJ[i] XIJ[j]
+//   F_GRADRHO  ContinuityEquationDeltaSPHPreStep  wc/basic.py:355-369: gradrho = sum (rho_b - rho_a) DWIJ V_b
+//   F_GCORR    GradientCorrection                 wc/kernel_correction.py:98-123, in front of it in the group: DWIJ
+//              becomes res = M^-1 DWIJ on the leading n x n block when |sum|res| - sum|DWIJ|| / (sum|DWIJ| + 1e-4 HIJ) < tol
+// The reference solves M res = DWIJ per pair with gj_solve (wc/linalg.py:94-166).  Its row search exchanges nothing
+// (after `bigrow = row` the exchange is of an element with itself), so it is elimination in the given row order, and
+// that does not depend on the right-hand side: load() factorises M once per destination (multipliers, the upper
+// triangle, reciprocal pivots), pair() applies the factors to DWIJ in gj_solve's own order.  gj_solve's ways out:
+//   * a pivot but the last below 1e-12 in magnitude: it returns with the result untouched (zero).  All factors are set
+//     to zero, which gives res = 0;
+//   * the last pivot exactly zero: with |rhs| > 1e-12 in that row the result stays zero; otherwise the row is left as
+//     it is (res_last = rhs_last, nothing eliminated above it): reciprocal 1, its column of the triangle 0, and the
+//     per-pair test of that rhs (`chk`).
+// res = 0 makes the change ~1 and DWIJ stays uncorrected (for tol <= 1), as in the reference.
+template <class T> struct FamDSPre_T {
+    typedef T Real;
+    static constexpr bool PRED = true;
+    static constexpr uint32_t CF0 = F_GRADRHO | F_GCORR;
+    static constexpr int MINB = 3;
+    static constexpr int NA = 2; // m rho
+    static constexpr int NR = 6;
+    struct Params {
+        int mdim;       // GradientCorrectionPreStep.dim
+        int n;          // GradientCorrection.dim
+        T tol;
+        double *mm[9];  // m_mat__0..8 of the destination: written by F_MOMENT, read by F_GCORR
+        double *gr[3];  // gradrho__0..2
+    };
+    struct Dest {
+        T rho;
+        T acc[9];                       // F_MOMENT: the nine sums; F_GRADRHO: acc[0..2]
+        T c10, c20, c21, u01, u02, u12; // elimination multipliers, upper triangle
+        T i0, i1, i2;                   // reciprocal pivots
+        bool chk;                       // last pivot exactly zero: the pair tests its right-hand side
+    };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *s, const A &a, uint32_t o)
+    {
+        D.rho = s[1];
+#pragma unroll
+        for (int k = 0; k < 9; k++) D.acc[k] = T(0.0);
+        D.c10 = D.c20 = D.c21 = D.u01 = D.u02 = D.u12 = D.i0 = D.i1 = D.i2 = T(0.0);
+        D.chk = false;
+        if (!(a.dflags & F_GCORR)) return;
+        const int n = a.p.n;
+        T M[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) M[i][j] = (i < n && j < n) ? (T)a.p.mm[3 * i + j][o] : T(i == j ? 1.0 : 0.0);
+        bool ok = true;
+        if (n > 1) { // column 0
+            const T d = M[0][0];
+            if (fabs(d) < T(1e-12)) ok = false;
+            else {
+                D.c10 = -M[1][0] / d;
+                M[1][1] += D.c10 * M[0][1]; M[1][2] += D.c10 * M[0][2];
+                if (n > 2) { D.c20 = -M[2][0] / d; M[2][1] += D.c20 * M[0][1]; M[2][2] += D.c20 * M[0][2]; }
+            }
+        }
+        if (ok && n > 2) { // column 1
+            const T d = M[1][1];
+            if (fabs(d) < T(1e-12)) ok = false;
+            else { D.c21 = -M[2][1] / d; M[2][2] += D.c21 * M[1][2]; }
+        }
+        if (!ok) { D.c10 = D.c20 = D.c21 = T(0.0); return; } // every factor zero: res = 0
+        D.u01 = M[0][1]; D.u02 = M[0][2]; D.u12 = M[1][2];
+        D.i0 = T(1.0) / M[0][0]; D.i1 = T(1.0) / M[1][1]; D.i2 = T(1.0) / M[2][2]; // (rows >= n: identity)
+        const T last = n == 3 ? M[2][2] : (n == 2 ? M[1][1] : M[0][0]);
+        if (last == T(0.0)) {
+            D.chk = true;
+            if (n == 3) { D.i2 = T(1.0); D.u02 = D.u12 = T(0.0); }
+            else if (n == 2) { D.i1 = T(1.0); D.u01 = T(0.0); }
+            else D.i0 = T(1.0);
+        }
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
+    {
+        PairGeomT<T> g;
+        pair_geom<KK, UH>(g, pi, pj, r2, a);
+        const T tg = pair_gradfac<KK, UH>(g);
+        T dw[3] = {tg * g.xij[0], tg * g.xij[1], tg * g.xij[2]};
+        const T Vj = pass ? s[0] * fast_rcp(s[1]) : T(0.0); // (a select: a parked padding row has rho = 0)
+        if (fl & F_MOMENT) {
+            const int md = a.p.mdim;
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int j = 0; j < 3; j++)
+                    if (i < md && j < md) D.acc[3 * i + j] = fma(-Vj * dw[i], g.xij[j], D.acc[3 * i + j]);
+        }
+        if (fl & F_GRADRHO) {
+            if (fl & F_GCORR) {
+                const int n = a.p.n;
+                // forward: rows 1, 2 += multiplier * row above, in gj_solve's order
+                T y0 = dw[0], y1 = dw[1], y2 = dw[2];
+                if (n > 1) y1 = fma(D.c10, y0, y1);
+                if (n > 2) { y2 = fma(D.c20, y0, y2); y2 = fma(D.c21, y1, y2); }
+                const T ylast = n == 3 ? y2 : (n == 2 ? y1 : y0);
+                // back substitution from the last row up
+                T x0, x1 = T(0.0), x2 = T(0.0);
+                if (n > 2) { x2 = y2 * D.i2; y1 = fma(-D.u12, x2, y1); y0 = fma(-D.u02, x2, y0); }
+                if (n > 1) { x1 = y1 * D.i1; y0 = fma(-D.u01, x1, y0); }
+                x0 = y0 * D.i0;
+                if (D.chk && fabs(ylast) > T(1e-12)) { x0 = x1 = x2 = T(0.0); }
+                T rmag = fabs(x0), dmag = fabs(dw[0]);
+                if (n > 1) { rmag += fabs(x1); dmag += fabs(dw[1]); }
+                if (n > 2) { rmag += fabs(x2); dmag += fabs(dw[2]); }
+                const T change = fabs(rmag - dmag) / (dmag + T(1.0e-4) * g.hij);
+                if (change < a.p.tol) {
+                    dw[0] = x0;
+                    if (n > 1) dw[1] = x1;
+                    if (n > 2) dw[2] = x2;
+                }
+            }
+            const T cf = (s[1] - D.rho) * Vj;
+            D.acc[0] = fma(cf, dw[0], D.acc[0]);
+            D.acc[1] = fma(cf, dw[1], D.acc[1]);
+            D.acc[2] = fma(cf, dw[2], D.acc[2]);
+        }
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        if (a.dflags & F_MOMENT) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) a.p.mm[k][o] = D.acc[k];
+        }
+        if (a.dflags & F_GRADRHO) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) a.p.gr[k][o] = D.acc[k];
+        }
+    }
+};
+
 // ---- density summations (basic_equations.py:19-29, transport_velocity.py:24-58)
 template <class T> struct FamDensity_T {
     typedef T Real; // arithmetic type of the pair loop
@@ -1349,7 +1570,7 @@ static bool is_nosrc_kind(int k)
 {
     return k == SPH_EQ_TAIT_EOS || k == SPH_EQ_TAIT_EOS_HG || k == SPH_EQ_TVF_STATE_EQUATION ||
            k == SPH_EQ_ISOTHERMAL_EOS || k == SPH_EQ_SOLID_ISOTHERMAL_EOS || k == SPH_EQ_MONAGHAN_ART_STRESS ||
-           k == SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE;
+           k == SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE || k == SPH_EQ_UPDATE_H_FERRARI;
 }
 
 static int need_prop(sph_ctx *c, int id, int prop, const char *who)
@@ -1368,7 +1589,9 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     EosArgs a;
     a.kind = e.kind;
     memcpy(a.par, e.par, sizeof a.par);
-    if (e.kind != SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE) { // (reads v_ij, s_ij and G only: alone in a group, rho and p are not on the device)
+    if (e.kind == SPH_EQ_UPDATE_H_FERRARI) { // reads m and rho, writes h
+        for (int p : {SPH_RHO, SPH_M, SPH_H}) SPH_TRY(need_prop(c, e.dest, p, "UpdateSmoothingLengthFerrari"));
+    } else if (e.kind != SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE) { // (reads v_ij, s_ij and G only: alone in a group, rho and p are not on the device)
         SPH_TRY(need_prop(c, e.dest, SPH_RHO, "EOS"));
         SPH_TRY(sph_array_ensure_prop(c, e.dest, SPH_P));
     }
@@ -1404,13 +1627,44 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     }
     ScopedTimer tm(c, T_EOS);
     hipLaunchKernelGGL(k_nosrc, dim3(div_up(stop - start, 256)), dim3(256), 0, c->stream, a);
+    if (e.kind == SPH_EQ_UPDATE_H_FERRARI) {
+        // h changed behind the neighbour grid: the next sph_nnps_update looks at the values again, and until then no
+        // pair loop may take "every particle has the h the last update saw" as a launch constant or a record layout
+        sph_mark_written(A, SPH_H);
+        c->uniform_h = false;
+    }
     return SPH_OK;
 }
 
-enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR };
+enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE };
 
-static int eq_family(int kind, uint32_t *flag, bool elastic)
+static bool is_wcsph_option_kind(int k)
 {
+    return k == SPH_EQ_CONTINUITY_DELTA_SPH || k == SPH_EQ_MOMENTUM_DELTA_SPH || k == SPH_EQ_LAMINAR_VISCOSITY ||
+           k == SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH;
+}
+
+// wcsphx: the destination carries a delta-SPH or laminar-viscosity term: its Continuity / Momentum / XSPH go with it
+static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false)
+{
+    switch (kind) {
+    case SPH_EQ_CONTINUITY_DELTA_SPH: *flag = F_DCONT; return FAM_WCSPHX;
+    case SPH_EQ_MOMENTUM_DELTA_SPH: *flag = F_DMOM; return FAM_WCSPHX;
+    case SPH_EQ_LAMINAR_VISCOSITY: *flag = F_LAM; return FAM_WCSPHX;
+    case SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH: *flag = F_LAMD; return FAM_WCSPHX;
+    case SPH_EQ_GRADIENT_CORRECTION_PRESTEP: *flag = F_MOMENT; return FAM_DSPRE;
+    case SPH_EQ_GRADIENT_CORRECTION: *flag = F_GCORR; return FAM_DSPRE;
+    case SPH_EQ_CONTINUITY_DELTA_SPH_PRESTEP: *flag = F_GRADRHO; return FAM_DSPRE;
+    default: break;
+    }
+    if (wcsphx && !elastic) {
+        switch (kind) {
+        case SPH_EQ_CONTINUITY: *flag = F_CONT; return FAM_WCSPHX;
+        case SPH_EQ_MOMENTUM: *flag = F_MOM; return FAM_WCSPHX;
+        case SPH_EQ_XSPH: *flag = F_XSPH; return FAM_WCSPHX;
+        default: break;
+        }
+    }
     if (elastic) {
         switch (kind) {
         case SPH_EQ_CONTINUITY: *flag = F_ECONT; return FAM_ELASTIC;
@@ -1454,6 +1708,16 @@ static PackPlan pack_plan(int fam)
         int pr[8] = {SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO, -1, SPH_CS, SPH_P};
         for (int k = 0; k < 8; k++) p.props[k] = pr[k];
         p.derived = 1;
+    } else if (fam == FAM_WCSPHX) { // the WCSPH slots; with a delta-SPH continuity term (sph_eval_group) + gradrho
+        p.nr = 12;
+        p.na = 8;
+        int pr[8] = {SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO, -1, SPH_CS, SPH_P};
+        for (int k = 0; k < 8; k++) p.props[k] = pr[k];
+        p.derived = 1;
+    } else if (fam == FAM_DSPRE) {
+        p.nr = 6;
+        p.na = 2;
+        p.props[0] = SPH_M; p.props[1] = SPH_RHO;
     } else if (fam == FAM_DENSITY) {
         p.nr = FamDensity::NR;
         p.na = 1;
@@ -1494,6 +1758,12 @@ static bool slot_required(int fam, uint32_t flags, int prop)
         if (prop == SPH_P || prop == SPH_CS) return flags & F_MOM;
         return false;
     }
+    if (fam == FAM_WCSPHX) {
+        if (prop == SPH_M || prop == SPH_U || prop == SPH_V || prop == SPH_W || prop == SPH_RHO) return true;
+        if (prop == SPH_P || prop == SPH_CS) return flags & F_MOM;
+        return flags & F_DCONT; // SPH_GRADRHO0..2
+    }
+    if (fam == FAM_DSPRE) return true;
     if (fam == FAM_DENSITY) return prop == SPH_M;
     if (fam == FAM_NBR) return false;
     if (fam == FAM_VGRAD) return true;
@@ -1574,7 +1844,7 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
             // it does not need a mass unless the equation uses the destination's own
             // (transport_velocity.SummationDensity: rho_i = m_i sum W)
             const bool mass_free = dest_only && pl.props[k] == SPH_M &&
-                                   (fam == FAM_WCSPH || (fam == FAM_DENSITY && !(flags & F_TVFSD)));
+                                   (fam == FAM_WCSPH || fam == FAM_WCSPHX || (fam == FAM_DENSITY && !(flags & F_TVFSD)));
             if (!pa.src[k] && !mass_free && slot_required(fam, flags, pl.props[k])) return need_prop(c, id, pl.props[k], "pair loop");
         }
     }
@@ -2136,12 +2406,16 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
                 (e.kind == SPH_EQ_MOMENTUM_WITH_STRESS || e.kind == SPH_EQ_MONAGHAN_ART_VISCOSITY))
                 elastic = true;
         }
+        bool wcsphx = false; // a delta-SPH / laminar-viscosity term on this destination: the WCSPH-options family
+        for (int i = 0; i < g->neq; i++) wcsphx |= g->eqs[i].dest == dst && g->eqs[i].nsrc > 0 && is_wcsph_option_kind(g->eqs[i].kind);
+        int eq_pos[32] = {};
         for (int i = 0; i < g->neq; i++) {
             const sph_equation &e = g->eqs[i];
             if (e.dest != dst || e.nsrc == 0) continue;
             if (e.kind < 0 || e.kind >= 32) { sph_set_error("bad equation kind %d", e.kind); return SPH_ERR_ARG; }
             uint32_t flag = 0;
-            int f = eq_family(e.kind, &flag, elastic);
+            int f = eq_family(e.kind, &flag, elastic, wcsphx);
+            eq_pos[e.kind] = i;
             if (f == FAM_NONE) { sph_set_error("equation kind %d has no hand-written pair kernel", e.kind); return SPH_ERR_UNSUPPORTED; }
             if (fam != FAM_NONE && f != fam) {
                 sph_set_error("group mixes equation families on destination %d (kinds are fused per family)", dst);
@@ -2170,7 +2444,27 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             dflags |= sflags[j];
             if (c->arr[srcs[j]].nnps_slot < 0) { sph_set_error("source array %d is not part of the neighbour grid", srcs[j]); return SPH_ERR_STATE; }
         }
-        if (fam == FAM_WCSPH && eq_of[SPH_EQ_MOMENTUM] && eq_of[SPH_EQ_MOMENTUM]->par[6] != 0.0) {
+        if (fam == FAM_WCSPHX) {
+            // the extra terms add into the sums of the Continuity / Momentum equations, whose finish() writes them
+            if ((dflags & F_DCONT) && !(dflags & F_CONT)) { sph_set_error("ContinuityEquationDeltaSPH needs a ContinuityEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+            if ((dflags & (F_DMOM | F_LAM | F_LAMD)) && !(dflags & F_MOM)) { sph_set_error("the delta-SPH / laminar viscosity terms need a MomentumEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+            if ((dflags & F_LAM) && (dflags & F_LAMD)) { sph_set_error("both LaminarViscosity and LaminarViscosityDeltaSPH on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        }
+        if (fam == FAM_DSPRE) {
+            // the moment matrix must be complete before a corrected gradient reads it: a group of its own, as in WCSPHScheme
+            if ((dflags & F_MOMENT) && (dflags & (F_GRADRHO | F_GCORR))) {
+                sph_set_error("GradientCorrectionPreStep shares a group with GradientCorrection / ContinuityEquationDeltaSPHPreStep on destination %d; put it in a group of its own before them", dst);
+                return SPH_ERR_UNSUPPORTED;
+            }
+            // GradientCorrection rewrites DWIJ for the equations AFTER it: behind the pre-step it corrects nothing
+            if ((dflags & F_GCORR) && (!(dflags & F_GRADRHO) || eq_pos[SPH_EQ_GRADIENT_CORRECTION] > eq_pos[SPH_EQ_CONTINUITY_DELTA_SPH_PRESTEP])) {
+                dflags &= ~(uint32_t)F_GCORR;
+                for (int j = 0; j < nsrcs; j++) sflags[j] &= ~(uint32_t)F_GCORR;
+            }
+            if (!dflags) continue;
+            for (int j = 0; j < nsrcs; j++) if ((sflags[j] & F_GCORR) && !(sflags[j] & F_GRADRHO)) sflags[j] &= ~(uint32_t)F_GCORR;
+        }
+        if ((fam == FAM_WCSPH || fam == FAM_WCSPHX) && eq_of[SPH_EQ_MOMENTUM] && eq_of[SPH_EQ_MOMENTUM]->par[6] != 0.0) {
             dflags |= F_TENSILE;
             for (int j = 0; j < nsrcs; j++) if (sflags[j] & F_MOM) sflags[j] |= F_TENSILE;
         }
@@ -2213,6 +2507,11 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             // a destination-only array is read through its own records only: its ghosts are no destinations
         }
         PackPlan pl = pack_plan(fam);
+        const bool wx_ds = fam == FAM_WCSPHX && (dflags & F_DCONT); // the records carry the sources' gradrho
+        if (wx_ds) {
+            for (int k = 0; k < 3; k++) pl.props[8 + k] = SPH_GRADRHO0 + k;
+            pl.na = 11; pl.nr = 16;
+        }
         // compact 80-B WCSPH records when neither h nor p of a neighbour is read
         if (c->pair_variant >= 3 && fam == FAM_WCSPH && c->uniform_h && c->use_uniform_h && !(dflags & F_TENSILE)) pl.nr = c->wcsph_nr ? (int)c->wcsph_nr : 10;
         if (c->pair_variant >= 3 && fam == FAM_DENSITY && c->uniform_h && c->use_uniform_h) pl.nr = 4;
@@ -2389,6 +2688,64 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             else if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(c, K->kind, a);
             else return launch_pair<F>(c, K->kind, a);
         };
+        // the WCSPH-options family: FamWCSPH_T's arguments + the parameters of the extra terms
+        auto run_wcsphx = [&](auto tag) -> int {
+            typedef decltype(tag) F;
+            PairArgs<F> a;
+            memset(&a, 0, sizeof a);
+            common(a);
+            const sph_equation *me = eq_of[SPH_EQ_MOMENTUM], *xe = eq_of[SPH_EQ_XSPH];
+            const sph_equation *dc = eq_of[SPH_EQ_CONTINUITY_DELTA_SPH], *dm = eq_of[SPH_EQ_MOMENTUM_DELTA_SPH],
+                               *lv = eq_of[SPH_EQ_LAMINAR_VISCOSITY], *ld = eq_of[SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH];
+            if (me) { a.p.c0 = me->par[0]; a.p.alpha = me->par[1]; a.p.beta = me->par[2]; a.p.gx = me->par[3]; a.p.gy = me->par[4]; a.p.gz = me->par[5]; }
+            if (xe) a.p.eps = xe->par[0];
+            if (dc) a.p.dfac = dc->par[1] * dc->par[0];                  // par c0 delta
+            if (dm) a.p.mfac = dm->par[2] * dm->par[1] * dm->par[0];     // par rho0 c0 alpha
+            if (lv) { a.p.nu4 = 4.0 * lv->par[0]; a.p.eta = lv->par[1]; } // par nu eta
+            if (ld) a.p.lfac = 2.0 * (ld->par[0] + 2.0) * ld->par[2] * ld->par[1]; // par dim rho0 nu
+            if (dflags & F_CONT) { SPH_TRY(ensure_out(c, dst, {SPH_ARHO})); a.p.arho = D.prop[SPH_ARHO]; }
+            if (dflags & F_MOM) {
+                SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW, SPH_DT_CFL, SPH_DT_FORCE}));
+                a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
+                a.p.dt_cfl = D.prop[SPH_DT_CFL]; a.p.dt_force = D.prop[SPH_DT_FORCE];
+            }
+            if (dflags & F_XSPH) {
+                SPH_TRY(ensure_out(c, dst, {SPH_AX, SPH_AY, SPH_AZ}));
+                a.p.ax = D.prop[SPH_AX]; a.p.ay = D.prop[SPH_AY]; a.p.az = D.prop[SPH_AZ];
+            }
+            return launch_pair<F>(c, K->kind, a);
+        };
+        // the delta-SPH pre-passes: the moment matrix, or the (renormalised) density gradient
+        auto run_dspre = [&](auto tag) -> int {
+            typedef decltype(tag) F;
+            PairArgs<F> a;
+            memset(&a, 0, sizeof a);
+            common(a);
+            const sph_equation *pe = eq_of[SPH_EQ_GRADIENT_CORRECTION_PRESTEP], *ge = eq_of[SPH_EQ_GRADIENT_CORRECTION];
+            a.p.mdim = pe ? (int)pe->par[0] : 0;
+            a.p.n = 0;
+            if (dflags & F_GCORR) { a.p.n = (int)ge->par[0]; a.p.tol = ge->par[1]; }
+            if (a.p.mdim < 0 || a.p.mdim > 3 || ((dflags & F_GCORR) && (a.p.n < 1 || a.p.n > 3))) {
+                sph_set_error("GradientCorrection / GradientCorrectionPreStep: dim must be 1, 2 or 3");
+                return SPH_ERR_ARG;
+            }
+            if (dflags & (F_MOMENT | F_GCORR)) {
+                for (int k = 0; k < 9; k++) {
+                    const int pid = SPH_MMAT0 + k;
+                    if (dflags & F_MOMENT) SPH_TRY(sph_array_ensure_prop(c, dst, pid));
+                    else if (!D.prop[pid]) return need_prop(c, dst, pid, "GradientCorrection (m_mat)");
+                    a.p.mm[k] = D.prop[pid];
+                }
+            }
+            if (dflags & F_GRADRHO) {
+                for (int k = 0; k < 3; k++) {
+                    const int pid = SPH_GRADRHO0 + k;
+                    SPH_TRY(sph_array_ensure_prop(c, dst, pid));
+                    a.p.gr[k] = D.prop[pid];
+                }
+            }
+            return launch_pair<F>(c, K->kind, a);
+        };
         auto run_density = [&](auto tag) -> int {
             typedef decltype(tag) F;
             PairArgs<F> a;
@@ -2468,6 +2825,9 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         else if (fam == FAM_WCSPH && eosf) SPH_TRY(f32 ? run_wcsph(FamWCSPHEG_T<float>()) : run_wcsph(FamWCSPHEG_T<double>()));
         else if (fam == FAM_WCSPH && eosv) SPH_TRY(f32 ? run_wcsph(FamWCSPHV_T<float>()) : run_wcsph(FamWCSPHV_T<double>()));
         else if (fam == FAM_WCSPH) SPH_TRY(f32 ? run_wcsph(FamWCSPH_T<float>()) : run_wcsph(FamWCSPH()));
+        else if (fam == FAM_WCSPHX && wx_ds) SPH_TRY(f32 ? run_wcsphx(FamWCSPHX_T<float, true>()) : run_wcsphx(FamWCSPHX_T<double, true>()));
+        else if (fam == FAM_WCSPHX) SPH_TRY(f32 ? run_wcsphx(FamWCSPHX_T<float, false>()) : run_wcsphx(FamWCSPHX_T<double, false>()));
+        else if (fam == FAM_DSPRE) SPH_TRY(f32 ? run_dspre(FamDSPre_T<float>()) : run_dspre(FamDSPre_T<double>()));
         else if (fam == FAM_DENSITY) SPH_TRY(f32 ? run_density(FamDensity_T<float>()) : run_density(FamDensity()));
         else if (fam == FAM_VGRAD) SPH_TRY(f32 ? run_vgrad(FamVGrad_T<float>()) : run_vgrad(FamVGrad()));
         else if (fam == FAM_ELASTIC && elu) SPH_TRY(f32 ? run_elastic(FamElasticU_T<float>()) : run_elastic(FamElasticU_T<double>()));
@@ -2835,6 +3195,10 @@ UNIT_BOTH(UNIT_PAIR, FamDensity_T);
 UNIT_BOTH(UNIT_PAIR, FamTVF_T);
 UNIT_BOTH(UNIT_PAIR, FamVGrad_T);
 UNIT_BOTH(UNIT_PAIR, FamElastic_T);
+UNIT_BOTH(UNIT_PAIR, FamDSPre_T);
+typedef FamWCSPHX_T<double, false> UnitX_d; typedef FamWCSPHX_T<double, true> UnitXD_d;
+typedef FamWCSPHX_T<float, false> UnitX_f; typedef FamWCSPHX_T<float, true> UnitXD_f;
+UNIT_PAIR(UnitX_d); UNIT_PAIR(UnitXD_d); UNIT_PAIR(UnitX_f); UNIT_PAIR(UnitXD_f);
 #define UNIT_FUSED_UH(F) UNIT_FUSED(F, true)
 #define UNIT_FUSED_VH(F) UNIT_FUSED(F, false)
 typedef FamWCSPHE_T<double, false> UnitE_d; typedef FamWCSPHE_T<double, true> UnitEU_d;

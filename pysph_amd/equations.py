@@ -150,6 +150,80 @@ class MonaghanArtificialViscosity(Equation):
 
 
 # --------------------------------------------------------------------------
+# WCSPHScheme options: delta-SPH, laminar viscosity, update_h
+# (pysph/sph/wc/kernel_correction.py, wc/basic.py, wc/viscosity.py)
+# --------------------------------------------------------------------------
+class GradientCorrectionPreStep(Equation):
+    """wc/kernel_correction.py:40-74 (a ``loop_all`` there: the plain
+    neighbour sum of the moment matrix ``m_mat``)."""
+
+    def __init__(self, dest, sources, dim=2):
+        self.dim = dim
+        super(GradientCorrectionPreStep, self).__init__(dest, sources)
+
+
+class GradientCorrection(Equation):
+    """wc/kernel_correction.py:77-123: rewrites DWIJ for the equations after
+    it in its group."""
+
+    def __init__(self, dest, sources, dim=2, tol=0.1):
+        self.dim = dim
+        self.tol = tol
+        super(GradientCorrection, self).__init__(dest, sources)
+
+
+class ContinuityEquationDeltaSPHPreStep(Equation):
+    """wc/basic.py:346-369."""
+
+
+class ContinuityEquationDeltaSPH(Equation):
+    """wc/basic.py:372-414."""
+
+    def __init__(self, dest, sources, c0, delta=0.1):
+        self.c0 = c0
+        self.delta = delta
+        super(ContinuityEquationDeltaSPH, self).__init__(dest, sources)
+
+
+class MomentumEquationDeltaSPH(Equation):
+    """wc/basic.py:272-343."""
+
+    def __init__(self, dest, sources, rho0, c0, alpha=1.0):
+        self.alpha = alpha
+        self.c0 = c0
+        self.rho0 = rho0
+        super(MomentumEquationDeltaSPH, self).__init__(dest, sources)
+
+
+class LaminarViscosity(Equation):
+    """wc/viscosity.py:6-27."""
+
+    def __init__(self, dest, sources, nu, eta=0.01):
+        self.nu = nu
+        self.eta = eta
+        super(LaminarViscosity, self).__init__(dest, sources)
+
+
+class LaminarViscosityDeltaSPH(Equation):
+    """wc/viscosity.py:116-144."""
+
+    def __init__(self, dest, sources, dim, rho0, nu):
+        self.dim = dim
+        self.rho0 = rho0
+        self.nu = nu
+        super(LaminarViscosityDeltaSPH, self).__init__(dest, sources)
+
+
+class UpdateSmoothingLengthFerrari(Equation):
+    """wc/basic.py:417-462."""
+
+    def __init__(self, dest, sources, dim, hdx):
+        self.dim1 = 1. / dim
+        self.hdx = hdx
+        super(UpdateSmoothingLengthFerrari, self).__init__(dest, sources)
+
+
+# --------------------------------------------------------------------------
 # Transport-velocity formulation (pysph/sph/wc/transport_velocity.py)
 # --------------------------------------------------------------------------
 class TVFSummationDensity(Equation):
@@ -222,6 +296,14 @@ EQ_TVF_MOM_ART_VISCOSITY = 11
 EQ_TVF_MOM_ART_STRESS = 12
 EQ_ISOTHERMAL_EOS = 13
 EQ_MONAGHAN_ART_VISCOSITY = 14
+EQ_GRADIENT_CORRECTION_PRESTEP = 22
+EQ_GRADIENT_CORRECTION = 23
+EQ_CONTINUITY_DELTA_SPH_PRESTEP = 24
+EQ_CONTINUITY_DELTA_SPH = 25
+EQ_MOMENTUM_DELTA_SPH = 26
+EQ_LAMINAR_VISCOSITY = 27
+EQ_LAMINAR_VISCOSITY_DELTA_SPH = 28
+EQ_UPDATE_H_FERRARI = 29
 
 _XV = ('x', 'y', 'z', 'h')
 EQUATION_TABLE = OrderedDict([
@@ -272,11 +354,38 @@ EQUATION_TABLE = OrderedDict([
         EQ_MONAGHAN_ART_VISCOSITY, ('alpha', 'beta'),
         _XV + ('u', 'v', 'w', 'rho', 'cs', 'au', 'av', 'aw'),
         _XV + ('u', 'v', 'w', 'rho', 'cs', 'm'))),
+    # the strided m_mat (9) and gradrho (3) are the component columns m_mat__0.. / gradrho__0.. on the device
+    ('GradientCorrectionPreStep', (
+        EQ_GRADIENT_CORRECTION_PRESTEP, ('dim',),
+        _XV + ('m_mat',), _XV + ('m', 'rho'))),
+    ('GradientCorrection', (
+        EQ_GRADIENT_CORRECTION, ('dim', 'tol'),
+        _XV + ('m_mat',), _XV)),
+    ('ContinuityEquationDeltaSPHPreStep', (
+        EQ_CONTINUITY_DELTA_SPH_PRESTEP, (),
+        _XV + ('rho', 'gradrho'), _XV + ('m', 'rho'))),
+    ('ContinuityEquationDeltaSPH', (
+        EQ_CONTINUITY_DELTA_SPH, ('c0', 'delta'),
+        _XV + ('rho', 'arho', 'gradrho'), _XV + ('m', 'rho', 'gradrho'))),
+    ('MomentumEquationDeltaSPH', (
+        EQ_MOMENTUM_DELTA_SPH, ('rho0', 'c0', 'alpha'),
+        _XV + ('u', 'v', 'w', 'rho', 'au', 'av', 'aw'),
+        _XV + ('u', 'v', 'w', 'rho', 'm'))),
+    ('LaminarViscosity', (
+        EQ_LAMINAR_VISCOSITY, ('nu', 'eta'),
+        _XV + ('u', 'v', 'w', 'rho', 'au', 'av', 'aw'),
+        _XV + ('u', 'v', 'w', 'rho', 'm'))),
+    ('LaminarViscosityDeltaSPH', (
+        EQ_LAMINAR_VISCOSITY_DELTA_SPH, ('dim', 'rho0', 'nu'),
+        _XV + ('u', 'v', 'w', 'rho', 'au', 'av', 'aw'),
+        _XV + ('u', 'v', 'w', 'rho', 'm'))),
+    ('UpdateSmoothingLengthFerrari', (
+        EQ_UPDATE_H_FERRARI, ('dim1', 'hdx'), ('h', 'm', 'rho'), ())),   # dim1 = 1 / dim
 ])
 
 # equations that have no neighbour loop
 NO_SOURCE_KINDS = (EQ_TAIT_EOS, EQ_TAIT_EOS_HG, EQ_TVF_STATE_EQUATION,
-                   EQ_ISOTHERMAL_EOS, 17, 19, 21)
+                   EQ_ISOTHERMAL_EOS, 17, 19, 21, EQ_UPDATE_H_FERRARI)
 
 
 def resolve_equation(eq):

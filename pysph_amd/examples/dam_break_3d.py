@@ -75,12 +75,14 @@ class DamBreak3DGeometry(object):
         return out
 
 
-def create_scheme(dx=0.02, hdx=hdx):
-    """dam_break_3d.py:54-60."""
+def create_scheme(dx=0.02, hdx=hdx, delta_sph=False, nu=0.0, update_h=False):
+    """dam_break_3d.py:54-60; delta_sph / nu / update_h: the options of the
+    reference's WCSPHScheme (its command line's --delta-sph, --update-h)."""
     return WCSPHScheme(['fluid'], ['boundary', 'obstacle'], dim=dim, rho0=ro,
                        c0=c0, h0=dx * hdx, hdx=hdx, gz=-9.81, alpha=alpha,
                        beta=beta, gamma=gamma, hg_correction=True,
-                       tensile_correction=False)
+                       tensile_correction=False, delta_sph=delta_sph, nu=nu,
+                       update_h=update_h)
 
 
 def create_kernel():

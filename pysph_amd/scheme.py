@@ -3,14 +3,23 @@
 Mirrors the *output* (group list, order, flags, parameters) of the
 reference's ``WCSPHScheme.get_equations`` (pysph/sph/scheme.py:388-506) and
 ``TVFScheme.get_equations`` (:616-687) for the options the BASELINE configs
-use.  Options that select equations without a hand-written kernel
-(delta-SPH, laminar viscosity, update_h, TVF solid walls) raise instead of
-silently dropping terms.  With the reference installed, its own ``Scheme``
-objects can be used instead: the backend consumes the resulting group list.
+use.  ``WCSPHScheme`` takes every combination of the reference's options:
+``delta_sph`` (moment matrix, renormalised density gradient, the delta-SPH
+continuity and momentum terms), ``nu`` (LaminarViscosity, or
+LaminarViscosityDeltaSPH under delta-SPH) and ``update_h``
+(UpdateSmoothingLengthFerrari) all select hand-written kernels; ``delta_sph``
+is ignored under ``summation_density`` as in the reference.  The TVF solid
+walls run through the generated-family path.  With the reference installed,
+its own ``Scheme`` objects can be used instead: the backend consumes the
+resulting group list.
 """
 from .equations import (
     Group, TaitEOS, TaitEOSHGCorrection, ContinuityEquation, MomentumEquation,
     XSPHCorrection, SummationDensity, TVFSummationDensity, StateEquation,
+    GradientCorrectionPreStep, GradientCorrection,
+    ContinuityEquationDeltaSPHPreStep, ContinuityEquationDeltaSPH,
+    MomentumEquationDeltaSPH, LaminarViscosity, LaminarViscosityDeltaSPH,
+    UpdateSmoothingLengthFerrari,
     MomentumEquationPressureGradient, MomentumEquationViscosity,
     MomentumEquationArtificialViscosity, MomentumEquationArtificialStress)
 from .particle_array import WCSPH_PROPS, TVF_FLUID_PROPS
@@ -28,10 +37,6 @@ class WCSPHScheme(object):
                  gx=0.0, gy=0.0, gz=0.0, alpha=0.1, beta=0.0, delta=0.1,
                  nu=0.0, tensile_correction=False, hg_correction=False,
                  update_h=False, delta_sph=False, summation_density=False):
-        if delta_sph or update_h or abs(nu) > 1e-14:
-            raise NotImplementedError(
-                'HIP backend: delta_sph / update_h / nu!=0 select equations '
-                'that have no hand-written kernel yet')
         self.fluids = list(fluids)
         self.solids = list(solids)
         self.dim = dim
@@ -43,6 +48,10 @@ class WCSPHScheme(object):
         self.gx, self.gy, self.gz = gx, gy, gz
         self.alpha = alpha
         self.beta = beta
+        self.delta = delta
+        self.nu = nu
+        self.update_h = update_h
+        self.delta_sph = delta_sph
         self.tensile_correction = tensile_correction
         self.hg_correction = hg_correction
         self.summation_density = summation_density
@@ -64,21 +73,64 @@ class WCSPHScheme(object):
                           gamma=self.gamma) for s in self.solids]
         groups.append(Group(equations=eos, real=False))
 
+        # delta-SPH: the moment matrix over ALL particles, then the renormalised
+        # density gradient (scheme.py:434-450; GradientCorrection keeps its
+        # default dim = 2 and tol = 0.1 there)
+        delta_sph = self.delta_sph and not self.summation_density
+        if delta_sph:
+            groups.append(Group(real=False, equations=[
+                GradientCorrectionPreStep(dest=f, sources=[f], dim=self.dim)
+                for f in self.fluids]))
+            pre = []
+            for f in self.fluids:
+                pre.extend([GradientCorrection(dest=f, sources=[f]),
+                            ContinuityEquationDeltaSPHPreStep(dest=f, sources=[f])])
+            groups.append(Group(equations=pre))
+
         rates = [ContinuityEquation(dest=s, sources=self.fluids)
                  for s in self.solids]
         for f in self.fluids:
             if not self.summation_density:
                 rates.append(ContinuityEquation(dest=f, sources=everyone))
+            if delta_sph:
+                rates.append(ContinuityEquationDeltaSPH(
+                    dest=f, sources=[f], c0=self.c0, delta=self.delta))
+            # MomentumEquation's artificial viscosity is switched off under
+            # delta-SPH, whose own momentum term carries alpha (scheme.py:467-482)
+            alpha = 0.0 if self.delta_sph else self.alpha
             rates.append(MomentumEquation(
-                dest=f, sources=everyone, c0=self.c0, alpha=self.alpha,
+                dest=f, sources=everyone, c0=self.c0, alpha=alpha,
                 beta=self.beta, gx=self.gx, gy=self.gy, gz=self.gz,
                 tensile_correction=self.tensile_correction))
+            if self.delta_sph:
+                rates.append(MomentumEquationDeltaSPH(
+                    dest=f, sources=[f], rho0=self.rho0, c0=self.c0,
+                    alpha=self.alpha))
             rates.append(XSPHCorrection(dest=f, sources=[f]))
+            if abs(self.nu) > 1e-14:
+                if self.delta_sph:
+                    eq = LaminarViscosityDeltaSPH(
+                        dest=f, sources=everyone, dim=self.dim, rho0=self.rho0,
+                        nu=self.nu)
+                else:
+                    eq = LaminarViscosity(dest=f, sources=everyone, nu=self.nu)
+                rates.insert(-1, eq)    # before the XSPH correction (scheme.py:495)
         groups.append(Group(equations=rates))
+
+        if self.update_h:
+            groups.append(Group(real=False, equations=[
+                UpdateSmoothingLengthFerrari(dest=f, sources=None, dim=self.dim,
+                                             hdx=self.hdx)
+                for f in self.fluids]))
         return groups
 
     def setup_properties(self, particles, clean=True):
         _ensure_props(particles, WCSPH_PROPS)
+        if self.delta_sph:          # scheme.py:514-519
+            for pa in particles:
+                for name, stride in (('m_mat', 9), ('gradrho', 3)):
+                    if name not in pa.properties:
+                        pa.add_property(name, stride=stride)
 
 
 class TVFScheme(object):
