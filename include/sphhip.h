@@ -118,7 +118,14 @@ enum sph_eq_kind {
     SPH_EQ_MOMENTUM_DELTA_SPH = 26,           /* wc/basic.py:272   par: rho0 c0 alpha   (with id 4) */
     SPH_EQ_LAMINAR_VISCOSITY = 27,            /* wc/viscosity.py:6     par: nu eta   (with id 4) */
     SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH = 28,  /* wc/viscosity.py:116   par: dim rho0 nu   (with id 4) */
-    SPH_EQ_UPDATE_H_FERRARI = 29              /* wc/basic.py:417   par: dim1 (= 1 / dim) hdx   (no sources; writes h) */
+    SPH_EQ_UPDATE_H_FERRARI = 29,             /* wc/basic.py:417   par: dim1 (= 1 / dim) hdx   (no sources; writes h) */
+    /* EDAC (pysph/sph/wc/edac.py).  ap, pavg and nnbr are user properties (sph_prop_register) of those names.  Ids 31-33
+     * share one force family with ids 10, 11, 12 (viscosity, artificial viscosity, artificial stress) and id 5 (XSPH)
+     * on the same destination.                                                                                      */
+    SPH_EQ_EDAC_AVG_PRESSURE = 30,            /* wc/edac.py:62-79     (writes pavg, nnbr; alone or with id 7 on a destination) */
+    SPH_EQ_EDAC_MOMENTUM = 31,                /* wc/edac.py:301-351   par: c0 gx gy gz tdamp */
+    SPH_EQ_EDAC_MOM_PRESSURE = 32,            /* wc/edac.py:389-488   par: pb gx gy gz tdamp   (reads pavg of the destination) */
+    SPH_EQ_EDAC = 33                          /* wc/edac.py:354-386   par: cs nu rho0   (writes ap) */
 };
 
 /* One Equation(dest, sources) instance: pysph/sph/equation.py:392-420. */
@@ -655,7 +662,9 @@ enum sph_stepper {
     SPH_STEP_TVF = 2,   /* TransportVelocityStep integrator_step.py:257-299 */
     SPH_STEP_SOLID_MECH = 3, /* SolidMechStep       integrator_step.py:173-255 */
     SPH_STEP_RIGID_RK2 = 4,  /* RK2StepRigidBody    pysph/sph/rigid_body.py:718-770 (needs sph_rigid_setup) */
-    SPH_STEP_RIGID_EULER = 5 /* EulerStepRigidBody  pysph/sph/rigid_body.py:695-715 (stage 1 only)          */
+    SPH_STEP_RIGID_EULER = 5,/* EulerStepRigidBody  pysph/sph/rigid_body.py:695-715 (stage 1 only)          */
+    SPH_STEP_EDAC = 6,       /* EDACStep            pysph/sph/wc/edac.py:95-133  (p0, ap: user properties)  */
+    SPH_STEP_EDAC_TVF = 7    /* EDACTVFStep         pysph/sph/wc/edac.py:493-540                            */
 };
 int sph_integrate_stage(sph_ctx *ctx, int array_id, int stepper, int stage, double dt);
 /* min over the first n_real particles of a property (h_minimum,
@@ -795,7 +804,8 @@ int sph_timer_reset(sph_ctx *ctx);
  * equation family: "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad",
  * "pair_elastic", "pair_wcsph_options" (the rates of a WCSPH destination with
  * delta-SPH or laminar-viscosity terms), "pair_delta_sph_pre" (moment matrix and
- * renormalised density gradient); out: total ms and launches.  Launch counters (ms = 0, counted
+ * renormalised density gradient), "pair_edac" (the EDAC force group), "pair_avg_pressure"
+ * (ComputeAveragePressure, alone or with a density summation); out: total ms and launches.  Launch counters (ms = 0, counted
  * whether or not timing is enabled): "n_eos_fused" (pair launches on the 64-byte
  * EOS-fused records), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group
  * evaluations run as one launch over the merged order), "n_tension_flag" (elastic rate launches that read the tension word), "n_phase2" (pair launches of the second half of a

@@ -272,10 +272,13 @@ class _BuiltinUnit(object):
         self.ceqs = (dev.SphEquation * max(len(eqs), 1))()
         self._const_params = []
         self.delta_sph_arrays = set()     # arrays whose m_mat / gradrho this unit reads or writes
+        self.edac_arrays = set()          # arrays an EDAC equation reads or writes
         for i, eq in enumerate(eqs):
             kind, vals, dprops, sprops = resolve_equation(eq)
             if kind in _DELTA_SPH_KINDS:
                 self.delta_sph_arrays.update([eq.dest] + list(eq.sources or []))
+            if kind in _EDAC_KINDS:
+                self.edac_arrays.update([eq.dest] + list(eq.sources or []))
             dprops = _columns(arrays[eq.dest], dprops)
             if kind == _UPDATE_H_KIND:
                 owner.outputs_exact[eq.dest].add('h')      # (the tables' 'h' is an input everywhere else)
@@ -327,6 +330,12 @@ class _BuiltinUnit(object):
     def _check(self, ev):
         """m_mat and gradrho are computed per evaluation for the rows a rank holds; ghost rows (a slab's Remote
         particles, periodic or mirror images) would need gradrho carried to them between the passes"""
+        for name in sorted(self.edac_arrays):
+            if getattr(self._arrays[name], 'slab_decomposed', False):
+                raise NotImplementedError(
+                    "EDAC equations on array '%s': not supported on a slab-decomposed array -- the pressure p is "
+                    "integrated state here, not a function of the density, and the halo messages carry no p / V / "
+                    "uhat set for it; stale values are not computed with" % name)
         for name in sorted(self.delta_sph_arrays):
             pa = self._arrays[name]
             owner = getattr(ev.helpers[name], 'ghost_owner', None)
@@ -338,7 +347,7 @@ class _BuiltinUnit(object):
                     % (name, ' (ghosts managed by %s)' % owner if owner else ''))
 
     def run(self, ev, t, dt, phase=0):
-        if self.delta_sph_arrays:
+        if self.delta_sph_arrays or self.edac_arrays:
             self._check(ev)
         self.cg.phase = phase
         try:
@@ -572,7 +581,7 @@ class _CGroup(object):
                 u.run(ev, t, dt)
             return
         for u in self.units:
-            if u.delta_sph_arrays:
+            if u.delta_sph_arrays or u.edac_arrays:
                 u._check(ev)
         if getattr(self, '_combined', None) is None:
             self._combined = self._combined_group()
@@ -594,6 +603,7 @@ class _CGroup(object):
             ev.ctx._h, C.byref(ev.ckernel), C.byref(cg), t, dt))
 
 
+_EDAC_KINDS = (30, 31, 32, 33)        # average pressure, the two pressure gradients, the pressure rate
 _DELTA_SPH_KINDS = (22, 23, 24, 25)   # moment matrix, gradient correction, gradrho pre-step, delta-SPH continuity
 _UPDATE_H_KIND = 29             # SPH_EQ_UPDATE_H_FERRARI
 _TAIT_KINDS = (1, 2)            # SPH_EQ_TAIT_EOS, SPH_EQ_TAIT_EOS_HG
@@ -813,6 +823,11 @@ class HipAccelerationEval(object):
     def compute(self, t, dt):
         if self.nnps is None:
             raise RuntimeError('HipAccelerationEval.compute: call set_nnps first')
+        # what no unit of the evaluation may run with is refused before the first launch of any of them
+        for cg in self._leaves(self.plan):
+            for u in cg.units:
+                if getattr(u, 'edac_arrays', None):
+                    u._check(self)
         if self.sync == 'auto':
             self.push_inputs()
         for entry in self.plan:

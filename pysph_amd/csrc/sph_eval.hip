@@ -1319,6 +1319,189 @@ template <class T> struct FamTVFE_T : FamTVF_T<T> {
     }
 };
 
+// ---- EDAC force group (pysph/sph/wc/edac.py:301-488 with transport_velocity.py:328-545 and basic_equations.py:260-300)
+//      Everything EDACScheme puts on a fluid destination in its force group, in ONE sweep: the pressure gradient
+//      (external form :320-343, or the internal one :443-478 with pb, the transport accelerations and the
+//      destination's pavg taken off both pressures), the artificial and the physical viscosity, the artificial stress
+//      (internal branch), the pressure rate ap (:365-386: a continuity-like term with cs^2 and a damping term with
+//      its OWN viscosity edac_nu) and the XSPH correction (external branch; it reads the fluid only, which the
+//      per-source flags express).  INT = the internal branch: the two branches are two instantiations, each with its
+//      scheme's default flag set as a compile-time constant and without the other branch's terms and accumulators.
+//      Records: the generic [x y z h | u v w uhat vhat what rho p V m Vj2 -] of FamTVF_T; under uniform h k_pack's
+//      compact layout 3 in its seven-piece form, which carries m (load_record_edac below).  p is integrated state
+//      here, not a function of rho, so the records that leave p and V out (FamTVFE_T) do not apply.
+enum { F_EP = 1, /* F_TVISC = 2, F_TAV = 4, F_TAS = 8 as in FamTVF_T */ F_EINT = 16, F_EDAC = 32, F_EXS = 64 };
+template <class T, bool INT> struct FamEDAC_T {
+    typedef T Real;
+    static constexpr bool PRED = true; // every term carries DWIJ or WIJ, both zero for a pair outside the criterion
+    static constexpr uint32_t CF0 = INT ? (F_EP | F_EINT | F_TVISC | F_TAS | F_EDAC) : (F_EP | F_TVISC | F_EDAC | F_EXS);
+    static constexpr uint32_t MASK = INT ? ~(uint32_t)F_EXS : ~(uint32_t)(F_TAS | F_EINT);
+    static constexpr int MINB = 4;
+    static constexpr int NA = 12; // u v w uhat vhat what rho p V m Vj2 pad
+    static constexpr int NR = 16;
+    struct Params {
+        T pb, gx, gy, gz, tdamp, nu, c0, alpha, cs2, enu, eps;
+        const double *m, *pavg; // the destination's own mass and average pressure
+        double *au, *av, *aw, *auhat, *avhat, *awhat, *ap, *ax, *ay, *az;
+    };
+    struct Dest {
+        T u, v, w, uh, vh, wh, rho, p, pavg, Vi2, mi1;
+        T au, av, aw, auh, avh, awh, ap, ax, ay, az;
+    };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &A_, uint32_t o)
+    {
+        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.uh = a[3]; D.vh = a[4]; D.wh = a[5];
+        D.rho = a[6]; D.p = a[7]; D.Vi2 = a[10]; D.mi1 = T(1.0) / T(A_.p.m[o]);
+        D.pavg = T(0.0); // the destination's, taken off both pressures (edac.py:450-454)
+        if (INT && (A_.dflags & F_EP)) D.pavg = T(A_.p.pavg[o]);
+        D.uh = INT ? D.uh : T(0.0); D.vh = INT ? D.vh : T(0.0); D.wh = INT ? D.wh : T(0.0);
+        D.au = D.av = D.aw = D.auh = D.avh = D.awh = D.ap = D.ax = D.ay = D.az = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t fl_, const A &a, bool pass = true)
+    {
+        const uint32_t fl = fl_ & MASK;
+        PairGeomT<T> g;
+        pair_geom<KK, UH>(g, pi, pj, r2, a);
+        T tg = pair_gradfac<KK, UH>(g);
+        tg = pass ? tg : T(0.0);
+        const T dw0 = tg * g.xij[0], dw1 = tg * g.xij[1], dw2 = tg * g.xij[2];
+        const T rhoj = s[6], Vj2 = s[10];
+        const T vsum = D.Vi2 + Vj2;
+        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
+        const T xdw = dw0 * g.xij[0] + dw1 * g.xij[1] + dw2 * g.xij[2]; // XIJ . DWIJ
+        const T rsum1 = fast_rcp(rhoj + D.rho);
+        if (fl & F_EP) { // edac.py:323-343 / :448-478
+            T pij = rhoj * (D.p - D.pavg) + D.rho * (s[7] - D.pavg);
+            pij *= rsum1;
+            T tmp = -pij * D.mi1 * vsum;
+            D.au += tmp * dw0; D.av += tmp * dw1; D.aw += tmp * dw2;
+            if (INT) {
+                tmp = -a.p.pb * D.mi1 * vsum;
+                D.auh += tmp * dw0; D.avh += tmp * dw1; D.awh += tmp * dw2;
+            }
+        }
+        if (fl & F_TAV) { // transport_velocity.py:420-436
+            const T vijdotrij = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
+            T piij = T(0.0);
+            if (vijdotrij < 0) {
+                const T muij = (g.hij * vijdotrij) * fast_rcp(r2 + g.eps);
+                piij = -a.p.alpha * a.p.c0 * muij;
+                piij = s[9] * piij * fast_rcp(T(0.5) * (D.rho + rhoj));
+            }
+            D.au += -piij * dw0; D.av += -piij * dw1; D.aw += -piij * dw2;
+        }
+        if (fl & (F_TVISC | F_EDAC)) {
+            // 2 rho_i rho_j / (rho_i + rho_j) / (r^2 + eps) (Vi2 + Vj2) / m_i (XIJ . DWIJ): shared by the physical
+            // viscosity (transport_velocity.py:363-384, times nu) and the pressure damping (edac.py:375,384-386, times edac_nu)
+            const T common = T(2.0) * (D.rho * rhoj) * rsum1 * D.mi1 * vsum * xdw * fast_rcp(r2 + g.eps);
+            if (fl & F_TVISC) {
+                const T tmp = a.p.nu * common;
+                D.au += tmp * vij0; D.av += tmp * vij1; D.aw += tmp * vij2;
+            }
+            if (fl & F_EDAC) {
+                const T vijdotdwij = dw0 * vij0 + dw1 * vij1 + dw2 * vij2;
+                D.ap += D.rho * fast_rcp(rhoj) * a.p.cs2 * s[9] * vijdotdwij; // :380-381
+                D.ap += a.p.enu * common * (D.p - s[7]);
+            }
+        }
+        if (INT && (fl & F_TAS)) { // transport_velocity.py:473-545, as FamTVF_T
+            const T ddi = (D.uh - D.u) * dw0 + (D.vh - D.v) * dw1 + (D.wh - D.w) * dw2;
+            const T ddj = (s[3] - s[0]) * dw0 + (s[4] - s[1]) * dw1 + (s[5] - s[2]) * dw2;
+            const T ci = D.rho * ddi, cj = rhoj * ddj;
+            const T tmp = T(0.5) * D.mi1 * vsum;
+            D.au += tmp * (ci * D.u + cj * s[0]);
+            D.av += tmp * (ci * D.v + cj * s[1]);
+            D.aw += tmp * (ci * D.w + cj * s[2]);
+        }
+        if (!INT && (fl & F_EXS)) { // basic_equations.py:290-295
+            T wij = pair_w<KK, UH>(g);
+            wij = pass ? wij : T(0.0);
+            const T tmp = -a.p.eps * s[9] * wij * fast_rcp(T(0.5) * (D.rho + rhoj));
+            D.ax += tmp * vij0; D.ay += tmp * vij1; D.az += tmp * vij2;
+        }
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        if (a.dflags & (F_EP | F_TVISC | F_TAV | F_TAS)) {
+            T gx = T(0.0), gy = T(0.0), gz = T(0.0);
+            if (a.dflags & F_EP) { // post_loop edac.py:345-351 / :480-488
+                T damp = T(1.0);
+                if (a.t < a.p.tdamp) damp = T(0.5) * (sin((-T(0.5) + a.t / a.p.tdamp) * M_PI) + T(1.0));
+                gx = a.p.gx * damp; gy = a.p.gy * damp; gz = a.p.gz * damp;
+            }
+            a.p.au[o] = D.au + gx; a.p.av[o] = D.av + gy; a.p.aw[o] = D.aw + gz;
+        }
+        if (INT && (a.dflags & F_EP)) { a.p.auhat[o] = D.auh; a.p.avhat[o] = D.avh; a.p.awhat[o] = D.awh; }
+        if (a.dflags & F_EDAC) a.p.ap[o] = D.ap;
+        if (!INT && (a.dflags & F_EXS)) { // post_loop basic_equations.py:297-300: with eps = 0 still ax = u (EDACStep moves x with it)
+            a.p.ax[o] = D.ax + D.u; a.p.ay[o] = D.ay + D.v; a.p.az[o] = D.az + D.w;
+        }
+    }
+};
+
+// EDAC records of the aggregated kernel under uniform h: k_pack layout 3 in its seven-piece form
+// [x y | z rho | u v | w p | Vj2 what | uhat vhat | m -] (112 B instead of the generic 128 B); the sixth piece is
+// read only where the artificial stress acts, the seventh (m: the pressure rate reads it) always.
+template <bool INT>
+__device__ __forceinline__ void load_record_edac(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12])
+{
+    const double2 *r2 = reinterpret_cast<const double2 *>(rj);
+    const double2 a0 = r2[0], a1 = r2[1], b0 = r2[2], b1 = r2[3], c0 = r2[4], e0 = r2[6];
+    pj.x = a0.x; pj.y = a0.y; pj.z = a1.x; pj.w = 0.0;
+    s[0] = b0.x; s[1] = b0.y; s[2] = b1.x; s[6] = a1.y; s[7] = b1.y; s[8] = 0.0; s[9] = e0.x; s[10] = c0.x; s[11] = 0.0;
+    s[3] = s[4] = 0.0; s[5] = c0.y;
+    if (INT && (fl & F_TAS)) {
+        const double2 d0 = r2[5];
+        s[3] = d0.x; s[4] = d0.y;
+    }
+}
+template <> __device__ __forceinline__ void load_record<FamEDAC_T<double, true>, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12]) { load_record_edac<true>(rj, fl, pj, s); }
+template <> __device__ __forceinline__ void load_record<FamEDAC_T<double, false>, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12]) { load_record_edac<false>(rj, fl, pj, s); }
+
+// ---- ComputeAveragePressure (edac.py:62-79), with the density summations when they share its destination and
+//      group (EDACScheme without solids).  pavg = sum of the neighbours' p, nnbr = their number -- the pairs that
+//      pass the exact criterion, as FamNbr counts them -- and the division.  Records [x y z h | m p].
+enum { F_AVGP = 4 }; // next to F_SD = 1, F_TVFSD = 2
+template <class T> struct FamAvgP_T {
+    typedef T Real;
+    static constexpr bool PRED = true;
+    static constexpr uint32_t CF0 = F_TVFSD | F_AVGP;
+    static constexpr int MINB = 4;
+    static constexpr int NA = 2; // m p
+    static constexpr int NR = 6; // x y z h m p
+    struct Params { double *rho, *V, *pavg, *nnbr; };
+    struct Dest { T m, rho, V, ps, nn; };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        D.m = a[0]; D.rho = T(0.0); D.V = T(0.0); D.ps = T(0.0); D.nn = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
+    {
+        if (fl & (F_SD | F_TVFSD)) {
+            PairGeomT<T> g;
+            pair_geom<KK, UH>(g, pi, pj, r2, a);
+            T wij = pair_w<KK, UH>(g);
+            wij = pass ? wij : T(0.0);
+            if (fl & F_SD) D.rho += s[0] * wij;
+            if (fl & F_TVFSD) { D.V += wij; D.rho += D.m * wij; }
+        }
+        if (fl & F_AVGP) { D.ps += pass ? s[1] : T(0.0); D.nn += pass ? T(1.0) : T(0.0); }
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        if (a.dflags & (F_SD | F_TVFSD)) a.p.rho[o] = D.rho;
+        if (a.dflags & F_TVFSD) a.p.V[o] = D.V;
+        if (a.dflags & F_AVGP) {
+            a.p.pavg[o] = D.nn > T(0.0) ? D.ps / D.nn : D.ps; // post_loop :77-79
+            a.p.nnbr[o] = D.nn;
+        }
+    }
+};
+
 // ---- velocity gradient (basic_equations.py:63-148) -------------------------
 template <class T> struct FamVGrad_T {
     typedef T Real; // arithmetic type of the pair loop
@@ -1636,7 +1819,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     return SPH_OK;
 }
 
-enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE };
+enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP };
 
 static bool is_wcsph_option_kind(int k)
 {
@@ -1644,9 +1827,36 @@ static bool is_wcsph_option_kind(int k)
            k == SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH;
 }
 
+static bool is_edac_force_kind(int k) { return k == SPH_EQ_EDAC_MOMENTUM || k == SPH_EQ_EDAC_MOM_PRESSURE || k == SPH_EQ_EDAC; }
+
 // wcsphx: the destination carries a delta-SPH or laminar-viscosity term: its Continuity / Momentum / XSPH go with it
-static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false)
+// edac: it carries an EDAC force equation: the TVF viscosity / artificial viscosity / artificial stress and XSPH go with it
+// avgp: it carries ComputeAveragePressure: a density summation goes with it
+static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false, bool edac = false, bool avgp = false)
 {
+    switch (kind) {
+    case SPH_EQ_EDAC_MOMENTUM: *flag = F_EP; return FAM_EDAC;
+    case SPH_EQ_EDAC_MOM_PRESSURE: *flag = F_EP | F_EINT; return FAM_EDAC;
+    case SPH_EQ_EDAC: *flag = F_EDAC; return FAM_EDAC;
+    case SPH_EQ_EDAC_AVG_PRESSURE: *flag = F_AVGP; return FAM_AVGP;
+    default: break;
+    }
+    if (edac && !elastic) {
+        switch (kind) {
+        case SPH_EQ_TVF_MOM_VISCOSITY: *flag = F_TVISC; return FAM_EDAC;
+        case SPH_EQ_TVF_MOM_ART_VISCOSITY: *flag = F_TAV; return FAM_EDAC;
+        case SPH_EQ_TVF_MOM_ART_STRESS: *flag = F_TAS; return FAM_EDAC;
+        case SPH_EQ_XSPH: *flag = F_EXS; return FAM_EDAC;
+        default: break;
+        }
+    }
+    if (avgp) {
+        switch (kind) {
+        case SPH_EQ_SUMMATION_DENSITY: *flag = F_SD; return FAM_AVGP;
+        case SPH_EQ_TVF_SUMMATION_DENSITY: *flag = F_TVFSD; return FAM_AVGP;
+        default: break;
+        }
+    }
     switch (kind) {
     case SPH_EQ_CONTINUITY_DELTA_SPH: *flag = F_DCONT; return FAM_WCSPHX;
     case SPH_EQ_MOMENTUM_DELTA_SPH: *flag = F_DMOM; return FAM_WCSPHX;
@@ -1722,6 +1932,10 @@ static PackPlan pack_plan(int fam)
         p.nr = FamDensity::NR;
         p.na = 1;
         p.props[0] = SPH_M;
+    } else if (fam == FAM_AVGP) {
+        p.nr = 6;
+        p.na = 2;
+        p.props[0] = SPH_M; p.props[1] = SPH_P;
     } else if (fam == FAM_NBR) {
         p.nr = FamNbr::NR;
         p.na = 1;
@@ -1739,7 +1953,7 @@ static PackPlan pack_plan(int fam)
                       SPH_R00, SPH_R01, SPH_R02, SPH_R11, SPH_R12, SPH_R22, SPH_P};
         for (int k = 0; k < 19; k++) p.props[k] = pr[k];
         p.derived = 3;
-    } else {
+    } else { // FAM_TVF and FAM_EDAC
         p.nr = FamTVF::NR;
         p.na = 12;
         int pr[12] = {SPH_U, SPH_V, SPH_W, SPH_UHAT, SPH_VHAT, SPH_WHAT, SPH_RHO, SPH_P, SPH_VOL, SPH_M, -1, -1};
@@ -1775,10 +1989,11 @@ static bool slot_required(int fam, uint32_t flags, int prop)
         if (prop >= SPH_S00 && prop <= SPH_S22) return flags & F_ESTRESS;
         return false; // r_ij default to 0 when absent
     }
-    if (fam == FAM_TVF) {
+    if (fam == FAM_TVF || fam == FAM_EDAC) {
         if (prop == SPH_UHAT || prop == SPH_VHAT || prop == SPH_WHAT) return flags & F_TAS;
         return true;
     }
+    if (fam == FAM_AVGP) return prop == SPH_M ? (flags & (F_SD | F_TVFSD)) != 0 : (flags & F_AVGP) != 0;
     return false;
 }
 
@@ -1859,7 +2074,7 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
     if (c->pair_variant >= 2) pa.rec = c->posh.as<double>();
     if (c->pair_variant >= 3) pa.fpos = c->fposb.as<float4>();
     pa.layout = (c->pair_variant >= 3 && fam == FAM_WCSPH) ? 1 : (c->pair_variant >= 3 && (fam == FAM_DENSITY || fam == FAM_NBR) && pl.nr == 4) ? 2
-              : (c->pair_variant >= 3 && fam == FAM_TVF && (pl.nr == 14 || pl.nr == 12)) ? 3 : 0;
+              : (c->pair_variant >= 3 && (fam == FAM_TVF || fam == FAM_EDAC) && (pl.nr == 14 || pl.nr == 12)) ? 3 : 0;
     if (c->pair_variant >= 3 && (c->record_f32 || c->arith_f32)) pa.layout = 5;
     pa.umass = 0;
     if (c->cur_eosf) {
@@ -2398,7 +2613,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         int srcs[SPH_MAX_ARRAYS], nsrcs = 0;
         uint32_t sflags[SPH_MAX_ARRAYS] = {};
         int fam = FAM_NONE;
-        const sph_equation *eq_of[32] = {};
+        const sph_equation *eq_of[64] = {};
         bool elastic = false;
         for (int i = 0; i < g->neq; i++) {
             const sph_equation &e = g->eqs[i];
@@ -2408,13 +2623,19 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         }
         bool wcsphx = false; // a delta-SPH / laminar-viscosity term on this destination: the WCSPH-options family
         for (int i = 0; i < g->neq; i++) wcsphx |= g->eqs[i].dest == dst && g->eqs[i].nsrc > 0 && is_wcsph_option_kind(g->eqs[i].kind);
-        int eq_pos[32] = {};
+        bool edac = false, avgp = false; // an EDAC force equation / ComputeAveragePressure on this destination
+        for (int i = 0; i < g->neq; i++) {
+            const bool here = g->eqs[i].dest == dst && g->eqs[i].nsrc > 0;
+            edac |= here && is_edac_force_kind(g->eqs[i].kind);
+            avgp |= here && g->eqs[i].kind == SPH_EQ_EDAC_AVG_PRESSURE;
+        }
+        int eq_pos[64] = {};
         for (int i = 0; i < g->neq; i++) {
             const sph_equation &e = g->eqs[i];
             if (e.dest != dst || e.nsrc == 0) continue;
-            if (e.kind < 0 || e.kind >= 32) { sph_set_error("bad equation kind %d", e.kind); return SPH_ERR_ARG; }
+            if (e.kind < 0 || e.kind >= 64) { sph_set_error("bad equation kind %d", e.kind); return SPH_ERR_ARG; }
             uint32_t flag = 0;
-            int f = eq_family(e.kind, &flag, elastic, wcsphx);
+            int f = eq_family(e.kind, &flag, elastic, wcsphx, edac, avgp);
             eq_pos[e.kind] = i;
             if (f == FAM_NONE) { sph_set_error("equation kind %d has no hand-written pair kernel", e.kind); return SPH_ERR_UNSUPPORTED; }
             if (fam != FAM_NONE && f != fam) {
@@ -2449,6 +2670,14 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             if ((dflags & F_DCONT) && !(dflags & F_CONT)) { sph_set_error("ContinuityEquationDeltaSPH needs a ContinuityEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
             if ((dflags & (F_DMOM | F_LAM | F_LAMD)) && !(dflags & F_MOM)) { sph_set_error("the delta-SPH / laminar viscosity terms need a MomentumEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
             if ((dflags & F_LAM) && (dflags & F_LAMD)) { sph_set_error("both LaminarViscosity and LaminarViscosityDeltaSPH on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        }
+        if (fam == FAM_EDAC) {
+            if (eq_of[SPH_EQ_EDAC_MOMENTUM] && eq_of[SPH_EQ_EDAC_MOM_PRESSURE]) { sph_set_error("both EDAC pressure-gradient forms on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+            if ((dflags & F_EINT) && (dflags & F_EXS)) { sph_set_error("XSPHCorrection next to the internal-flow EDAC pressure gradient on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+            if (!(dflags & F_EINT) && (dflags & F_TAS)) { sph_set_error("MomentumEquationArtificialStress next to the external-flow EDAC equations on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+            // the branch is a property of the destination: one instantiation per branch, and equal flag sets on the
+            // sources of a default group so that the compile-time set applies
+            if (dflags & F_EINT) for (int j = 0; j < nsrcs; j++) sflags[j] |= F_EINT;
         }
         if (fam == FAM_DSPRE) {
             // the moment matrix must be complete before a corrected gradient reads it: a group of its own, as in WCSPHScheme
@@ -2516,6 +2745,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         if (c->pair_variant >= 3 && fam == FAM_WCSPH && c->uniform_h && c->use_uniform_h && !(dflags & F_TENSILE)) pl.nr = c->wcsph_nr ? (int)c->wcsph_nr : 10;
         if (c->pair_variant >= 3 && fam == FAM_DENSITY && c->uniform_h && c->use_uniform_h) pl.nr = 4;
         if (c->pair_variant >= 3 && fam == FAM_TVF && c->uniform_h && c->use_uniform_h) pl.nr = (dflags & F_TAV) ? 14 : 12;
+        if (c->pair_variant >= 3 && fam == FAM_EDAC && c->uniform_h && c->use_uniform_h) pl.nr = 14; // (m always: load_record_edac)
         if (c->pair_variant >= 3 && (c->record_f32 || c->arith_f32)) pl.nr = (4 + pl.na + 3) & ~3; // floats
         // The caller promised (sph_group.src_eos) that p, cs of every array read here are the Tait EOS of its
         // rho: with gamma = 7 (powers by multiplication), uniform h and no tensile correction the pair kernel
@@ -2817,6 +3047,59 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(c, K->kind, a);
             else return launch_pair<F>(c, K->kind, a);
         };
+        // the EDAC force group: parameters of its up to six equations; ap and pavg are user properties by name
+        auto run_edac = [&](auto tag) -> int {
+            typedef decltype(tag) F;
+            PairArgs<F> a;
+            memset(&a, 0, sizeof a);
+            common(a);
+            const sph_equation *pe = eq_of[SPH_EQ_EDAC_MOM_PRESSURE], *me = eq_of[SPH_EQ_EDAC_MOMENTUM], *ee = eq_of[SPH_EQ_EDAC],
+                               *ve = eq_of[SPH_EQ_TVF_MOM_VISCOSITY], *ae = eq_of[SPH_EQ_TVF_MOM_ART_VISCOSITY], *xe = eq_of[SPH_EQ_XSPH];
+            if (pe) { a.p.pb = pe->par[0]; a.p.gx = pe->par[1]; a.p.gy = pe->par[2]; a.p.gz = pe->par[3]; a.p.tdamp = pe->par[4]; }
+            if (me) { a.p.gx = me->par[1]; a.p.gy = me->par[2]; a.p.gz = me->par[3]; a.p.tdamp = me->par[4]; } // par c0 gx gy gz tdamp
+            if (ve) a.p.nu = ve->par[0];
+            if (ae) { a.p.c0 = ae->par[0]; a.p.alpha = ae->par[1]; }
+            if (ee) { a.p.cs2 = ee->par[0] * ee->par[0]; a.p.enu = ee->par[1]; } // par cs nu rho0
+            if (xe) a.p.eps = xe->par[0];
+            a.p.m = D.prop[SPH_M];
+            if (dflags & (F_EP | F_TVISC | F_TAV | F_TAS)) {
+                SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW}));
+                a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
+            }
+            if (dflags & F_EINT) {
+                SPH_TRY(ensure_out(c, dst, {SPH_AUHAT, SPH_AVHAT, SPH_AWHAT}));
+                a.p.auhat = D.prop[SPH_AUHAT]; a.p.avhat = D.prop[SPH_AVHAT]; a.p.awhat = D.prop[SPH_AWHAT];
+                const int ppavg = sph_prop_register("pavg");
+                if (ppavg < 0) return ppavg;
+                SPH_TRY(need_prop(c, dst, ppavg, "MomentumEquationPressureGradient of EDAC (pavg)"));
+                a.p.pavg = D.prop[ppavg];
+            }
+            if (dflags & F_EDAC) {
+                const int pap = sph_prop_register("ap");
+                if (pap < 0) return pap;
+                SPH_TRY(ensure_out(c, dst, {pap}));
+                a.p.ap = D.prop[pap];
+            }
+            if (dflags & F_EXS) {
+                SPH_TRY(ensure_out(c, dst, {SPH_AX, SPH_AY, SPH_AZ}));
+                a.p.ax = D.prop[SPH_AX]; a.p.ay = D.prop[SPH_AY]; a.p.az = D.prop[SPH_AZ];
+            }
+            return launch_pair<F>(c, K->kind, a);
+        };
+        auto run_avgp = [&](auto tag) -> int {
+            typedef decltype(tag) F;
+            PairArgs<F> a;
+            memset(&a, 0, sizeof a);
+            common(a);
+            if ((dflags & F_SD) && (dflags & F_TVFSD)) { sph_set_error("both SummationDensity flavours on one destination"); return SPH_ERR_UNSUPPORTED; }
+            if (dflags & (F_SD | F_TVFSD)) { SPH_TRY(ensure_out(c, dst, {SPH_RHO})); a.p.rho = D.prop[SPH_RHO]; }
+            if (dflags & F_TVFSD) { SPH_TRY(ensure_out(c, dst, {SPH_VOL})); a.p.V = D.prop[SPH_VOL]; }
+            const int ppavg = sph_prop_register("pavg"), pnn = sph_prop_register("nnbr");
+            if (ppavg < 0 || pnn < 0) return SPH_ERR_ARG;
+            SPH_TRY(ensure_out(c, dst, {ppavg, pnn}));
+            a.p.pavg = D.prop[ppavg]; a.p.nnbr = D.prop[pnn];
+            return launch_pair<F>(c, K->kind, a);
+        };
         const bool f32 = c->arith_f32 != 0;
         const bool g7 = tait_gk(g->eos_par[2]) == 3; // the usual exponent: kernels that fold it
         if (fam == FAM_WCSPH && eosf && umass && g7) SPH_TRY(f32 ? run_wcsph(FamWCSPHE_T<float, true>()) : run_wcsph(FamWCSPHE_T<double, true>()));
@@ -2829,6 +3112,9 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         else if (fam == FAM_WCSPHX) SPH_TRY(f32 ? run_wcsphx(FamWCSPHX_T<float, false>()) : run_wcsphx(FamWCSPHX_T<double, false>()));
         else if (fam == FAM_DSPRE) SPH_TRY(f32 ? run_dspre(FamDSPre_T<float>()) : run_dspre(FamDSPre_T<double>()));
         else if (fam == FAM_DENSITY) SPH_TRY(f32 ? run_density(FamDensity_T<float>()) : run_density(FamDensity()));
+        else if (fam == FAM_AVGP) SPH_TRY(f32 ? run_avgp(FamAvgP_T<float>()) : run_avgp(FamAvgP_T<double>()));
+        else if (fam == FAM_EDAC && (dflags & F_EINT)) SPH_TRY(f32 ? run_edac(FamEDAC_T<float, true>()) : run_edac(FamEDAC_T<double, true>()));
+        else if (fam == FAM_EDAC) SPH_TRY(f32 ? run_edac(FamEDAC_T<float, false>()) : run_edac(FamEDAC_T<double, false>()));
         else if (fam == FAM_VGRAD) SPH_TRY(f32 ? run_vgrad(FamVGrad_T<float>()) : run_vgrad(FamVGrad()));
         else if (fam == FAM_ELASTIC && elu) SPH_TRY(f32 ? run_elastic(FamElasticU_T<float>()) : run_elastic(FamElasticU_T<double>()));
         else if (fam == FAM_ELASTIC) SPH_TRY(f32 ? run_elastic(FamElastic_T<float>()) : run_elastic(FamElastic()));
@@ -3193,6 +3479,11 @@ template <class Fam, int K> int launch_interp_ext(sph_ctx *c, const PairArgs<Fam
 UNIT_BOTH(UNIT_PAIR, FamWCSPH_T);
 UNIT_BOTH(UNIT_PAIR, FamDensity_T);
 UNIT_BOTH(UNIT_PAIR, FamTVF_T);
+UNIT_BOTH(UNIT_PAIR, FamAvgP_T);
+template <class T> using FamEDACInt_T = FamEDAC_T<T, true>;
+template <class T> using FamEDACExt_T = FamEDAC_T<T, false>;
+UNIT_BOTH(UNIT_PAIR, FamEDACInt_T);
+UNIT_BOTH(UNIT_PAIR, FamEDACExt_T);
 UNIT_BOTH(UNIT_PAIR, FamVGrad_T);
 UNIT_BOTH(UNIT_PAIR, FamElastic_T);
 UNIT_BOTH(UNIT_PAIR, FamDSPre_T);

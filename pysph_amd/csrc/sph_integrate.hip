@@ -11,6 +11,7 @@ struct StageArgs {
     int stepper, stage;
     double dt;
     size_t n;
+    int ip0, iap; // EDAC steppers: the user properties p0 and ap
     double *p[SPH_PROP_COUNT];
 };
 
@@ -70,6 +71,32 @@ __global__ __launch_bounds__(256) void k_stage(StageArgs a)
             p[SPH_U][i] = u; p[SPH_V][i] = v; p[SPH_W][i] = w;
             p[SPH_VMAG2][i] = u * u + v * v + w * w;
         }
+    } else if (a.stepper == SPH_STEP_EDAC || a.stepper == SPH_STEP_EDAC_TVF) {
+        if (a.stage == 0) { // wc/edac.py:95-105, :493-503
+            p[SPH_X0][i] = p[SPH_X][i]; p[SPH_Y0][i] = p[SPH_Y][i]; p[SPH_Z0][i] = p[SPH_Z][i];
+            p[SPH_U0][i] = p[SPH_U][i]; p[SPH_V0][i] = p[SPH_V][i]; p[SPH_W0][i] = p[SPH_W][i];
+            p[a.ip0][i] = p[SPH_P][i];
+        } else { // stage1 (dt/2), stage2 (dt)
+            const double f = a.stage == 1 ? dtb2 : dt;
+            const double u = p[SPH_U0][i] + f * p[SPH_AU][i];
+            const double v = p[SPH_V0][i] + f * p[SPH_AV][i];
+            const double w = p[SPH_W0][i] + f * p[SPH_AW][i];
+            p[SPH_U][i] = u; p[SPH_V][i] = v; p[SPH_W][i] = w;
+            if (a.stepper == SPH_STEP_EDAC) { // :107-133: positions move with ax (u + the XSPH correction)
+                p[SPH_X][i] = p[SPH_X0][i] + f * p[SPH_AX][i];
+                p[SPH_Y][i] = p[SPH_Y0][i] + f * p[SPH_AY][i];
+                p[SPH_Z][i] = p[SPH_Z0][i] + f * p[SPH_AZ][i];
+            } else { // :505-540: with the transport velocity
+                const double uh = u + f * p[SPH_AUHAT][i];
+                const double vh = v + f * p[SPH_AVHAT][i];
+                const double wh = w + f * p[SPH_AWHAT][i];
+                p[SPH_UHAT][i] = uh; p[SPH_VHAT][i] = vh; p[SPH_WHAT][i] = wh;
+                p[SPH_X][i] = p[SPH_X0][i] + f * uh;
+                p[SPH_Y][i] = p[SPH_Y0][i] + f * vh;
+                p[SPH_Z][i] = p[SPH_Z0][i] + f * wh;
+            }
+            p[SPH_P][i] = p[a.ip0][i] + f * p[a.iap][i];
+        }
     }
 }
 
@@ -92,15 +119,24 @@ extern "C" int sph_integrate_stage(sph_ctx *c, int id, int stepper, int stage, d
                               SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, SPH_RHO0, SPH_E0, SPH_S000, SPH_S010, SPH_S020, SPH_S110,
                               SPH_S120, SPH_S220, SPH_AX, SPH_AY, SPH_AZ, SPH_AU, SPH_AV, SPH_AW, SPH_ARHO, SPH_AE, SPH_AS00, SPH_AS01,
                               SPH_AS02, SPH_AS11, SPH_AS12, SPH_AS22, -1};
+    const int ip0 = sph_prop_register("p0"), iap = sph_prop_register("ap");
+    if (ip0 < 0 || iap < 0) return SPH_ERR_ARG;
+    const int ed0[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_P, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, ip0, -1};
+    const int ed1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_P, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, ip0,
+                       SPH_AU, SPH_AV, SPH_AW, SPH_AX, SPH_AY, SPH_AZ, iap, -1};
+    const int et1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_P, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, ip0,
+                       SPH_AU, SPH_AV, SPH_AW, SPH_UHAT, SPH_VHAT, SPH_WHAT, SPH_AUHAT, SPH_AVHAT, SPH_AWHAT, iap, -1};
     const int *need = nullptr;
-    if (stepper == SPH_STEP_WCSPH) need = stage == 0 ? wc0 : wc1;
+    if (stepper == SPH_STEP_EDAC) need = stage == 0 ? ed0 : ed1;
+    else if (stepper == SPH_STEP_EDAC_TVF) need = stage == 0 ? ed0 : et1;
+    else if (stepper == SPH_STEP_WCSPH) need = stage == 0 ? wc0 : wc1;
     else if (stepper == SPH_STEP_SOLID_MECH) need = stage == 0 ? sm0 : sm1;
     else if (stepper == SPH_STEP_TVF) { if (stage == 0) return SPH_OK; need = stage == 1 ? tv1 : tv2; }
     else { sph_set_error("sph_integrate_stage: unknown stepper %d", stepper); return SPH_ERR_UNSUPPORTED; }
     for (const int *q = need; *q >= 0; q++) SPH_TRY(sph_array_ensure_prop(c, id, *q));
     if (A.n_real == 0) return SPH_OK;
     StageArgs a;
-    a.stepper = stepper; a.stage = stage; a.dt = dt; a.n = A.n_real;
+    a.stepper = stepper; a.stage = stage; a.dt = dt; a.n = A.n_real; a.ip0 = ip0; a.iap = iap;
     for (int k = 0; k < SPH_PROP_COUNT; k++) a.p[k] = A.prop[k];
     ScopedTimer tm(c, T_STAGE);
     hipLaunchKernelGGL(k_stage, dim3(div_up(A.n_real, 256)), dim3(256), 0, c->stream, a);

@@ -304,6 +304,10 @@ EQ_MOMENTUM_DELTA_SPH = 26
 EQ_LAMINAR_VISCOSITY = 27
 EQ_LAMINAR_VISCOSITY_DELTA_SPH = 28
 EQ_UPDATE_H_FERRARI = 29
+EQ_EDAC_AVG_PRESSURE = 30
+EQ_EDAC_MOMENTUM = 31
+EQ_EDAC_MOM_PRESSURE = 32
+EQ_EDAC = 33
 
 _XV = ('x', 'y', 'z', 'h')
 EQUATION_TABLE = OrderedDict([
@@ -381,6 +385,23 @@ EQUATION_TABLE = OrderedDict([
         _XV + ('u', 'v', 'w', 'rho', 'm'))),
     ('UpdateSmoothingLengthFerrari', (
         EQ_UPDATE_H_FERRARI, ('dim1', 'hdx'), ('h', 'm', 'rho'), ())),   # dim1 = 1 / dim
+    # EDAC (pysph_amd/edac.py, pysph/sph/wc/edac.py).  Its MomentumEquation and MomentumEquationPressureGradient share
+    # their class names with the WCSPH / TVF ones: `resolve_equation` tells them apart by module and looks them up
+    # under the 'EDAC...' keys.  One force family reads every slot of its records on every source (u v w rho p V m).
+    ('ComputeAveragePressure', (
+        EQ_EDAC_AVG_PRESSURE, (), _XV + ('pavg', 'nnbr'), _XV + ('p',))),
+    ('EDACMomentumEquation', (
+        EQ_EDAC_MOMENTUM, ('c0', 'gx', 'gy', 'gz', 'tdamp'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V', 'au', 'av', 'aw'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V'))),
+    ('EDACMomentumEquationPressureGradient', (
+        EQ_EDAC_MOM_PRESSURE, ('pb', 'gx', 'gy', 'gz', 'tdamp'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'pavg', 'V', 'au', 'av', 'aw', 'auhat', 'avhat', 'awhat'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V'))),
+    ('EDACEquation', (
+        EQ_EDAC, ('cs', 'nu', 'rho0'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V', 'ap'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V'))),
 ])
 
 # equations that have no neighbour loop
@@ -397,6 +418,10 @@ def resolve_equation(eq):
         name = 'TVFSummationDensity'
     if name == 'IsothermalEOS' and 'solid_mech' in type(eq).__module__:
         name = 'SolidIsothermalEOS'
+    if 'edac' in type(eq).__module__:
+        # EDAC's own classes of these names (wc/edac.py:301, :389), this package's or the reference's
+        if name in ('MomentumEquation', 'MomentumEquationPressureGradient'):
+            name = 'EDAC' + name
     if name not in EQUATION_TABLE:
         try:   # the elastic family registers itself on import
             from . import solid_mech  # noqa: F401

@@ -49,10 +49,24 @@ class TransportVelocityStep(IntegratorStep):
 
 STEP_RIGID_RK2 = 4
 STEP_RIGID_EULER = 5
+STEP_EDAC = 6
+STEP_EDAC_TVF = 7
+
+
+class EDACStep(IntegratorStep):
+    """pysph/sph/wc/edac.py:82-133: predictor-corrector on x, u and the pressure; positions move with ax."""
+    _kind = STEP_EDAC
+
+
+class EDACTVFStep(IntegratorStep):
+    """pysph/sph/wc/edac.py:491-540: the same with the transport velocity."""
+    _kind = STEP_EDAC_TVF
+
 
 # (the two rigid-body steppers are classes of pysph_amd.rigid_body; their stages need the array's body state)
 _STEP_KINDS = {'WCSPHStep': STEP_WCSPH, 'TransportVelocityStep': STEP_TVF,
-               'RK2StepRigidBody': STEP_RIGID_RK2, 'EulerStepRigidBody': STEP_RIGID_EULER}
+               'RK2StepRigidBody': STEP_RIGID_RK2, 'EulerStepRigidBody': STEP_RIGID_EULER,
+               'EDACStep': STEP_EDAC, 'EDACTVFStep': STEP_EDAC_TVF}
 
 
 def stepper_kind(step):

@@ -276,6 +276,25 @@ def get_particle_array_tvf_fluid(constants=None, **props):
     return pa
 
 
+EDAC_PROPS = ('ap', 'au', 'av', 'aw', 'ax', 'ay', 'az', 'x0', 'y0', 'z0', 'u0', 'v0', 'w0', 'p0', 'V')
+
+EDAC_SOLID_PROPS = ('ap', 'p0', 'wij', 'uf', 'vf', 'wf', 'ug', 'vg', 'wg', 'ax', 'ay', 'az', 'V')
+
+
+def get_particle_array_edac(constants=None, **props):
+    """pysph/sph/wc/edac.py:30-43."""
+    pa = get_particle_array(constants=constants, additional_props=EDAC_PROPS, **props)
+    pa.set_output_arrays(['x', 'y', 'z', 'u', 'v', 'w', 'rho', 'p', 'au', 'av', 'aw', 'ap', 'm', 'h'])
+    return pa
+
+
+def get_particle_array_edac_solid(constants=None, **props):
+    """pysph/sph/wc/edac.py:46-59."""
+    pa = get_particle_array(constants=constants, additional_props=EDAC_SOLID_PROPS, **props)
+    pa.set_output_arrays(['x', 'y', 'z', 'u', 'v', 'w', 'rho', 'p', 'h'])
+    return pa
+
+
 RIGID_BODY_PROPS = ['au', 'av', 'aw', 'V', 'fx', 'fy', 'fz', 'x0', 'y0', 'z0',
                     'tang_disp_x', 'tang_disp_y', 'tang_disp_z', 'tang_disp_x0', 'tang_disp_y0', 'tang_disp_z0',
                     'tang_velocity_x', 'tang_velocity_y', 'rad_s', 'tang_velocity_z', 'nx', 'ny', 'nz']
