@@ -157,6 +157,11 @@ typedef struct {
      *   SPH_EQ_TAIT_EOS[_HG] equation over ALL its particles left them (the
      *   group before this one) -- the pair kernel may recompute them from rho
      *   instead of gathering them (64-byte records).
+     * src_eos = 3: the promise of 1, but that plain SPH_EQ_TAIT_EOS group has NOT
+     *   run: this call applies it to every particle of every array the group
+     *   touches -- while it packs the EOS-fused records of a one-array group
+     *   with gamma = 7 (counter "n_eos_absorbed"), otherwise by the EOS kernel before anything
+     *   else -- and goes on as for 1.  p and cs get the same bits either way.
      * src_eos = 2: p and V of every array this group's pair loops read are
      *   p = p0 (rho / rho0 - b) and V = rho / m with eos_par = {p0, rho0, b, -}, as
      *   SPH_EQ_TVF_STATE_EQUATION (the group before this one) and
@@ -746,6 +751,8 @@ int sph_rigid_motion(sph_ctx *ctx, int array_id, int real_only, long start, long
  *                    group instead of once per destination that reads them.
  *                    Nothing else may modify the arrays in between.
  *   "eos_fuse"       0: ignore sph_group.src_eos (default 1)
+ *   "eos_absorb"     0: the Python host keeps the Tait-EOS group before a WCSPH pair group and passes
+ *                    src_eos = 1; a src_eos = 3 call runs the EOS kernel first (default 1)
  *   "mass_fuse"      0: EOS-fused records always carry the mass (default 1: when every array read by a
  *                    launch had ONE mass at the last sph_nnps_update -- the reduction that finds the
  *                    bounds also looks at m once an evaluation could have used it, i.e. from the second
@@ -807,7 +814,7 @@ int sph_timer_reset(sph_ctx *ctx);
  * renormalised density gradient), "pair_edac" (the EDAC force group), "pair_avg_pressure"
  * (ComputeAveragePressure, alone or with a density summation); out: total ms and launches.  Launch counters (ms = 0, counted
  * whether or not timing is enabled): "n_eos_fused" (pair launches on the 64-byte
- * EOS-fused records), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group
+ * EOS-fused records), "n_eos_absorbed" (of those, the ones whose record packing ran the Tait EOS: sph_group.src_eos 3), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group
  * evaluations run as one launch over the merged order), "n_tension_flag" (elastic rate launches that read the tension word), "n_phase2" (pair launches of the second half of a
  * split evaluation: sph_group.phase 2),
  * "n_nl_keep" / "n_nl_reuse" (launches that kept / started from kept neighbour

@@ -492,6 +492,8 @@ class _CGroup(object):
         self.units = []
         self.rigid_arrays = set()         # arrays whose per-body state the group reads or writes
         self.moments = {}                 # RigidBodyMoments equation -> its unit: run in place of the reduce hook
+        self.eos_absorbed_by = None       # annotate_plan: the pair group after this Tait-EOS group that may run the EOS itself
+        self.absorbs_eos = False          # ... and that pair group's side of it
         self._arrays = arrays
         dests = []
         for eq in group.equations:
@@ -565,7 +567,7 @@ class _CGroup(object):
             u.refresh(start, stop)
         self._start_stop = (start, stop)
 
-    def run(self, ev, t, dt):
+    def _shared(self):
         # several destinations with hand-written kernels only: ONE call for the
         # whole group (the equations by value, as the units hold them now)
         shared = len(self.units) > 1 and all(isinstance(u, _BuiltinUnit) for u in self.units)
@@ -576,9 +578,28 @@ class _CGroup(object):
             u0 = self.units[0].cg
             shared = all(u.cg.src_eos == u0.src_eos and list(u.cg.eos_par) == list(u0.eos_par) and u.cg.nl_mode == 0
                          for u in self.units)
+        return shared
+
+    def will_absorb(self, ev):
+        """Does this pair group run the Tait EOS of the group before it (annotate_plan: absorbs_eos)?  Only as ONE
+        library call, which then sees every array of the group, and unless option eos_absorb is 0."""
+        return bool(self.absorbs_eos and ev.ctx.options.get('eos_absorb', 1)
+                    and (len(self.units) == 1 or self._shared()))
+
+    def run(self, ev, t, dt):
+        if self.eos_absorbed_by is not None and self.eos_absorbed_by.will_absorb(ev):
+            return                       # the pair group after this one runs the equation (src_eos = 3)
+        absorb = self.will_absorb(ev)
+        shared = self._shared()
         if not shared:
             for u in self.units:
-                u.run(ev, t, dt)
+                if absorb:               # (one unit: will_absorb) the promise of 1, the EOS still to run
+                    u.cg.src_eos = 3
+                try:
+                    u.run(ev, t, dt)
+                finally:
+                    if absorb:
+                        u.cg.src_eos = 1
             return
         for u in self.units:
             if u.delta_sph_arrays or u.edac_arrays:
@@ -594,7 +615,7 @@ class _CGroup(object):
         cg.start_idx, cg.stop_idx = self._start_stop
         # the promises annotate_plan made for every unit (the same for all: checked above) hold for the group
         u0 = self.units[0].cg
-        cg.src_eos = u0.src_eos
+        cg.src_eos = 3 if absorb else u0.src_eos
         for k in range(4):
             cg.eos_par[k] = u0.eos_par[k]
         cg.nl_mode = 0
@@ -651,6 +672,8 @@ def annotate_plan(plan):
     leaves = [(g, cg) for g, cg in plan]
     plain = [_plain_leaf(g, cg) for g, cg in leaves]
     for g, cg in leaves:
+        cg.eos_absorbed_by = None
+        cg.absorbs_eos = False
         for u in cg.units:
             if isinstance(u, _BuiltinUnit):
                 u.cg.src_eos = 0
@@ -677,6 +700,8 @@ def annotate_plan(plan):
         if not ok or not eos or len(set(eos.values())) != 1:
             continue
         par = list(eos.values())[0]
+        touched = set()
+        promised = []
         for u in cg1.units:
             used = set()
             pair = True
@@ -686,10 +711,19 @@ def annotate_plan(plan):
                     pair = False
                 used.add(ce.dest)
                 used.update(ce.src[j] for j in range(ce.nsrc))
-            if pair and used and used <= set(eos):
+            touched |= used
+            promised.append(pair and bool(used) and used <= set(eos))
+            if promised[-1]:
                 u.cg.src_eos = 1
                 for k in range(4):
                     u.cg.eos_par[k] = par[k]
+        # ... and when the EOS group is the plain TaitEOS over EXACTLY the arrays of the pair group, every unit of
+        # which got the promise, the pair group may run the equation itself (sph_group.src_eos = 3, _CGroup.run):
+        # the library computes p and cs while it packs the records, or runs the EOS kernel first where it cannot
+        plain_tait = all(u.ceqs[k].kind == 1 for u in cg0.units for k in range(len(u.eqs)))
+        if plain_tait and all(promised) and touched == set(eos):
+            cg0.eos_absorbed_by = cg1
+            cg1.absorbs_eos = True
     # -- TVF state fusion: [TVF SummationDensity | StateEquation | force group], each over ALL
     #    particles (real=False, no range) of the arrays the force group reads: p and V = rho / m
     #    are functions of rho when the force group runs (src_eos = 2, eos_par = p0 rho0 b)

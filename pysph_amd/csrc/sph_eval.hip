@@ -41,6 +41,22 @@
 #endif
 #define SPH_PRIMARY_UNIT (SPH_KERNEL_UNIT == 0)
 
+// TaitEOS (wc/basic.py:60-65): ONE body for k_nosrc and for the pack kernel that absorbs the equation (PackArgs::eos_abs),
+// so that p and cs have the same bits whichever of the two wrote them
+__device__ __forceinline__ void tait_eos(double rho, double rho0, double c0, double gamma, double p0, double &p, double &cs)
+{
+    double ratio = rho * (1.0 / rho0);
+    double tmp, csr;
+    if (tait_gk(gamma) >= 0) { // odd integer exponents (7: water): the powers by multiplication (two pow() calls made this kernel compute-bound)
+        tait_powers(ratio, tait_gk(gamma), tmp, csr);
+    } else {
+        tmp = pow(ratio, gamma);
+        csr = pow(ratio, 0.5 * (gamma - 1.0));
+    }
+    p = p0 + (rho0 * c0 * c0 / gamma) * (tmp - 1.0);
+    cs = c0 * csr;
+}
+
 #if SPH_PRIMARY_UNIT
 
 // ---------------------------------------------------------------------------
@@ -97,18 +113,11 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
     size_t i = a.start + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.stop) return;
     switch (a.kind) {
-    case SPH_EQ_TAIT_EOS: { // wc/basic.py:60-65
-        double rho0 = a.par[0], c0 = a.par[1], gamma = a.par[2], p0 = a.par[3];
-        double ratio = a.rho[i] * (1.0 / rho0);
-        double tmp, csr;
-        if (tait_gk(gamma) >= 0) { // odd integer exponents (7: water): the powers by multiplication (two pow() calls made this kernel compute-bound)
-            tait_powers(ratio, tait_gk(gamma), tmp, csr);
-        } else {
-            tmp = pow(ratio, gamma);
-            csr = pow(ratio, 0.5 * (gamma - 1.0));
-        }
-        a.p[i] = p0 + (rho0 * c0 * c0 / gamma) * (tmp - 1.0);
-        a.cs[i] = c0 * csr;
+    case SPH_EQ_TAIT_EOS: {
+        double p, cs;
+        tait_eos(a.rho[i], a.par[0], a.par[1], a.par[2], a.par[3], p, cs);
+        a.p[i] = p;
+        a.cs[i] = cs;
         break;
     }
     case SPH_EQ_TAIT_EOS_HG: { // wc/basic.py:118-126
@@ -253,6 +262,11 @@ struct PackArgs {
     int lds_np;                   // 16-B pieces per record when the launch carries 256 * lds_np * 16 B of LDS, else 0
     double gmin[3];
     double radius_scale;
+    double hu;                    // h == nullptr: the one h of every particle (uniform h, layouts 6 / 7: the record holds none)
+    int eos_abs;                  // layouts 6 / 7 / 12 / 13: the Tait EOS of the group before has NOT run (sph_group.src_eos = 3):
+                                  // p and cs are computed here from the rho just loaded, stored, and p / rho^2 formed from that p
+    double eos_par[4];            // rho0 c0 gamma p0
+    double *p_out, *cs_out;
 };
 
 #define PACK_MAXP ((4 + MAX_AUX) / 2) // 16-B pieces of the widest record
@@ -297,12 +311,21 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a)
     uint32_t o = a.perm[i];
     const int layout = LAYOUT >= 0 ? LAYOUT : a.layout;
     double4 ph;
-    ph.x = a.x[o]; ph.y = a.y[o]; ph.z = a.z[o]; ph.w = a.h[o];
+    ph.x = a.x[o]; ph.y = a.y[o]; ph.z = a.z[o]; ph.w = a.h ? a.h[o] : a.hu;
     double v[MAX_AUX];
     // (compile-time layouts read the slots their record holds: WCSPH u v w m rho tmpj cs p = 0..7, elastic 0..17 + p)
     constexpr int NV = (LAYOUT == 6 || LAYOUT == 7 || LAYOUT == 12 || LAYOUT == 13) ? 8 : (LAYOUT == 2 ? 1 : (LAYOUT == 3 || LAYOUT == 8 || LAYOUT == 9) ? 11 : MAX_AUX);
 #pragma unroll
     for (int k = 0; k < MAX_AUX; k++) v[k] = (k < NV && (k < a.na || (a.derived == 3 && k == 18) || (a.derived == 4 && k == 4)) && a.src[k]) ? a.src[k][o] : 0.0;
+    if constexpr (LAYOUT == 6 || LAYOUT == 7 || LAYOUT == 12 || LAYOUT == 13) {
+        if (a.eos_abs) { // the Tait EOS of this particle, as k_nosrc would have left it (p is not read: a.src[7] is null)
+            double p, cs;
+            tait_eos(v[4], a.eos_par[0], a.eos_par[1], a.eos_par[2], a.eos_par[3], p, cs);
+            a.p_out[o] = p;
+            a.cs_out[o] = cs;
+            v[7] = p;
+        }
+    }
     if (a.derived == 1) v[5] = v[4] != 0.0 ? v[7] * (1.0 / (v[4] * v[4])) : 0.0; // tmpj = p*rhoj21, wc/basic.py:211,234
     if (a.derived == 2) { double Vj = 1. / v[8]; v[10] = Vj * Vj; } // Vj2, transport_velocity.py:303-306
     if (a.derived == 4) v[3] = v[3] / v[4]; // m/rho, basic_equations.py:103,139 (VelocityGradient tmp)
@@ -2077,16 +2100,24 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
               : (c->pair_variant >= 3 && (fam == FAM_TVF || fam == FAM_EDAC) && (pl.nr == 14 || pl.nr == 12)) ? 3 : 0;
     if (c->pair_variant >= 3 && (c->record_f32 || c->arith_f32)) pa.layout = 5;
     pa.umass = 0;
+    pa.hu = 0.0;
+    pa.eos_abs = 0;
+    for (int k = 0; k < 4; k++) pa.eos_par[k] = 0.0;
+    pa.p_out = pa.cs_out = nullptr;
     if (c->cur_eosf) {
         // p, cs (and p / rho^2) are recomputed by the pair kernel: not read here
         pa.layout = c->arith_f32 ? 7 : 6;
         pa.src[5] = pa.src[6] = nullptr;
         if (c->cur_umass) { // ... except p / rho^2, which takes the place of the (uniform) mass: derived 1 reads p
             pa.umass = 1;
+            pa.src[3] = nullptr; // the record holds no mass
         } else {
             pa.src[7] = nullptr;
             pa.derived = 0;
         }
+        // ... and no h: the prefilter's radius_scale * h from the launch constant of the pair kernel (fill_common: hu)
+        pa.h = nullptr;
+        pa.hu = 0.5 * (c->h_uniform + c->h_uniform);
     }
     if (c->cur_elu) pa.layout = c->arith_f32 ? 11 : 10; // h and m are launch / source constants
     if (c->cur_eosv) { // p, cs, p / rho^2 recomputed, m a source constant: none of them read here
@@ -2098,6 +2129,13 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
         pa.layout = c->arith_f32 ? 9 : 8;
         pa.src[7] = pa.src[8] = pa.src[9] = nullptr;
         pa.derived = 0;
+    }
+    if (c->cur_eos_abs && (c->cur_eosf || c->cur_eosv)) { // the Tait EOS of this array has not run: p and cs leave from here
+        pa.eos_abs = 1;
+        for (int k = 0; k < 4; k++) pa.eos_par[k] = c->cur_eos_par[k];
+        pa.p_out = A.prop[SPH_P];
+        pa.cs_out = A.prop[SPH_CS];
+        pa.src[7] = nullptr; // p is computed, not read
     }
     pa.lds_np = pack_pieces(pa);
     if (launch) launch_pack(c, pa, nseg);
@@ -2563,6 +2601,30 @@ static int eval_group_merged(sph_ctx *c, const sph_kernel *K, const sph_group *g
     return SPH_OK;
 }
 
+// sph_group.src_eos = 3 where the records cannot absorb the equation: the Tait EOS over every particle of every array the
+// group touches, as the group the host left out would have run it
+static int run_pending_eos(sph_ctx *c, const sph_group *g)
+{
+    bool seen[SPH_MAX_ARRAYS] = {};
+    auto one = [&](int id) -> int {
+        if (id < 0 || id >= SPH_MAX_ARRAYS || !c->arr[id].used || seen[id]) return SPH_OK; // (bad ids: reported by the caller)
+        seen[id] = true;
+        sph_equation e;
+        memset(&e, 0, sizeof e);
+        e.kind = SPH_EQ_TAIT_EOS;
+        e.dest = id;
+        for (int k = 0; k < 4; k++) e.par[k] = g->eos_par[k];
+        SPH_TRY(run_nosrc(c, e, 0, c->arr[id].n));
+        c->pack_cache[id].epoch = 0;
+        return SPH_OK;
+    };
+    for (int i = 0; i < g->neq; i++) {
+        SPH_TRY(one(g->eqs[i].dest));
+        for (int k = 0; k < g->eqs[i].nsrc && k < SPH_MAX_ARRAYS; k++) SPH_TRY(one(g->eqs[i].src[k]));
+    }
+    return SPH_OK;
+}
+
 extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *g, double t, double dt)
 {
     if (!c || !K || !g) { sph_set_error("sph_eval_group: NULL argument"); return SPH_ERR_ARG; }
@@ -2571,6 +2633,18 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
     SPH_TRY(check_kernel("sph_eval_group", K));
     HIP_TRY(hipSetDevice(c->device));
     if (!c->pack_group) c->pack_epoch++; // packed records are reused between the destinations of ONE group only (option pack_group)
+    // src_eos = 3: the promise of 1, but the Tait EOS has not run yet.  The EOS-fused records of ONE array compute it while
+    // they are packed (pack_array); everything else runs it here, first, and goes on as for 1.
+    sph_group g_run;
+    bool eos_pending = false;
+    c->cur_eos_abs = false;
+    if (g->src_eos == 3) {
+        g_run = *g;
+        g_run.src_eos = 1;
+        g = &g_run;
+        eos_pending = true;
+        if (c->merged_valid || g->phase != 0) { SPH_TRY(run_pending_eos(c, g)); eos_pending = false; }
+    }
     {
         bool done = false;
         SPH_TRY(eval_group_merged(c, K, g, t, &done));
@@ -2788,6 +2862,26 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         c->cur_umass = umass;
         c->cur_eosf = eosf;
         c->cur_nrec = pl.nr;
+        // The Tait EOS the host left to this call: absorbed by the records when they are the EOS-fused ones of ONE array
+        // and the pack launches below visit every particle of it (both segments); else run now, over all of every array
+        c->cur_eos_abs = false;
+        if (eos_pending) {
+            eos_pending = false;
+            // (gamma = 7 only: the other odd exponents keep the EOS kernel)
+            const bool absorb = (eosf || eosv) && c->eos_absorb && tait_gk(g->eos_par[2]) == 3 && phase == 0 && ndest == 1 &&
+                                nsrcs == 1 && srcs[0] == dst && D.n > 0 && D.n_binned + D.g_n == D.n;
+            if (absorb) {
+                SPH_TRY(need_prop(c, dst, SPH_RHO, "EOS"));
+                SPH_TRY(sph_array_ensure_prop(c, dst, SPH_P));
+                SPH_TRY(sph_array_ensure_prop(c, dst, SPH_CS));
+                c->cur_eos_abs = true;
+                for (int k = 0; k < 4; k++) c->cur_eos_par[k] = g->eos_par[k];
+                c->pack_cache[dst].epoch = 0; // the records are packed now, whatever an earlier destination left
+                c->timers[T_N_EOSABS].count++;
+            } else {
+                SPH_TRY(run_pending_eos(c, g));
+            }
+        }
         const void *rec_was = c->posh.ptr, *fpos_was = c->fposb.ptr;
         // phase 1 leaves room for the ghosts phase 2 packs behind the real particles' records (the array's capacity bounds
         // them); phase 2 keeps what phase 1 packed should the buffers have to grow after all
@@ -2826,6 +2920,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             for (int j = 0; j < nsrcs; j++) SPH_TRY(pack_once(srcs[j], off_of[j], srcs[j] == dst ? dflags : sflags[j], false));
             if (!dest_is_src) SPH_TRY(pack_once(dst, d_off, dflags, true));
         }
+        c->cur_eos_abs = false;
 
         // Neighbour-list reuse between the pair passes of one evaluation (sph_group.nl_mode): one source,
         // the wave-tile kernel, same grid.  A pass that keeps its lists (1) records what they belong to; a pass
@@ -3121,6 +3216,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         else if (tvff) SPH_TRY(f32 ? run_tvf(FamTVFE_T<float>()) : run_tvf(FamTVFE_T<double>()));
         else SPH_TRY(f32 ? run_tvf(FamTVF_T<float>()) : run_tvf(FamTVF()));
     }
+    if (eos_pending) SPH_TRY(run_pending_eos(c, g)); // (no destination came as far as its records)
     HIP_TRY(hipGetLastError());
     return SPH_OK;
 }

@@ -135,7 +135,7 @@ struct RigidState {
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
 // T_N_*: launch counters only (no time): pair launches on EOS-fused records, launches that kept / reused neighbour lists
 // T_N_INTERP_MOM / _SWEEP: moment passes / property sweeps of sph_interpolate
-enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 11, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_COUNT };
+enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 11, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_COUNT };
 
 struct Timer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -297,6 +297,9 @@ struct sph_ctx {
     bool want_mrange = false; // an evaluation could have used uniform-mass records: the next neighbour updates look at the masses
     long block_sorted_outputs = 0;
     long eos_fuse = 1;      // honour sph_group.src_eos (64-byte WCSPH records, p and cs recomputed from rho)
+    long eos_absorb = 1;    // the host may leave the Tait EOS before a WCSPH pair group to that group (sph_group.src_eos = 3)
+    bool cur_eos_abs = false;      // the records being packed absorb the Tait EOS (PackArgs::eos_abs) ...
+    double cur_eos_par[4] = {};    // ... with these parameters: rho0 c0 gamma p0
     long nl_reuse = 0;      // honour sph_group.nl_mode (neighbour lists kept between the pair passes of one evaluation): built,
                             // bit-identical, and measured SLOWER on MI355X (phase 1 overlaps other wavefronts' gathers)
     long fill_holes = 1;    // sph_halo_remove_selected moves the tail's kept rows into the holes when few particles leave (0: always the stable compaction)
