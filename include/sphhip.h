@@ -57,7 +57,7 @@ enum sph_prop {
      * reference's ParticleArray.add_property for equation-specific arrays,
      * e.g. uf, ug, wij of the TVF wall equations)                           */
     SPH_USER0,
-    SPH_PROP_COUNT = SPH_USER0 + 96
+    SPH_PROP_COUNT = SPH_USER0 + 128   /* (the largest by-value kernel argument that holds two pointers per property, IoXfer of sph_halo.hip, stays below 4 KiB) */
 };
 
 /* pysph/base/kernels.py class -> id */
@@ -125,7 +125,21 @@ enum sph_eq_kind {
     SPH_EQ_EDAC_AVG_PRESSURE = 30,            /* wc/edac.py:62-79     (writes pavg, nnbr; alone or with id 7 on a destination) */
     SPH_EQ_EDAC_MOMENTUM = 31,                /* wc/edac.py:301-351   par: c0 gx gy gz tdamp */
     SPH_EQ_EDAC_MOM_PRESSURE = 32,            /* wc/edac.py:389-488   par: pb gx gy gz tdamp   (reads pavg of the destination) */
-    SPH_EQ_EDAC = 33                          /* wc/edac.py:354-386   par: cs nu rho0   (writes ap) */
+    SPH_EQ_EDAC = 33,                         /* wc/edac.py:354-386   par: cs nu rho0   (writes ap) */
+    /* Gas dynamics (pysph/sph/gas_dynamics/basic.py).  e, cs, ae, arho, e0, rho0, dt_cfl are built-in properties; ah, omega,
+     * dwdh, converged, div, grhox..z, alpha1/2, aalpha1/2, alpha10/20, del2e, h0 are user properties (sph_prop_register)
+     * of those names.                                                                                                   */
+    SPH_EQ_GASD_SUMMATION_DENSITY = 34,       /* gas_dynamics/basic.py:74-219   par: dim k htol density_iterations iterate_only_once
+                                                 (writes rho arho grhox..z dwdh div; iterating: h omega ah converged, and
+                                                 the group's convergence word: sph_gasd_unconverged)                      */
+    SPH_EQ_IDEAL_GAS_EOS = 35,                /* :222-230   par: gamma   (no sources; writes p, cs) */
+    SPH_EQ_MPM_ACCELERATIONS = 36,            /* :356-483   par: beta sigma alpha1_min alpha2_min update_alpha1 update_alpha2
+                                                 (writes au av aw ae del2e dt_cfl aalpha1 aalpha2)                         */
+    SPH_EQ_SCALE_SMOOTHING_LENGTH = 37,       /* :13-19     par: factor   (no sources; writes h) */
+    SPH_EQ_UPDATE_H_FROM_VOLUME = 38,         /* :22-29     par: k dim1 (= 1 / dim)   (no sources; writes h) */
+    SPH_EQ_MPM_UPDATE_GHOST_PROPS = 39        /* :486-497   (no sources, Group(real=False)): p and cs of every row behind the real
+                                                 ones from the row the user property orig_idx names (a real row; an image
+                                                 is a copy of its row and so carries that row's orig_idx)                 */
 };
 
 /* One Equation(dest, sources) instance: pysph/sph/equation.py:392-420. */
@@ -669,9 +683,15 @@ enum sph_stepper {
     SPH_STEP_RIGID_RK2 = 4,  /* RK2StepRigidBody    pysph/sph/rigid_body.py:718-770 (needs sph_rigid_setup) */
     SPH_STEP_RIGID_EULER = 5,/* EulerStepRigidBody  pysph/sph/rigid_body.py:695-715 (stage 1 only)          */
     SPH_STEP_EDAC = 6,       /* EDACStep            pysph/sph/wc/edac.py:95-133  (p0, ap: user properties)  */
-    SPH_STEP_EDAC_TVF = 7    /* EDACTVFStep         pysph/sph/wc/edac.py:493-540                            */
+    SPH_STEP_EDAC_TVF = 7,   /* EDACTVFStep         pysph/sph/wc/edac.py:493-540                            */
+    SPH_STEP_GASD = 8        /* GasDFluidStep       integrator_step.py:351-428 (h0, ah, converged, omega, alpha*: user properties) */
 };
 int sph_integrate_stage(sph_ctx *ctx, int array_id, int stepper, int stage, double dt);
+/* The convergence word of the last sph_eval_group call that ran an iterating SPH_EQ_GASD_SUMMATION_DENSITY
+ * (density_iterations != 0): *flag = 1 when at least one destination particle has not converged (the reference's
+ * equation_has_converged = -1), else 0.  Every lane that fails stores the same constant into one device word, no
+ * atomics; the library reads it once per call.                                                                   */
+int sph_gasd_unconverged(sph_ctx *ctx, int *flag);
 /* min over the first n_real particles of a property (h_minimum,
  * pysph/sph/integrator.py:150-160).                                        */
 int sph_reduce_min(sph_ctx *ctx, int array_id, int prop, double *out);
@@ -788,6 +808,10 @@ int sph_rigid_motion(sph_ctx *ctx, int array_id, int real_only, long start, long
  *   "row_lds"        1: the elastic rates on uniform-h records evaluate a row tile's hits from an LDS copy of its
  *                    records, tile after tile (default 0: measured 45 % slower); same pairs,
  *                    another summation order
+ *   "gasd_skip"      1: a wavefront of the iterating gas-dynamics density sweep whose 64 destinations have all converged
+ *                    skips its neighbour work and only restores the raw arho and div (default 0: DESIGN.md section 7g);
+ *                    acts in calls the host marks with "gasd_repeat" 1 -- the second and later iterations of ONE
+ *                    iterated group, between which nothing but the group and the neighbour update ran
  *   "row_mod3"       order in which a wavefront visits its 3x3 rows of cells: 3 (default) = the row whose
  *                    (y mod 3, z mod 3) equals the step, so that all wavefronts in flight walk rows of one
  *                    residue class at a time and find each other's lines in L1 / L2; 1 / 2 = y / z only;
@@ -812,7 +836,9 @@ int sph_timer_reset(sph_ctx *ctx);
  * "pair_elastic", "pair_wcsph_options" (the rates of a WCSPH destination with
  * delta-SPH or laminar-viscosity terms), "pair_delta_sph_pre" (moment matrix and
  * renormalised density gradient), "pair_edac" (the EDAC force group), "pair_avg_pressure"
- * (ComputeAveragePressure, alone or with a density summation); out: total ms and launches.  Launch counters (ms = 0, counted
+ * (ComputeAveragePressure, alone or with a density summation), "pair_gasd_density" (the gas-dynamics density sweep with
+ * its Newton step for h), "pair_gasd_mpm" (MPMAccelerations); the counter "n_gasd_skipped" (wavefronts of that sweep
+ * that left early under option gasd_skip); out: total ms and launches.  Launch counters (ms = 0, counted
  * whether or not timing is enabled): "n_eos_fused" (pair launches on the 64-byte
  * EOS-fused records), "n_eos_absorbed" (of those, the ones whose record packing ran the Tait EOS: sph_group.src_eos 3), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group
  * evaluations run as one launch over the merged order), "n_tension_flag" (elastic rate launches that read the tension word), "n_phase2" (pair launches of the second half of a

@@ -273,14 +273,22 @@ class _BuiltinUnit(object):
         self._const_params = []
         self.delta_sph_arrays = set()     # arrays whose m_mat / gradrho this unit reads or writes
         self.edac_arrays = set()          # arrays an EDAC equation reads or writes
+        self.gasd_arrays = set()          # arrays a gas-dynamics equation reads or writes
+        self.gasd_iterating = []          # the SummationDensity equations of gas dynamics that iterate on h
         for i, eq in enumerate(eqs):
             kind, vals, dprops, sprops = resolve_equation(eq)
             if kind in _DELTA_SPH_KINDS:
                 self.delta_sph_arrays.update([eq.dest] + list(eq.sources or []))
             if kind in _EDAC_KINDS:
                 self.edac_arrays.update([eq.dest] + list(eq.sources or []))
+            if kind in _GASD_KINDS:
+                self.gasd_arrays.update([eq.dest] + list(eq.sources or []))
+                if kind == _GASD_DENSITY_KIND and vals[3]:
+                    self.gasd_iterating.append(eq)
+                if kind == _GASD_GHOST_KIND:
+                    owner.orig_idx_arrays.add(eq.dest)
             dprops = _columns(arrays[eq.dest], dprops)
-            if kind == _UPDATE_H_KIND:
+            if kind in _WRITES_H_KINDS and (kind != _GASD_DENSITY_KIND or vals[3]):
                 owner.outputs_exact[eq.dest].add('h')      # (the tables' 'h' is an input everywhere else)
             ce = self.ceqs[i]
             ce.kind = kind
@@ -330,6 +338,12 @@ class _BuiltinUnit(object):
     def _check(self, ev):
         """m_mat and gradrho are computed per evaluation for the rows a rank holds; ghost rows (a slab's Remote
         particles, periodic or mirror images) would need gradrho carried to them between the passes"""
+        for name in sorted(self.gasd_arrays):
+            if getattr(self._arrays[name], 'slab_decomposed', False):
+                raise NotImplementedError(
+                    "gas-dynamics equations on array '%s': not supported on a slab-decomposed array -- the smoothing "
+                    "length is an unknown of the evaluation, and the halo messages carry no h / omega / alpha / e set "
+                    "between the density iterations; stale values are not computed with" % name)
         for name in sorted(self.edac_arrays):
             if getattr(self._arrays[name], 'slab_decomposed', False):
                 raise NotImplementedError(
@@ -347,7 +361,7 @@ class _BuiltinUnit(object):
                     % (name, ' (ghosts managed by %s)' % owner if owner else ''))
 
     def run(self, ev, t, dt, phase=0):
-        if self.delta_sph_arrays or self.edac_arrays:
+        if self.delta_sph_arrays or self.edac_arrays or self.gasd_arrays:
             self._check(ev)
         self.cg.phase = phase
         try:
@@ -355,6 +369,17 @@ class _BuiltinUnit(object):
                 ev.ctx._h, C.byref(ev.ckernel), C.byref(self.cg), t, dt))
         finally:
             self.cg.phase = 0
+        self.read_convergence(ev)
+
+    def read_convergence(self, ev):
+        """``equation_has_converged`` of the iterating density equations from the word the last ``sph_eval_group``
+        call left (one word per call: every equation of the call gets the same answer, and an iterated group
+        needs all of them to have converged)"""
+        if self.gasd_iterating:
+            flag = C.c_int(0)
+            dev._check(ev.lib.sph_gasd_unconverged(ev.ctx._h, C.byref(flag)))
+            for eq in self.gasd_iterating:
+                eq.equation_has_converged = -1 if flag.value else 1
 
 
 class _GeneratedUnit(object):
@@ -491,6 +516,7 @@ class _CGroup(object):
         self.outputs_exact = defaultdict(set)  # generated families: exactly the written properties
         self.units = []
         self.rigid_arrays = set()         # arrays whose per-body state the group reads or writes
+        self.orig_idx_arrays = set()      # arrays whose orig_idx column MPMUpdateGhostProps reads
         self.moments = {}                 # RigidBodyMoments equation -> its unit: run in place of the reduce hook
         self.eos_absorbed_by = None       # annotate_plan: the pair group after this Tait-EOS group that may run the EOS itself
         self.absorbs_eos = False          # ... and that pair group's side of it
@@ -602,7 +628,7 @@ class _CGroup(object):
                         u.cg.src_eos = 1
             return
         for u in self.units:
-            if u.delta_sph_arrays or u.edac_arrays:
+            if u.delta_sph_arrays or u.edac_arrays or u.gasd_arrays:
                 u._check(ev)
         if getattr(self, '_combined', None) is None:
             self._combined = self._combined_group()
@@ -622,8 +648,14 @@ class _CGroup(object):
         cg.phase = 0
         dev._check(ev.lib.sph_eval_group(
             ev.ctx._h, C.byref(ev.ckernel), C.byref(cg), t, dt))
+        for u in self.units:
+            u.read_convergence(ev)
 
 
+_GASD_KINDS = (34, 35, 36, 37, 38, 39)    # gas dynamics: density sweep, ideal-gas EOS, MPM accelerations, the two h equations, ghost p / cs
+_GASD_GHOST_KIND = 39
+_GASD_DENSITY_KIND = 34
+_WRITES_H_KINDS = (29, 34, 37, 38)    # UpdateSmoothingLengthFerrari; the iterating density sweep; scale h; h from the volume
 _EDAC_KINDS = (30, 31, 32, 33)        # average pressure, the two pressure gradients, the pressure rate
 _DELTA_SPH_KINDS = (22, 23, 24, 25)   # moment matrix, gradient correction, gradrho pre-step, delta-SPH continuity
 _UPDATE_H_KIND = 29             # SPH_EQ_UPDATE_H_FERRARI
@@ -804,6 +836,7 @@ class HipAccelerationEval(object):
         self.lib = self.ctx.lib
         self.sync = sync
         self.nnps = None
+        self.iteration_counts = {}
         k = a_eval.kernel
         self.ckernel = dev.SphKernel(kernel_id(k), int(k.dim), float(k.fac),
                                      float(k.radius_scale),
@@ -827,6 +860,12 @@ class HipAccelerationEval(object):
         self.rigid_arrays = set()
         for cg in self._leaves(self.plan):
             self.rigid_arrays.update(cg.rigid_arrays)
+            for name in cg.orig_idx_arrays:
+                # orig_idx is an integer column of the host array (GasDScheme.setup_properties): it gets a device
+                # column here, once -- the images the domain manager makes are copies of their rows and carry it on
+                dev.prop_register('orig_idx')
+                if 'orig_idx' in self.arrays[name].properties and not self.helpers[name].managed:
+                    self.helpers[name].push('orig_idx')
             for n, p in cg.inputs.items():
                 self.inputs[n].update(p)
             for n, p in cg.outputs.items():
@@ -860,7 +899,7 @@ class HipAccelerationEval(object):
         # what no unit of the evaluation may run with is refused before the first launch of any of them
         for cg in self._leaves(self.plan):
             for u in cg.units:
-                if getattr(u, 'edac_arrays', None):
+                if getattr(u, 'edac_arrays', None) or getattr(u, 'gasd_arrays', None):
                     u._check(self)
         if self.sync == 'auto':
             self.push_inputs()
@@ -949,13 +988,27 @@ class HipAccelerationEval(object):
             return
         if g.iterate:
             count = 1
-            while True:
-                self._run_once(g, item, t, dt)
-                done = self._converged(g)
-                if count >= g.min_iterations and \
-                        (done or count == g.max_iterations):
-                    break
-                count += 1
+            # the second and later passes of ONE iterated group repeat the previous call with nothing but the group and
+            # its neighbour update in between: what option gasd_skip relies on (sphhip.h).  Only a group that holds
+            # NOTHING but iterating density equations qualifies: any other equation in it could write positions,
+            # velocities, masses or h between two sweeps
+            repeats = not isinstance(item, list) and bool(item.units) and g.pre is None and g.post is None \
+                and all(isinstance(u, _BuiltinUnit) and len(u.gasd_iterating) == len(u.eqs) for u in item.units) \
+                and not any(hasattr(eq, 'py_initialize') or hasattr(eq, 'reduce') for eq in g.equations)
+            try:
+                while True:
+                    self._run_once(g, item, t, dt)
+                    done = self._converged(g)
+                    if count >= g.min_iterations and \
+                            (done or count == g.max_iterations):
+                        break
+                    count += 1
+                    if repeats and count == 2:
+                        self.ctx.set_option('gasd_repeat', 1)
+            finally:
+                if repeats and count >= 2:
+                    self.ctx.set_option('gasd_repeat', 0)
+            self.iteration_counts[g.name] = count    # of the last evaluation, per iterated group
         else:
             self._run_once(g, item, t, dt)
 

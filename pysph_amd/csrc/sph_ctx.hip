@@ -137,7 +137,7 @@ int sph_ctx_destroy(sph_ctx *c)
         A.keys.release(); A.keys_sorted.release(); A.idx.release(); A.perm.release();
         A.tile_key.release(); A.tile_id.release(); A.tile_order.release();
         A.dlist.release(); A.dl_cnt.release(); A.ctile_key.release(); A.ctile_id.release(); A.ctile_order.release();
-        A.cell_start.release(); A.fkeys_sorted.release(); A.fine_start.release(); A.tflag.release();
+        A.cell_start.release(); A.fkeys_sorted.release(); A.fine_start.release(); A.tflag.release(); A.gasd_araw.release();
         A.g_keys.release(); A.g_fkeys.release(); A.g_perm.release(); A.g_fine_start.release(); A.g_cell_start.release();
     }
     {
@@ -376,6 +376,8 @@ int sph_set_option(sph_ctx *c, const char *key, long value)
     if (strcmp(key, "nl_reuse") == 0) { c->nl_reuse = value; c->nl.valid = false; return SPH_OK; }
     if (strcmp(key, "norm_masks") == 0) { c->norm_masks = value; return SPH_OK; }
     if (strcmp(key, "row_lds") == 0) { c->row_lds = value; return SPH_OK; }
+    if (strcmp(key, "gasd_skip") == 0) { c->gasd_skip = value; return SPH_OK; }
+    if (strcmp(key, "gasd_repeat") == 0) { c->gasd_repeat = value; return SPH_OK; }
     if (strcmp(key, "fill_holes") == 0) { c->fill_holes = value ? 1 : 0; return SPH_OK; }
     if (strcmp(key, "dest_list") == 0) { c->dest_list = value < 0 ? 0 : (value > 2 ? 2 : value); c->nnps_valid = false; return SPH_OK; }
     if (strcmp(key, "merge_arrays") == 0) { c->merge_arrays = value ? 1 : 0; c->nnps_valid = false; return SPH_OK; }
@@ -460,8 +462,8 @@ int sph_timer_get(sph_ctx *c, const char *key, double *ms, long *count)
 {
     static const char *names[T_COUNT] = {"nnps", "pack", "eos", "pair", "stage",
                                          "pair_none", "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad", "pair_elastic",
-                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure",
-                                         "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep", "n_eos_absorbed"};
+                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure", "pair_gasd_density", "pair_gasd_mpm",
+                                         "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep", "n_eos_absorbed", "n_gasd_skipped"};
     SPH_TRY(timer_drain(c));
     for (int i = 0; i < T_COUNT; i++)
         if (strcmp(key, names[i]) == 0) {

@@ -216,6 +216,28 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
     case SPH_EQ_UPDATE_H_FERRARI: // wc/basic.py:459-463; par dim1 (= 1 / dim) hdx
         a.q[SPH_H][i] = a.par[1] * pow(a.q[SPH_M][i] / a.rho[i], a.par[0]);
         break;
+    case SPH_EQ_IDEAL_GAS_EOS: { // gas_dynamics/basic.py:228-230; par gamma
+        const double r = a.rho[i], p = (a.par[0] - 1.0) * r * a.q[SPH_E][i];
+        a.p[i] = p;
+        a.cs[i] = sqrt(a.par[0] * p / r);
+        break;
+    }
+    case SPH_EQ_SCALE_SMOOTHING_LENGTH: // gas_dynamics/basic.py:18-19; par factor
+        a.q[SPH_H][i] = a.q[SPH_H][i] * a.par[0];
+        break;
+    case SPH_EQ_UPDATE_H_FROM_VOLUME: // gas_dynamics/basic.py:28-29; par k dim1 (= 1 / dim)
+        a.q[SPH_H][i] = a.par[0] * pow(a.q[SPH_M][i] / a.rho[i], a.par[1]);
+        break;
+    case SPH_EQ_MPM_UPDATE_GHOST_PROPS: { // gas_dynamics/basic.py:492-497; par[0] = the array's real rows, par[1] = the column of orig_idx
+        const size_t n_real = (size_t)a.par[0];
+        if (i < n_real) break;            // (tag == Ghost: the rows behind the real ones)
+        const double oi = a.q[(int)a.par[1]][i];
+        if (!(oi >= 0.0 && oi < (double)n_real)) break; // a row whose orig_idx names no real row is left alone
+        const size_t idx = (size_t)oi;
+        a.p[i] = a.p[idx];
+        a.cs[i] = a.cs[idx];
+        break;
+    }
     }
 }
 
@@ -1525,6 +1547,214 @@ template <class T> struct FamAvgP_T {
     }
 };
 
+// ---- gas dynamics (pysph/sph/gas_dynamics/basic.py) -------------------------------------------------------------
+// The geometry of a pair at ONE smoothing length: WI / DWI / GHI of the reference are the kernel at the
+// destination's own h, DWJ at the source's (equation.py:214-224), where `gij` holds the pair at HIJ.  Under uniform h
+// the three lengths are one and `gij` is returned as it is.
+template <int KK, bool UH, class T, class A>
+__device__ __forceinline__ void pair_geom_at(PairGeomT<T> &g, const PairGeomT<T> &gij, T h, const A &a)
+{
+    g = gij;
+    if (!UH) {
+        g.hij = h;
+        g.h1 = SphKernel<KK>::CUTOFF ? T(1) / h : fast_rcp(h);
+        g.fac = kernel_norm((T)a.k.sigma, g.h1, a.k.dim);
+        g.q = g.rij * g.h1;
+    }
+}
+
+// SummationDensity (:74-219): the sums rho, arho, grhox..z, dwdh with WI / DWI / GHI and, in finish(), the whole
+// post_loop -- one Newton-Raphson step for h of every particle that has not converged, the 0.8 / 1.2 clamp, the
+// fallback, the convergence test and the group's convergence word -- in ONE launch.  The post_loop runs in fp64 whatever
+// the arithmetic of the sums.  A particle that converged in an EARLIER iteration is summed again every iteration and
+// leaves with the raw arho (its post_loop block is skipped); one that converges in this launch leaves with arho * omega:
+// the reference's behaviour, kept.  The new h goes to the property column only: the records every wavefront reads were
+// packed before the launch.  Records [x y z h | m u v w].
+enum { F_GSD = 1 };
+template <class T> struct FamGasSD_T {
+    typedef T Real;
+    static constexpr bool PRED = true; // every sum carries WI, DWI or GHI, masked for a pair outside the criterion
+    static constexpr uint32_t CF0 = F_GSD;
+    static constexpr int MINB = 4;
+    static constexpr int NA = 4; // m u v w
+    static constexpr int NR = 8;
+    static constexpr bool WAVE_SKIP = true;
+    struct Params {
+        double dim, k, htol;
+        int iterate, once;     // density_iterations, iterate_only_once
+        int skip;              // option gasd_skip in a repeated call: wavefronts without an unconverged destination leave early
+        double *araw;          // ... the raw arho of every row, as the last full sweep summed it (null: not kept)
+        const double *m, *h0;
+        double *h, *rho, *arho, *grhox, *grhoy, *grhoz, *dwdh, *div, *omega, *ah, *converged;
+        uint32_t *flag;        // the convergence word: 1 = some particle has not converged; flag[1]: wavefronts skipped
+    };
+    struct Dest { T u, v, w, rho, arho, gx, gy, gz, dwdh; };
+    // Option gasd_skip: with positions, velocities, masses and its own h unchanged since the previous sweep, a converged
+    // particle's sums come out the same again; what the reference's re-summation changes is arho (raw again, where the
+    // sweep in which the particle converged left arho * omega) and div.  The wave-tile kernel only.
+    template <class A> static __device__ __forceinline__ bool wave_skip(const A &a, uint32_t o, bool active)
+    {
+        if (!a.p.skip) return false;
+        if (!__all(!active || a.p.converged[o] == 1.0)) return false;
+        if ((threadIdx.x & 63) == 0) atomicAdd(a.p.flag + 1, 1u); // wavefronts that left here ("n_gasd_skipped")
+        if (active) {
+            const double ar = a.p.araw[o];
+            a.p.arho[o] = ar;
+            a.p.div[o] = -ar / a.p.rho[o];
+        }
+        return true;
+    }
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        D.u = a[1]; D.v = a[2]; D.w = a[3];
+        D.rho = D.arho = D.gx = D.gy = D.gz = D.dwdh = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        PairGeomT<T> gij, g;
+        pair_geom<KK, UH>(gij, pi, pj, r2, a);
+        pair_geom_at<KK, UH>(g, gij, pi.w, a);
+        T wi = pair_w<KK, UH>(g), tg = pair_gradfac<KK, UH>(g), ghi = pair_gradh<KK, UH>(g, a.k.dim);
+        wi = pass ? wi : T(0.0); tg = pass ? tg : T(0.0); ghi = pass ? ghi : T(0.0);
+        const T mj = s[0];
+        const T dw0 = tg * g.xij[0], dw1 = tg * g.xij[1], dw2 = tg * g.xij[2];
+        const T vijdotdwij = (D.u - s[1]) * dw0 + (D.v - s[2]) * dw1 + (D.w - s[3]) * dw2;
+        D.rho += mj * wi;
+        D.arho += mj * vijdotdwij;
+        D.gx += mj * dw0; D.gy += mj * dw1; D.gz += mj * dw2;
+        D.dwdh += mj * ghi;
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        const double rho = (double)D.rho, dwdh = (double)D.dwdh;
+        double arho = (double)D.arho;
+        if (a.p.araw) a.p.araw[o] = arho;
+        if (a.p.iterate && !(a.p.converged[o] == 1.0)) { // :150-213
+            const double mi = a.p.m[o], hi = a.p.h[o], hi0 = a.p.h0[o];
+            const double rhoi = mi / pow(hi / a.p.k, a.p.dim);
+            const double dhdrhoi = -hi / (a.p.dim * rho);
+            double omegai = 1.0 - dhdrhoi * dwdh;
+            if (omegai < 0) omegai = 1.0;
+            const double gradhi = 1.0 / omegai;
+            a.p.omega[o] = gradhi;
+            const double func = rhoi - rho, dfdh = omegai / dhdrhoi;
+            double hnew = hi - func / dfdh;
+            if (hnew > 1.2 * hi) hnew = 1.2 * hi;
+            else if (hnew < 0.8 * hi) hnew = 0.8 * hi;
+            if (hnew <= 1e-6 || gradhi < 1e-6) hnew = a.p.k * pow(mi / rho, 1.0 / a.p.dim);
+            const double diff = fabs(hnew - hi) / hi0;
+            if (!((diff < a.p.htol && omegai > 0) || a.p.once)) {
+                *a.p.flag = 1u; // the same constant from every lane that fails; the host reads the word once per call
+                a.p.h[o] = hnew;
+                a.p.converged[o] = 0.0;
+            } else {
+                arho *= gradhi;
+                a.p.ah[o] = arho * dhdrhoi;
+                a.p.converged[o] = 1.0;
+            }
+        }
+        a.p.rho[o] = rho;
+        a.p.arho[o] = arho;
+        a.p.grhox[o] = (double)D.gx; a.p.grhoy[o] = (double)D.gy; a.p.grhoz[o] = (double)D.gz;
+        a.p.dwdh[o] = dwdh;
+        a.p.div[o] = -arho / rho;
+    }
+};
+
+// MPMAccelerations (:356-483): everything its loop does in one sweep -- the grad-h pressure terms with DWI and DWJ (each
+// at its own h), the artificial viscosity and its heating under dot <= 0, the thermal conduction with the signal
+// velocity sqrt(|p_i - p_j| / RHOIJ), del2e and dt_cfl -- and the post_loop's sources of alpha1 / alpha2.  XIJ is
+// normalised (zeroed below RIJ = 1e-8) AFTER the kernel gradients were formed from it, as in the reference, so Fij is
+// the normalised XIJ against DWIJ at HIJ; the self pair adds to dt_cfl only.
+// Records [x y z h | u v w rho p cs e m omega alpha1 alpha2 -]: 128 B in fp64 (eight 16-B pieces), 64 B in fp32.
+enum { F_MPM = 1 };
+template <class T> struct FamMPM_T {
+    typedef T Real;
+    static constexpr bool PRED = true; // the sums carry a kernel gradient, masked outside the criterion; dt_cfl is selected
+    static constexpr uint32_t CF0 = F_MPM;
+    static constexpr int MINB = 3;
+    static constexpr int NA = 12; // u v w rho p cs e m omega alpha1 alpha2 pad
+    static constexpr int NR = 16;
+    struct Params {
+        T beta;
+        double sigma, alpha1_min, alpha2_min;
+        int update_alpha1, update_alpha2;
+        const double *h, *cs, *e, *div, *alpha1, *alpha2;
+        double *au, *av, *aw, *ae, *del2e, *dt_cfl, *aalpha1, *aalpha2;
+    };
+    struct Dest {
+        T u, v, w, rho, p, cs, e, al1, al2, pwi; // pwi = p_i / rho_i^2 omega_i
+        T au, av, aw, ae, del2e, dtc;
+    };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[3]; D.p = a[4]; D.cs = a[5]; D.e = a[6];
+        D.al1 = a[9]; D.al2 = a[10];
+        D.pwi = a[4] / (a[3] * a[3]) * a[8];
+        D.au = D.av = D.aw = D.ae = D.del2e = D.dtc = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        PairGeomT<T> g, gi, gj;
+        pair_geom<KK, UH>(g, pi, pj, r2, a);
+        pair_geom_at<KK, UH>(gi, g, pi.w, a);
+        pair_geom_at<KK, UH>(gj, g, pj.w, a);
+        T tij = pair_gradfac<KK, UH>(g), ti = pair_gradfac<KK, UH>(gi), tj = pair_gradfac<KK, UH>(gj);
+        tij = pass ? tij : T(0.0); ti = pass ? ti : T(0.0); tj = pass ? tj : T(0.0);
+        const T mj = s[7], rhoj = s[3];
+        const T pjw = s[4] / (rhoj * rhoj) * s[8]; // p_j / rho_j^2 omega_j
+        const T cij = T(0.5) * (D.cs + s[5]);
+        // :412-420: the normalised interaction vector
+        const T rn = g.rij < T(1e-8) ? T(0.0) : g.rinv;
+        const T x0 = g.xij[0] * rn, x1 = g.xij[1] * rn, x2 = g.xij[2] * rn;
+        const T v0 = D.u - s[0], v1 = D.v - s[1], v2 = D.w - s[2];
+        const T dot = v0 * x0 + v1 * x1 + v2 * x2;
+        const T dwij0 = tij * g.xij[0], dwij1 = tij * g.xij[1], dwij2 = tij * g.xij[2];
+        const T Fij = x0 * dwij0 + x1 * dwij1 + x2 * dwij2;
+        const T rhoij1 = fast_rcp(T(0.5) * (D.rho + rhoj)); // 1 / RHOIJ
+        const T pdiff = fabs(D.p - s[4]);
+        const T vsig1 = T(0.5) * raw_max(T(2.0) * cij - a.p.beta * dot, T(0.0));
+        const T vsig2 = sqrt(pdiff * rhoij1);
+        const T cfl = cij + a.p.beta * dot;
+        D.dtc = (pass && cfl > D.dtc) ? cfl : D.dtc;
+        if (dot <= T(0.0)) { // :437-447
+            const T alpha1 = T(0.5) * (D.al1 + s[9]);
+            const T tmpv = mj * rhoij1 * alpha1 * vsig1 * dot;
+            D.au += tmpv * dwij0; D.av += tmpv * dwij1; D.aw += tmpv * dwij2;
+            D.ae += T(-0.5) * tmpv * dot * Fij;
+        }
+        // :455-461: the grad-h terms, DWI at h_i and DWJ at h_j
+        const T gsum = D.pwi * ti + pjw * tj;
+        D.au -= mj * gsum * g.xij[0]; D.av -= mj * gsum * g.xij[1]; D.aw -= mj * gsum * g.xij[2];
+        const T vijdotdwi = ti * (v0 * g.xij[0] + v1 * g.xij[1] + v2 * g.xij[2]);
+        D.ae += mj * D.pwi * vijdotdwi;
+        // :463-469: conduction and the Laplacian of e
+        const T alpha2 = T(0.5) * (D.al2 + s[10]);
+        const T eij = D.e - s[6];
+        D.ae += mj * rhoij1 * alpha2 * vsig2 * eij * Fij;
+        D.del2e += mj / rhoj * eij * fast_rcp(g.rij + g.eps) * Fij;
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        a.p.au[o] = (double)D.au; a.p.av[o] = (double)D.av; a.p.aw[o] = (double)D.aw; a.p.ae[o] = (double)D.ae;
+        const double del2e = (double)D.del2e;
+        a.p.del2e[o] = del2e;
+        a.p.dt_cfl[o] = (double)D.dtc;
+        double aa1 = 0.0, aa2 = 0.0; // :471-483
+        if (a.p.update_alpha1 || a.p.update_alpha2) {
+            const double hi = a.p.h[o];
+            const double tau = hi / (a.p.sigma * a.p.cs[o]);
+            if (a.p.update_alpha1) aa1 = (a.p.alpha1_min - a.p.alpha1[o]) / tau + fmax(-a.p.div[o], 0.0);
+            if (a.p.update_alpha2) aa2 = (a.p.alpha2_min - a.p.alpha2[o]) / tau + 0.01 * hi * fabs(del2e) / sqrt(a.p.e[o]);
+        }
+        a.p.aalpha1[o] = aa1; a.p.aalpha2[o] = aa2;
+    }
+};
+
 // ---- velocity gradient (basic_equations.py:63-148) -------------------------
 template <class T> struct FamVGrad_T {
     typedef T Real; // arithmetic type of the pair loop
@@ -1776,7 +2006,8 @@ static bool is_nosrc_kind(int k)
 {
     return k == SPH_EQ_TAIT_EOS || k == SPH_EQ_TAIT_EOS_HG || k == SPH_EQ_TVF_STATE_EQUATION ||
            k == SPH_EQ_ISOTHERMAL_EOS || k == SPH_EQ_SOLID_ISOTHERMAL_EOS || k == SPH_EQ_MONAGHAN_ART_STRESS ||
-           k == SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE || k == SPH_EQ_UPDATE_H_FERRARI;
+           k == SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE || k == SPH_EQ_UPDATE_H_FERRARI || k == SPH_EQ_IDEAL_GAS_EOS ||
+           k == SPH_EQ_SCALE_SMOOTHING_LENGTH || k == SPH_EQ_UPDATE_H_FROM_VOLUME || k == SPH_EQ_MPM_UPDATE_GHOST_PROPS;
 }
 
 static int need_prop(sph_ctx *c, int id, int prop, const char *who)
@@ -1795,8 +2026,21 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     EosArgs a;
     a.kind = e.kind;
     memcpy(a.par, e.par, sizeof a.par);
-    if (e.kind == SPH_EQ_UPDATE_H_FERRARI) { // reads m and rho, writes h
-        for (int p : {SPH_RHO, SPH_M, SPH_H}) SPH_TRY(need_prop(c, e.dest, p, "UpdateSmoothingLengthFerrari"));
+    const bool writes_h = e.kind == SPH_EQ_UPDATE_H_FERRARI || e.kind == SPH_EQ_SCALE_SMOOTHING_LENGTH || e.kind == SPH_EQ_UPDATE_H_FROM_VOLUME;
+    if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS) {
+        const int po = sph_prop_register("orig_idx");
+        if (po < 0) return po;
+        SPH_TRY(need_prop(c, e.dest, po, "MPMUpdateGhostProps (orig_idx)"));
+        SPH_TRY(need_prop(c, e.dest, SPH_P, "MPMUpdateGhostProps (p)"));
+        SPH_TRY(need_prop(c, e.dest, SPH_CS, "MPMUpdateGhostProps (cs)"));
+        a.par[0] = (double)A.n_real;
+        a.par[1] = (double)po;
+        if (start < A.n_real) start = A.n_real; // nothing to do on the real rows
+        if (stop <= start) return SPH_OK;
+    } else if (e.kind == SPH_EQ_SCALE_SMOOTHING_LENGTH) {
+        SPH_TRY(need_prop(c, e.dest, SPH_H, "ScaleSmoothingLength"));
+    } else if (writes_h) { // reads m and rho, writes h
+        for (int p : {SPH_RHO, SPH_M, SPH_H}) SPH_TRY(need_prop(c, e.dest, p, "UpdateSmoothingLengthFerrari / FromVolume"));
     } else if (e.kind != SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE) { // (reads v_ij, s_ij and G only: alone in a group, rho and p are not on the device)
         SPH_TRY(need_prop(c, e.dest, SPH_RHO, "EOS"));
         SPH_TRY(sph_array_ensure_prop(c, e.dest, SPH_P));
@@ -1804,7 +2048,8 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     a.rho = A.prop[SPH_RHO];
     a.p = A.prop[SPH_P];
     a.cs = nullptr;
-    if (e.kind == SPH_EQ_TAIT_EOS || e.kind == SPH_EQ_TAIT_EOS_HG) {
+    if (e.kind == SPH_EQ_IDEAL_GAS_EOS) SPH_TRY(need_prop(c, e.dest, SPH_E, "IdealGasEOS"));
+    if (e.kind == SPH_EQ_TAIT_EOS || e.kind == SPH_EQ_TAIT_EOS_HG || e.kind == SPH_EQ_IDEAL_GAS_EOS) {
         SPH_TRY(sph_array_ensure_prop(c, e.dest, SPH_CS));
         a.cs = A.prop[SPH_CS];
     }
@@ -1823,6 +2068,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     for (int k = 0; k < SPH_PROP_COUNT; k++) a.q[k] = A.prop[k];
     a.rho = A.prop[SPH_RHO];
     a.p = A.prop[SPH_P];
+    if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS) a.cs = A.prop[SPH_CS];
     a.tflag = nullptr;
     if (e.kind == SPH_EQ_MONAGHAN_ART_STRESS) {
         // "no particle in tension" for the rates kernel: valid when this launch covers every particle of the array
@@ -1833,7 +2079,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     }
     ScopedTimer tm(c, T_EOS);
     hipLaunchKernelGGL(k_nosrc, dim3(div_up(stop - start, 256)), dim3(256), 0, c->stream, a);
-    if (e.kind == SPH_EQ_UPDATE_H_FERRARI) {
+    if (writes_h) {
         // h changed behind the neighbour grid: the next sph_nnps_update looks at the values again, and until then no
         // pair loop may take "every particle has the h the last update saw" as a launch constant or a record layout
         sph_mark_written(A, SPH_H);
@@ -1842,7 +2088,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     return SPH_OK;
 }
 
-enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP };
+enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP, FAM_GASSD, FAM_MPM };
 
 static bool is_wcsph_option_kind(int k)
 {
@@ -1862,6 +2108,8 @@ static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false
     case SPH_EQ_EDAC_MOM_PRESSURE: *flag = F_EP | F_EINT; return FAM_EDAC;
     case SPH_EQ_EDAC: *flag = F_EDAC; return FAM_EDAC;
     case SPH_EQ_EDAC_AVG_PRESSURE: *flag = F_AVGP; return FAM_AVGP;
+    case SPH_EQ_GASD_SUMMATION_DENSITY: *flag = F_GSD; return FAM_GASSD;
+    case SPH_EQ_MPM_ACCELERATIONS: *flag = F_MPM; return FAM_MPM;
     default: break;
     }
     if (edac && !elastic) {
@@ -1959,6 +2207,17 @@ static PackPlan pack_plan(int fam)
         p.nr = 6;
         p.na = 2;
         p.props[0] = SPH_M; p.props[1] = SPH_P;
+    } else if (fam == FAM_GASSD) {
+        p.nr = 8;
+        p.na = 4;
+        int pr[4] = {SPH_M, SPH_U, SPH_V, SPH_W};
+        for (int k = 0; k < 4; k++) p.props[k] = pr[k];
+    } else if (fam == FAM_MPM) { // omega, alpha1, alpha2: user properties by name (run_mpm refuses the launch should the slots have run out)
+        p.nr = 16;
+        p.na = 12;
+        int pr[12] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_E, SPH_M, sph_prop_register("omega"),
+                      sph_prop_register("alpha1"), sph_prop_register("alpha2"), -1};
+        for (int k = 0; k < 12; k++) p.props[k] = pr[k];
     } else if (fam == FAM_NBR) {
         p.nr = FamNbr::NR;
         p.na = 1;
@@ -2017,6 +2276,7 @@ static bool slot_required(int fam, uint32_t flags, int prop)
         return true;
     }
     if (fam == FAM_AVGP) return prop == SPH_M ? (flags & (F_SD | F_TVFSD)) != 0 : (flags & F_AVGP) != 0;
+    if (fam == FAM_GASSD || fam == FAM_MPM) return true;
     return false;
 }
 
@@ -2629,6 +2889,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
 {
     if (!c || !K || !g) { sph_set_error("sph_eval_group: NULL argument"); return SPH_ERR_ARG; }
     c->cur_dt = dt;
+    c->gasd_unconverged = 0;
     if (g->neq > SPH_MAX_EQS) { sph_set_error("sph_eval_group: too many equations"); return SPH_ERR_ARG; }
     SPH_TRY(check_kernel("sph_eval_group", K));
     HIP_TRY(hipSetDevice(c->device));
@@ -3195,6 +3456,77 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
             a.p.pavg = D.prop[ppavg]; a.p.nnbr = D.prop[pnn];
             return launch_pair<F>(c, K->kind, a);
         };
+        // the gas-dynamics density sweep: when it iterates, the convergence word is cleared before the launch and read
+        // back behind it (one word, one synchronise per call), and h counts as written
+        auto run_gassd = [&](auto tag) -> int {
+            typedef decltype(tag) F;
+            PairArgs<F> a;
+            memset(&a, 0, sizeof a);
+            common(a);
+            const sph_equation *se = eq_of[SPH_EQ_GASD_SUMMATION_DENSITY]; // par dim k htol density_iterations iterate_only_once
+            a.p.dim = se->par[0]; a.p.k = se->par[1]; a.p.htol = se->par[2];
+            a.p.iterate = se->par[3] != 0.0; a.p.once = se->par[4] != 0.0;
+            const char *names[5] = {"grhox", "grhoy", "grhoz", "dwdh", "div"};
+            int ids[5];
+            for (int k = 0; k < 5; k++) { ids[k] = sph_prop_register(names[k]); if (ids[k] < 0) return ids[k]; }
+            SPH_TRY(ensure_out(c, dst, {SPH_RHO, SPH_ARHO, ids[0], ids[1], ids[2], ids[3], ids[4]}));
+            a.p.rho = D.prop[SPH_RHO]; a.p.arho = D.prop[SPH_ARHO];
+            a.p.grhox = D.prop[ids[0]]; a.p.grhoy = D.prop[ids[1]]; a.p.grhoz = D.prop[ids[2]];
+            a.p.dwdh = D.prop[ids[3]]; a.p.div = D.prop[ids[4]];
+            if (a.p.iterate) {
+                const int ph0 = sph_prop_register("h0"), pom = sph_prop_register("omega"), pah = sph_prop_register("ah"),
+                          pcv = sph_prop_register("converged");
+                if (ph0 < 0 || pom < 0 || pah < 0 || pcv < 0) return SPH_ERR_ARG;
+                SPH_TRY(need_prop(c, dst, ph0, "SummationDensity of gas dynamics (h0)"));
+                SPH_TRY(need_prop(c, dst, pcv, "SummationDensity of gas dynamics (converged)"));
+                SPH_TRY(need_prop(c, dst, SPH_M, "SummationDensity of gas dynamics (m)"));
+                SPH_TRY(ensure_out(c, dst, {pom, pah}));
+                a.p.m = D.prop[SPH_M]; a.p.h0 = D.prop[ph0]; a.p.h = D.prop[SPH_H];
+                a.p.omega = D.prop[pom]; a.p.ah = D.prop[pah]; a.p.converged = D.prop[pcv];
+                if (c->gasd_skip && c->pair_variant == 6) {
+                    // the raw arho of every row is kept by every sweep; a repeated call may use what the previous one kept
+                    const bool had = D.gasd_araw.ptr && D.gasd_araw.bytes >= D.n * sizeof(double);
+                    SPH_TRY(D.gasd_araw.reserve(D.n * sizeof(double), true, c->stream));
+                    a.p.araw = D.gasd_araw.as<double>();
+                    a.p.skip = c->gasd_repeat && had;
+                }
+                SPH_TRY(c->gen_state.reserve(SPH_GEN_MAX_STATE * sizeof(double)));
+                a.p.flag = c->gen_state.as<uint32_t>();
+                HIP_TRY(hipMemsetAsync(a.p.flag, 0, 2 * sizeof(uint32_t), c->stream));
+            }
+            SPH_TRY(launch_pair<F>(c, K->kind, a));
+            if (a.p.iterate) {
+                uint32_t word[2] = {0, 0};
+                HIP_TRY(hipMemcpyAsync(word, a.p.flag, sizeof word, hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+                c->gasd_unconverged |= word[0];
+                c->timers[T_N_GASD_SKIP].count += word[1];
+                // h changed behind the neighbour grid (as UpdateSmoothingLengthFerrari in run_nosrc)
+                sph_mark_written(D, SPH_H);
+                c->uniform_h = false;
+            }
+            return SPH_OK;
+        };
+        auto run_mpm = [&](auto tag) -> int {
+            typedef decltype(tag) F;
+            PairArgs<F> a;
+            memset(&a, 0, sizeof a);
+            common(a);
+            const sph_equation *me = eq_of[SPH_EQ_MPM_ACCELERATIONS]; // par beta sigma alpha1_min alpha2_min update_alpha1 update_alpha2
+            a.p.beta = me->par[0]; a.p.sigma = me->par[1]; a.p.alpha1_min = me->par[2]; a.p.alpha2_min = me->par[3];
+            a.p.update_alpha1 = me->par[4] != 0.0; a.p.update_alpha2 = me->par[5] != 0.0;
+            const int pa1 = sph_prop_register("alpha1"), pa2 = sph_prop_register("alpha2"), paa1 = sph_prop_register("aalpha1"),
+                      paa2 = sph_prop_register("aalpha2"), pd2 = sph_prop_register("del2e"), pdv = sph_prop_register("div"),
+                      pom = sph_prop_register("omega");
+            if (pa1 < 0 || pa2 < 0 || paa1 < 0 || paa2 < 0 || pd2 < 0 || pdv < 0 || pom < 0) return SPH_ERR_ARG; // (the records carry omega, alpha1, alpha2)
+            SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW, SPH_AE, SPH_DT_CFL, paa1, paa2, pd2}));
+            if (a.p.update_alpha1) SPH_TRY(need_prop(c, dst, pdv, "MPMAccelerations (div)"));
+            a.p.h = D.prop[SPH_H]; a.p.cs = D.prop[SPH_CS]; a.p.e = D.prop[SPH_E]; a.p.div = D.prop[pdv];
+            a.p.alpha1 = D.prop[pa1]; a.p.alpha2 = D.prop[pa2];
+            a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW]; a.p.ae = D.prop[SPH_AE];
+            a.p.del2e = D.prop[pd2]; a.p.dt_cfl = D.prop[SPH_DT_CFL]; a.p.aalpha1 = D.prop[paa1]; a.p.aalpha2 = D.prop[paa2];
+            return launch_pair<F>(c, K->kind, a);
+        };
         const bool f32 = c->arith_f32 != 0;
         const bool g7 = tait_gk(g->eos_par[2]) == 3; // the usual exponent: kernels that fold it
         if (fam == FAM_WCSPH && eosf && umass && g7) SPH_TRY(f32 ? run_wcsph(FamWCSPHE_T<float, true>()) : run_wcsph(FamWCSPHE_T<double, true>()));
@@ -3208,6 +3540,8 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         else if (fam == FAM_DSPRE) SPH_TRY(f32 ? run_dspre(FamDSPre_T<float>()) : run_dspre(FamDSPre_T<double>()));
         else if (fam == FAM_DENSITY) SPH_TRY(f32 ? run_density(FamDensity_T<float>()) : run_density(FamDensity()));
         else if (fam == FAM_AVGP) SPH_TRY(f32 ? run_avgp(FamAvgP_T<float>()) : run_avgp(FamAvgP_T<double>()));
+        else if (fam == FAM_GASSD) SPH_TRY(f32 ? run_gassd(FamGasSD_T<float>()) : run_gassd(FamGasSD_T<double>()));
+        else if (fam == FAM_MPM) SPH_TRY(f32 ? run_mpm(FamMPM_T<float>()) : run_mpm(FamMPM_T<double>()));
         else if (fam == FAM_EDAC && (dflags & F_EINT)) SPH_TRY(f32 ? run_edac(FamEDAC_T<float, true>()) : run_edac(FamEDAC_T<double, true>()));
         else if (fam == FAM_EDAC) SPH_TRY(f32 ? run_edac(FamEDAC_T<float, false>()) : run_edac(FamEDAC_T<double, false>()));
         else if (fam == FAM_VGRAD) SPH_TRY(f32 ? run_vgrad(FamVGrad_T<float>()) : run_vgrad(FamVGrad()));
@@ -3218,6 +3552,13 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
     }
     if (eos_pending) SPH_TRY(run_pending_eos(c, g)); // (no destination came as far as its records)
     HIP_TRY(hipGetLastError());
+    return SPH_OK;
+}
+
+extern "C" int sph_gasd_unconverged(sph_ctx *c, int *flag)
+{
+    if (!c || !flag) { sph_set_error("sph_gasd_unconverged: NULL argument"); return SPH_ERR_ARG; }
+    *flag = c->gasd_unconverged ? 1 : 0;
     return SPH_OK;
 }
 
@@ -3576,6 +3917,8 @@ UNIT_BOTH(UNIT_PAIR, FamWCSPH_T);
 UNIT_BOTH(UNIT_PAIR, FamDensity_T);
 UNIT_BOTH(UNIT_PAIR, FamTVF_T);
 UNIT_BOTH(UNIT_PAIR, FamAvgP_T);
+UNIT_BOTH(UNIT_PAIR, FamGasSD_T);
+UNIT_BOTH(UNIT_PAIR, FamMPM_T);
 template <class T> using FamEDACInt_T = FamEDAC_T<T, true>;
 template <class T> using FamEDACExt_T = FamEDAC_T<T, false>;
 UNIT_BOTH(UNIT_PAIR, FamEDACInt_T);

@@ -12,6 +12,7 @@ struct StageArgs {
     double dt;
     size_t n;
     int ip0, iap; // EDAC steppers: the user properties p0 and ap
+    int gd[10];   // GasDFluidStep: h0 ah converged omega alpha1 alpha2 alpha10 alpha20 aalpha1 aalpha2
     double *p[SPH_PROP_COUNT];
 };
 
@@ -97,6 +98,36 @@ __global__ __launch_bounds__(256) void k_stage(StageArgs a)
             }
             p[SPH_P][i] = p[a.ip0][i] + f * p[a.iap][i];
         }
+    } else if (a.stepper == SPH_STEP_GASD) {
+        enum { H0, AH, CONV, OMEGA, AL1, AL2, AL10, AL20, AAL1, AAL2 };
+        const int *g = a.gd;
+        if (a.stage == 0) { // integrator_step.py:353-378
+            p[SPH_X0][i] = p[SPH_X][i]; p[SPH_Y0][i] = p[SPH_Y][i]; p[SPH_Z0][i] = p[SPH_Z][i];
+            p[SPH_U0][i] = p[SPH_U][i]; p[SPH_V0][i] = p[SPH_V][i]; p[SPH_W0][i] = p[SPH_W][i];
+            p[SPH_E0][i] = p[SPH_E][i];
+            p[g[H0]][i] = p[SPH_H][i];
+            p[SPH_RHO0][i] = p[SPH_RHO][i];
+            p[g[CONV]][i] = 0.0;  // no particle has converged at the beginning of an evaluation
+            p[g[OMEGA]][i] = 1.0; // the grad-h factor until the density iteration sets it
+            p[g[AL10]][i] = p[g[AL1]][i];
+            p[g[AL20]][i] = p[g[AL2]][i];
+        } else { // stage1 :380-407 (dt/2), stage2 :409-428 (dt)
+            const double f = a.stage == 1 ? dtb2 : dt;
+            const double u = p[SPH_U0][i] + f * p[SPH_AU][i];
+            const double v = p[SPH_V0][i] + f * p[SPH_AV][i];
+            const double w = p[SPH_W0][i] + f * p[SPH_AW][i];
+            p[SPH_U][i] = u; p[SPH_V][i] = v; p[SPH_W][i] = w;
+            p[SPH_X][i] = p[SPH_X0][i] + f * u;
+            p[SPH_Y][i] = p[SPH_Y0][i] + f * v;
+            p[SPH_Z][i] = p[SPH_Z0][i] + f * w;
+            p[SPH_E][i] = p[SPH_E0][i] + f * p[SPH_AE][i];
+            if (a.stage == 1) { // h and rho are predicted for a faster convergence of the next density iteration
+                p[SPH_H][i] = p[g[H0]][i] + f * p[g[AH]][i];
+                p[SPH_RHO][i] = p[SPH_RHO0][i] + f * p[SPH_ARHO][i];
+            }
+            p[g[AL1]][i] = p[g[AL10]][i] + f * p[g[AAL1]][i];
+            p[g[AL2]][i] = p[g[AL20]][i] + f * p[g[AAL2]][i];
+        }
     }
 }
 
@@ -126,8 +157,20 @@ extern "C" int sph_integrate_stage(sph_ctx *c, int id, int stepper, int stage, d
                        SPH_AU, SPH_AV, SPH_AW, SPH_AX, SPH_AY, SPH_AZ, iap, -1};
     const int et1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_P, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, ip0,
                        SPH_AU, SPH_AV, SPH_AW, SPH_UHAT, SPH_VHAT, SPH_WHAT, SPH_AUHAT, SPH_AVHAT, SPH_AWHAT, iap, -1};
+    int gd[10] = {}, gd0[32], gd1[40];
+    if (stepper == SPH_STEP_GASD) {
+        const char *names[10] = {"h0", "ah", "converged", "omega", "alpha1", "alpha2", "alpha10", "alpha20", "aalpha1", "aalpha2"};
+        for (int k = 0; k < 10; k++) { gd[k] = sph_prop_register(names[k]); if (gd[k] < 0) return SPH_ERR_ARG; }
+        const int b0[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_E, SPH_H, SPH_RHO, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0,
+                          SPH_E0, SPH_RHO0, gd[0], gd[2], gd[3], gd[4], gd[5], gd[6], gd[7], -1};
+        const int b1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_E, SPH_H, SPH_RHO, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0,
+                          SPH_E0, SPH_RHO0, SPH_AU, SPH_AV, SPH_AW, SPH_AE, SPH_ARHO, gd[0], gd[1], gd[4], gd[5], gd[6], gd[7], gd[8], gd[9], -1};
+        memcpy(gd0, b0, sizeof b0);
+        memcpy(gd1, b1, sizeof b1);
+    }
     const int *need = nullptr;
-    if (stepper == SPH_STEP_EDAC) need = stage == 0 ? ed0 : ed1;
+    if (stepper == SPH_STEP_GASD) need = stage == 0 ? gd0 : gd1;
+    else if (stepper == SPH_STEP_EDAC) need = stage == 0 ? ed0 : ed1;
     else if (stepper == SPH_STEP_EDAC_TVF) need = stage == 0 ? ed0 : et1;
     else if (stepper == SPH_STEP_WCSPH) need = stage == 0 ? wc0 : wc1;
     else if (stepper == SPH_STEP_SOLID_MECH) need = stage == 0 ? sm0 : sm1;
@@ -137,9 +180,11 @@ extern "C" int sph_integrate_stage(sph_ctx *c, int id, int stepper, int stage, d
     if (A.n_real == 0) return SPH_OK;
     StageArgs a;
     a.stepper = stepper; a.stage = stage; a.dt = dt; a.n = A.n_real; a.ip0 = ip0; a.iap = iap;
+    for (int k = 0; k < 10; k++) a.gd[k] = gd[k];
     for (int k = 0; k < SPH_PROP_COUNT; k++) a.p[k] = A.prop[k];
     ScopedTimer tm(c, T_STAGE);
     hipLaunchKernelGGL(k_stage, dim3(div_up(A.n_real, 256)), dim3(256), 0, c->stream, a);
     if (stepper == SPH_STEP_TVF ? stage == 1 : stage > 0) c->nnps_valid = false; // positions moved
+    if (stepper == SPH_STEP_GASD && stage == 1) { sph_mark_written(A, SPH_H); c->uniform_h = false; } // h predicted: the next neighbour update looks at it
     return SPH_OK;
 }

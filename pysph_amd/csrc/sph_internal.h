@@ -93,6 +93,7 @@ struct DevArray {
     // "no particle of this array is in tension": a device word the artificial-stress kernel (k_nosrc) sets to 1 when
     // any r_ij is non-zero; valid while that kernel covered every particle and nothing wrote r_ij since
     DevBuf tflag;
+    DevBuf gasd_araw;                    // gas-dynamics density iteration: the raw (unscaled) arho of every row (option gasd_skip)
     bool tflag_valid = false;
     double *spare = nullptr;             // one more property-sized buffer: the compaction of sph_halo_remove_selected rotates through it
     size_t spare_cap = 0;                // ... holding this many doubles
@@ -135,7 +136,7 @@ struct RigidState {
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
 // T_N_*: launch counters only (no time): pair launches on EOS-fused records, launches that kept / reused neighbour lists
 // T_N_INTERP_MOM / _SWEEP: moment passes / property sweeps of sph_interpolate
-enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 11, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_COUNT };
+enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 13, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_N_GASD_SKIP, T_COUNT };
 
 struct Timer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -281,6 +282,9 @@ struct sph_ctx {
     long tile_block_rows = 8; // destination tiles are traversed in blocks of this many cell rows (y) through all z planes; 0: memory order
     long row_mod3 = 3;        // the pair kernel visits a wavefront's 3x3 rows of cells in (y mod 3, z mod 3) order (PairArgs::row_mod3)
     double cur_dt = 0.0;    // dt of the sph_eval_group call being set up
+    long gasd_skip = 0;     // wavefronts of an iterating density sweep whose destinations have all converged skip their neighbour work
+    long gasd_repeat = 0;   // ... the host says: this call repeats the previous one inside an iterated group (nothing else ran in between)
+    uint32_t gasd_unconverged = 0; // the last sph_eval_group call: an iterating gas-dynamics density sweep left particles unconverged
     DevBuf csr_start[SPH_MAX_ARRAYS], csr_nbrs[SPH_MAX_ARRAYS]; // neighbour lists of generated loop_all families
     unsigned long long pack_epoch = 0;
     long pack_group = 0;    // 1 between the per-destination sph_eval_group calls of one host group (records shared)

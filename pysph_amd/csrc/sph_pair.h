@@ -155,6 +155,11 @@ template <class F> struct fam_token<F, decltype((void)F::TOKEN)> { static conste
 template <class F, class = void> struct fam_eosf { static constexpr bool value = false; };
 template <class F> struct fam_eosf<F, decltype((void)F::EOSF)> { static constexpr bool value = F::EOSF; };
 
+// does the family let a whole wavefront leave before any neighbour work (Fam::wave_skip(a, o, active): wave-uniform; it
+// writes what the skipped lanes owe)?  (the gas-dynamics density iteration: 64 destinations that have all converged)
+template <class F, class = void> struct fam_wave_skip { static constexpr bool value = false; };
+template <class F> struct fam_wave_skip<F, decltype((void)F::WAVE_SKIP)> { static constexpr bool value = F::WAVE_SKIP; };
+
 // does the family's pair() also take the neighbour's position in the packed buffers?  (generated transposed
 // families: a hit whose ORIGINAL index lies outside the forward loop's destination range is dropped there)
 template <class F, class = void> struct fam_pair_index { static constexpr bool value = false; };
@@ -482,6 +487,9 @@ __global__ __launch_bounds__(64 * WPB, Fam::MINB) void k_pair_wave(PairArgs<Fam>
         active = valid && o >= (uint32_t)rg && o < (uint32_t)(rg >> 32);
     } else {
         active = valid && o >= a.d_start && o < a.d_stop;
+    }
+    if constexpr (fam_wave_skip<Fam>::value) {
+        if (Fam::wave_skip(a, o, active)) return;
     }
     const uint32_t fkey = a.d_fkeys[ic];
     const uint32_t key = fkey / SPH_NSUB;

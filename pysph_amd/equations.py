@@ -308,6 +308,12 @@ EQ_EDAC_AVG_PRESSURE = 30
 EQ_EDAC_MOMENTUM = 31
 EQ_EDAC_MOM_PRESSURE = 32
 EQ_EDAC = 33
+EQ_GASD_SUMMATION_DENSITY = 34
+EQ_IDEAL_GAS_EOS = 35
+EQ_MPM_ACCELERATIONS = 36
+EQ_SCALE_SMOOTHING_LENGTH = 37
+EQ_UPDATE_H_FROM_VOLUME = 38
+EQ_MPM_UPDATE_GHOST_PROPS = 39
 
 _XV = ('x', 'y', 'z', 'h')
 EQUATION_TABLE = OrderedDict([
@@ -402,11 +408,29 @@ EQUATION_TABLE = OrderedDict([
         EQ_EDAC, ('cs', 'nu', 'rho0'),
         _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V', 'ap'),
         _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'V'))),
+    # Gas dynamics (pysph_amd/gas_dynamics.py, pysph/sph/gas_dynamics/basic.py).  Its SummationDensity is the third class
+    # of that name: `resolve_equation` finds it by module under the key 'GasDSummationDensity'.  The iterating form
+    # also writes h (acceleration_eval._WRITES_H_KINDS).
+    ('GasDSummationDensity', (
+        EQ_GASD_SUMMATION_DENSITY, ('dim', 'k', 'htol', 'density_iterations', 'iterate_only_once'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'arho', 'grhox', 'grhoy', 'grhoz', 'dwdh', 'div', 'omega', 'h0', 'ah', 'converged'),
+        _XV + ('u', 'v', 'w', 'm'))),
+    ('IdealGasEOS', (EQ_IDEAL_GAS_EOS, ('gamma',), ('rho', 'e', 'p', 'cs'), ())),
+    ('MPMAccelerations', (
+        EQ_MPM_ACCELERATIONS, ('beta', 'sigma', 'alpha1_min', 'alpha2_min', 'update_alpha1', 'update_alpha2'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'cs', 'e', 'omega', 'alpha1', 'alpha2', 'div', 'au', 'av', 'aw', 'ae',
+               'del2e', 'dt_cfl', 'aalpha1', 'aalpha2'),
+        _XV + ('u', 'v', 'w', 'm', 'rho', 'p', 'cs', 'e', 'omega', 'alpha1', 'alpha2'))),
+    ('ScaleSmoothingLength', (EQ_SCALE_SMOOTHING_LENGTH, ('factor',), ('h',), ())),
+    ('UpdateSmoothingLengthFromVolume', (EQ_UPDATE_H_FROM_VOLUME, ('k', 'dim1'), ('h', 'm', 'rho'), ())),
+    # (the two parameters are the library's own: the real rows and the column of orig_idx)
+    ('MPMUpdateGhostProps', (EQ_MPM_UPDATE_GHOST_PROPS, (), ('p', 'cs', 'orig_idx'), ())),
 ])
 
 # equations that have no neighbour loop
 NO_SOURCE_KINDS = (EQ_TAIT_EOS, EQ_TAIT_EOS_HG, EQ_TVF_STATE_EQUATION,
-                   EQ_ISOTHERMAL_EOS, 17, 19, 21, EQ_UPDATE_H_FERRARI)
+                   EQ_ISOTHERMAL_EOS, 17, 19, 21, EQ_UPDATE_H_FERRARI, EQ_IDEAL_GAS_EOS, EQ_SCALE_SMOOTHING_LENGTH,
+                   EQ_UPDATE_H_FROM_VOLUME, EQ_MPM_UPDATE_GHOST_PROPS)
 
 
 def resolve_equation(eq):
@@ -422,6 +446,9 @@ def resolve_equation(eq):
         # EDAC's own classes of these names (wc/edac.py:301, :389), this package's or the reference's
         if name in ('MomentumEquation', 'MomentumEquationPressureGradient'):
             name = 'EDAC' + name
+    if name == 'SummationDensity' and 'gas_dynamics' in type(eq).__module__:
+        # the third class of this name (gas_dynamics/basic.py:74), this package's or the reference's
+        name = 'GasDSummationDensity'
     if name not in EQUATION_TABLE:
         try:   # the elastic family registers itself on import
             from . import solid_mech  # noqa: F401

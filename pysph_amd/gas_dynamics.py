@@ -1,0 +1,215 @@
+"""Compressible gas dynamics for the HIP backend.
+
+Mirrors the interface of pysph/sph/gas_dynamics/basic.py and ``GasDScheme`` of pysph/sph/scheme.py:884-1141
+(Sod tubes, blast waves, Sedov, Kelvin-Helmholtz):
+
+* the equation classes ``SummationDensity`` (basic.py:74-219), ``IdealGasEOS`` (:222-230), ``MPMAccelerations``
+  (:356-483), ``ScaleSmoothingLength`` (:13-19) and ``UpdateSmoothingLengthFromVolume`` (:22-29) are parameter
+  holders with the reference's constructor signatures and defaults: their bodies are the hand-written families
+  ``FamGasSD_T`` / ``FamMPM_T`` and three cases of ``k_nosrc`` in csrc/sph_eval.hip.
+  ``SummationDensity`` is the third class of that name next to basic_equations' and transport_velocity's;
+  ``equations.resolve_equation`` finds it by the module name (``'gas_dynamics' in type(eq).__module__``), for this
+  class and for the reference's own;
+* ``SummationDensity(density_iterations=True)`` under ``Group(update_nnps=True, iterate=True)`` solves the smoothing
+  length of every particle by Newton-Raphson, one neighbour update and one sweep per iteration.  The sweep leaves one
+  device word, which the evaluator turns into ``equation_has_converged`` (-1 / 1) behind every launch: ``converged()``
+  is what the iterated group asks, as in the reference;
+* ``MPMUpdateGhostProps`` (:486-497), which ``GasDScheme(has_ghosts=True)`` puts in a ``real=False`` group, copies
+  ``p`` and ``cs`` of every row behind the real ones from the row ``orig_idx`` names.  ``orig_idx`` gets a device
+  column when the evaluator is set up; the periodic / mirror images of ``HipDomainManager`` are copies of their rows,
+  so they carry the right value, and every domain update hands them the current ``h, rho, omega, alpha*, e``;
+* ``GasDScheme`` gives the reference's group list for ``adaptive_h_scheme='mpm'`` and ``'gsph'``; ``solids`` are
+  refused at construction (running the reference's ``WallBoundary`` through the translator was not attempted);
+* ``GasDFluidStep`` lives in ``pysph_amd.integrator``, ``get_particle_array_gasd`` in ``pysph_amd.particle_array``.
+"""
+import numpy as np
+
+from .equations import Equation, Group
+from .integrator import GasDFluidStep, PECIntegrator
+from .particle_array import GASD_PROPS, get_npy, get_particle_array_gasd  # noqa: F401
+
+
+class ScaleSmoothingLength(Equation):
+    """gas_dynamics/basic.py:13-19: ``h *= factor``."""
+
+    def __init__(self, dest, sources, factor=2.0):
+        super(ScaleSmoothingLength, self).__init__(dest, sources)
+        self.factor = factor
+
+
+class UpdateSmoothingLengthFromVolume(Equation):
+    """gas_dynamics/basic.py:22-29: ``h = k (m / rho)^(1 / dim)``."""
+
+    def __init__(self, dest, sources, dim, k=1.2):
+        super(UpdateSmoothingLengthFromVolume, self).__init__(dest, sources)
+        self.k = k
+        self.dim1 = 1. / dim
+
+
+class SummationDensity(Equation):
+    """gas_dynamics/basic.py:74-219: density, its rate, its gradient and dW/dh with the destination's own h, and
+    with ``density_iterations`` one Newton-Raphson step for h per evaluation of the group."""
+
+    def __init__(self, dest, sources, dim, density_iterations=False,
+                 iterate_only_once=False, k=1.2, htol=1e-6):
+        self.density_iterations = density_iterations
+        self.iterate_only_once = iterate_only_once
+        self.dim = dim
+        self.k = k
+        self.htol = htol
+        # 1: converged; the evaluator writes -1 behind a sweep that left a particle unconverged
+        self.equation_has_converged = 1
+        super(SummationDensity, self).__init__(dest, sources)
+
+    def converged(self):
+        return self.equation_has_converged
+
+
+class IdealGasEOS(Equation):
+    """gas_dynamics/basic.py:222-230: ``p = (gamma - 1) rho e``, ``cs = sqrt(gamma p / rho)``."""
+
+    def __init__(self, dest, sources, gamma):
+        self.gamma = gamma
+        self.gamma1 = gamma - 1.0
+        super(IdealGasEOS, self).__init__(dest, sources)
+
+
+class MPMAccelerations(Equation):
+    """gas_dynamics/basic.py:356-483: grad-h momentum and energy rates with artificial viscosity, artificial
+    conduction and the sources of the two switches."""
+
+    def __init__(self, dest, sources, beta=2.0, update_alpha1=False,
+                 update_alpha2=False, alpha1_min=0.1, alpha2_min=0.1,
+                 sigma=0.1):
+        self.beta = beta
+        self.sigma = sigma
+        self.update_alpha1 = update_alpha1
+        self.update_alpha2 = update_alpha2
+        self.alpha1_min = alpha1_min
+        self.alpha2_min = alpha2_min
+        super(MPMAccelerations, self).__init__(dest, sources)
+
+
+class MPMUpdateGhostProps(Equation):
+    """gas_dynamics/basic.py:486-497: ``p`` and ``cs`` of an image row from the row it mirrors (``orig_idx``)."""
+
+    def __init__(self, dest, sources=None, dim=2):
+        super(MPMUpdateGhostProps, self).__init__(dest, sources)
+        self.dim = dim
+
+
+class GasDScheme(object):
+    """scheme.py:884-1141."""
+
+    def __init__(self, fluids, solids, dim, gamma, kernel_factor, alpha1=1.0,
+                 alpha2=0.1, beta=2.0, adaptive_h_scheme='mpm',
+                 update_alpha1=False, update_alpha2=False,
+                 max_density_iterations=250,
+                 density_iteration_tolerance=1e-3, has_ghosts=False):
+        if list(solids):
+            raise NotImplementedError(
+                'GasDScheme(solids=%r): the WallBoundary equation of gas_dynamics/boundary_equations.py has '
+                'not been run through this backend (not attempted); stale wall values are not computed with' % (list(solids),))
+        if adaptive_h_scheme not in ('mpm', 'gsph'):
+            raise ValueError("adaptive_h_scheme must be 'mpm' or 'gsph', not %r" % (adaptive_h_scheme,))
+        self.fluids = list(fluids)
+        self.solids = list(solids)
+        self.dim = dim
+        self.solver = None
+        self.integrator = None
+        self.kernel = None
+        self.gamma = gamma
+        self.alpha1 = alpha1
+        self.alpha2 = alpha2
+        self.update_alpha1 = update_alpha1
+        self.update_alpha2 = update_alpha2
+        self.beta = beta
+        self.kernel_factor = kernel_factor
+        self.adaptive_h_scheme = adaptive_h_scheme
+        self.density_iteration_tolerance = density_iteration_tolerance
+        self.max_density_iterations = max_density_iterations
+        self.has_ghosts = has_ghosts
+
+    def configure(self, **kw):
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise RuntimeError('Parameter %s not defined for %s.' % (k, type(self).__name__))
+            setattr(self, k, v)
+
+    def get_stepper_class(self):
+        return GasDFluidStep
+
+    def configure_solver(self, kernel=None, integrator_cls=None,
+                         extra_steppers=None, **kw):
+        """:985-1024: the kernel (Gaussian by default), one ``GasDFluidStep`` per fluid, a PEC integrator unless
+        another class is given.  The integrator is kept in ``self.integrator`` (this package has no ``Solver``;
+        ``integrator.setup_integrator`` installs it)."""
+        from .kernels import Gaussian
+        if kernel is None:
+            kernel = Gaussian(dim=self.dim)
+        steppers = {}
+        if extra_steppers is not None:
+            steppers.update(extra_steppers)
+        cls = integrator_cls if integrator_cls is not None else PECIntegrator
+        step_cls = self.get_stepper_class()
+        for name in self.fluids:
+            if name not in steppers:
+                steppers[name] = step_cls()
+        self.kernel = kernel
+        self.integrator = cls(**steppers)
+        self.solver_args = dict(kw)
+        return self.integrator
+
+    def get_integrator(self):
+        if self.integrator is None:
+            self.configure_solver()
+        return self.integrator
+
+    def get_equations(self):
+        """:1026-1120."""
+        equations = []
+        if self.adaptive_h_scheme == 'mpm':
+            g1 = [SummationDensity(dest=fluid, sources=self.fluids, k=self.kernel_factor,
+                                   density_iterations=True, dim=self.dim,
+                                   htol=self.density_iteration_tolerance) for fluid in self.fluids]
+            equations.append(Group(equations=g1, update_nnps=True, iterate=True,
+                                   max_iterations=self.max_density_iterations))
+        else:
+            equations.append(Group(
+                equations=[ScaleSmoothingLength(dest=fluid, sources=None, factor=2.0) for fluid in self.fluids],
+                update_nnps=True))
+            equations.append(Group(
+                equations=[SummationDensity(dest=fluid, sources=self.fluids, dim=self.dim) for fluid in self.fluids],
+                update_nnps=False))
+            equations.append(Group(
+                equations=[UpdateSmoothingLengthFromVolume(dest=fluid, sources=None, k=self.kernel_factor,
+                                                           dim=self.dim) for fluid in self.fluids],
+                update_nnps=True))
+            equations.append(Group(
+                equations=[SummationDensity(dest=fluid, sources=self.fluids, dim=self.dim) for fluid in self.fluids],
+                update_nnps=False))
+        equations.append(Group(equations=[IdealGasEOS(dest=fluid, sources=None, gamma=self.gamma)
+                                          for fluid in self.fluids]))
+        equations.append(Group(equations=[]))          # the (empty) wall group of the reference's list
+        if self.has_ghosts:
+            equations.append(Group(equations=[MPMUpdateGhostProps(dest=fluid, sources=None) for fluid in self.fluids],
+                                   real=False))
+        equations.append(Group(equations=[
+            MPMAccelerations(dest=fluid, sources=self.fluids + self.solids, alpha1_min=self.alpha1,
+                             alpha2_min=self.alpha2, beta=self.beta, update_alpha1=self.update_alpha1,
+                             update_alpha2=self.update_alpha2) for fluid in self.fluids]))
+        return equations
+
+    def setup_properties(self, particles, clean=True):
+        """:1122-1141 (properties are added; none is removed)."""
+        arrays = dict((pa.name, pa) for pa in particles)
+        for fluid in self.fluids:
+            pa = arrays[fluid]
+            for p in GASD_PROPS:
+                if p not in pa.properties:
+                    pa.add_property(p)
+            if 'orig_idx' not in pa.properties:
+                pa.add_property('orig_idx', type='int')
+            get_npy(pa, 'orig_idx')[:] = np.arange(pa.get_number_of_particles())
+            pa.set_output_arrays(['x', 'y', 'u', 'v', 'rho', 'm', 'h', 'cs', 'p', 'e', 'au', 'av', 'ae', 'pid', 'gid',
+                                  'tag', 'dwdh', 'alpha1', 'alpha2'])

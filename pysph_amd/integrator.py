@@ -63,10 +63,19 @@ class EDACTVFStep(IntegratorStep):
     _kind = STEP_EDAC_TVF
 
 
+STEP_GASD = 8
+
+
+class GasDFluidStep(IntegratorStep):
+    """integrator_step.py:351-428: predictor-corrector for gas dynamics; ``initialize`` also clears ``converged`` and
+    sets ``omega`` to 1 for the density iteration, ``stage1`` predicts ``h`` and ``rho``."""
+    _kind = STEP_GASD
+
+
 # (the two rigid-body steppers are classes of pysph_amd.rigid_body; their stages need the array's body state)
 _STEP_KINDS = {'WCSPHStep': STEP_WCSPH, 'TransportVelocityStep': STEP_TVF,
                'RK2StepRigidBody': STEP_RIGID_RK2, 'EulerStepRigidBody': STEP_RIGID_EULER,
-               'EDACStep': STEP_EDAC, 'EDACTVFStep': STEP_EDAC_TVF}
+               'EDACStep': STEP_EDAC, 'EDACTVFStep': STEP_EDAC_TVF, 'GasDFluidStep': STEP_GASD}
 
 
 def stepper_kind(step):

@@ -17,7 +17,7 @@ New here:
   ceil(len(props) / 4) sweeps; ``interpolate(prop)`` is its one-property case.
   With ``pull=False`` nothing comes back to the host: the results stay on the
   device as properties of ``self.pa`` named ``ip0, ip1, ...`` (user property
-  slots, of which a process has 96 -- ``pull=True`` takes none) -- property k of
+  slots, of which a process has 128 -- ``pull=True`` takes none) -- property k of
   the list is ``ip<k>``, for ``'order1'`` its value and gradient are
   ``ip<4k> .. ip<4k+3>`` -- and their names are returned.
 * ``ctx=`` shares a ``HipContext`` with a running simulation.  ``sync=True``

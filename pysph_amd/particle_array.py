@@ -295,6 +295,20 @@ def get_particle_array_edac_solid(constants=None, **props):
     return pa
 
 
+GASD_PROPS = ('x', 'y', 'z', 'u', 'v', 'w', 'rho', 'h', 'm', 'cs', 'p', 'e', 'au', 'av', 'aw', 'arho', 'ae', 'am', 'ah',
+              'x0', 'y0', 'z0', 'u0', 'v0', 'w0', 'rho0', 'e0', 'h0', 'div', 'dt_cfl', 'grhox', 'grhoy', 'grhoz', 'dwdh',
+              'omega', 'converged', 'alpha1', 'alpha10', 'aalpha1', 'alpha2', 'alpha20', 'aalpha2', 'del2e')
+
+
+def get_particle_array_gasd(constants=None, **props):
+    """pysph/base/utils.py:360-400; ``h0`` starts as ``h`` (the density iteration divides by it)."""
+    pa = get_particle_array(constants=constants, additional_props=GASD_PROPS, **props)
+    get_npy(pa, 'h0')[:] = get_npy(pa, 'h')
+    pa.set_output_arrays(['x', 'y', 'u', 'v', 'rho', 'm', 'h', 'cs', 'p', 'e', 'au', 'av', 'ae', 'pid', 'gid', 'tag',
+                          'dwdh', 'alpha1', 'alpha2'])
+    return pa
+
+
 RIGID_BODY_PROPS = ['au', 'av', 'aw', 'V', 'fx', 'fy', 'fz', 'x0', 'y0', 'z0',
                     'tang_disp_x', 'tang_disp_y', 'tang_disp_z', 'tang_disp_x0', 'tang_disp_y0', 'tang_disp_z0',
                     'tang_velocity_x', 'tang_velocity_y', 'rad_s', 'tang_velocity_z', 'nx', 'ny', 'nz']
