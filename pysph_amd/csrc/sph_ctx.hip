@@ -120,8 +120,6 @@ int sph_ctx_create(int device, void *stream, sph_ctx **out)
         c->own_stream = true;
     }
     HIP_TRY(hipHostMalloc((void **)&c->pinned, 64 * sizeof(double), hipHostMallocDefault));
-    // development aid: SPH_PAIR_VARIANT overrides the default pair-kernel schedule
-    if (const char *pv = getenv("SPH_PAIR_VARIANT")) c->pair_variant = atol(pv);
     *out = c;
     return SPH_OK;
 }

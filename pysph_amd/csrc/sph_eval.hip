@@ -2245,6 +2245,48 @@ static PackPlan pack_plan(int fam)
     return p;
 }
 
+// The packed records of one (destination, sources) block.  choose_records decides them for a destination of
+// sph_eval_group; the callers that are fp64 by contract (neighbour lists, the interpolator) start from RecordLayout(fam),
+// whatever the options say.  pack_array, the pack cache, fill_common and the choice of the family instantiation read the
+// decision from here and from nowhere else.
+enum RecordKind {
+    REC_PLAIN, // the family's own records (PackPlan; compact under uniform h where pack_layout has a layout for them)
+    REC_EOSF,  // 64-byte WCSPH records, uniform h: p and cs recomputed per record (sph_group.src_eos)
+    REC_EOSV,  // 64-byte WCSPH records with variable h [x y z h u v w rho], one mass per source array
+    REC_TVFF,  // state-fused TVF records: p and V recomputed from rho
+    REC_ELU,   // elastic-rates records without h and m (uniform h, one mass per source array)
+};
+struct RecordLayout {
+    PackPlan pl;             // nr: doubles per record (floats with record_f32 / arith_f32)
+    bool record_f32 = false; // the precision, as the options of these names: fp32 records read by fp64 arithmetic ...
+    bool arith_f32 = false;  // ... fp32 records, arithmetic and accumulators
+    RecordKind kind = REC_PLAIN;
+    bool umass = false;      // REC_EOSF: p / rho^2 in the mass slot (every source array has one mass)
+    bool eos_abs = false;    // REC_EOSF / REC_EOSV: the pack computes the Tait EOS that has not run (PackArgs::eos_abs) ...
+    double eos_par[4] = {};  // ... with these parameters: rho0 c0 gamma p0
+    explicit RecordLayout(int fam) : pl(pack_plan(fam)) {}
+    bool eos_fused() const { return kind == REC_EOSF || kind == REC_EOSV; }
+    // what the pack cache compares: records packed under another signature cannot be reused
+    int sig() const
+    {
+        return pl.nr * 32 + (record_f32 ? 1 : 0) + (arith_f32 ? 2 : 0) + (kind == REC_EOSF ? 4 : 0) + (umass ? 8 : 0) +
+               (kind == REC_TVFF || kind == REC_ELU || kind == REC_EOSV ? 16 : 0);
+    }
+};
+
+// PackArgs::layout of these records
+static int pack_layout(const RecordLayout &rl, int fam, bool wave)
+{
+    static const int special[] = {0, 6, 12, 8, 10}; // by RecordKind, in fp64; the fp32 form of each is the next number
+    if (rl.kind != REC_PLAIN) return special[rl.kind] + (rl.arith_f32 ? 1 : 0);
+    if (!wave) return 0;
+    if (rl.record_f32 || rl.arith_f32) return 5;
+    if (fam == FAM_WCSPH) return 1;
+    if ((fam == FAM_DENSITY || fam == FAM_NBR) && rl.pl.nr == 4) return 2;
+    if ((fam == FAM_TVF || fam == FAM_EDAC) && (rl.pl.nr == 14 || rl.pl.nr == 12)) return 3;
+    return 0;
+}
+
 // which aux slots a family really needs given the union of flags (others may be absent -> 0)
 static bool slot_required(int fam, uint32_t flags, int prop)
 {
@@ -2285,17 +2327,9 @@ static bool slot_required(int fam, uint32_t flags, int prop)
 static int pack_pieces(const PackArgs &pa)
 {
     if (!pa.rec) return 0;
-    if (pa.layout == 6) return 4;
-    if (pa.layout == 7) return 2;
-    if (pa.layout == 8) return pa.nr / 2;
-    if (pa.layout == 9) return pa.nr / 4;
-    if (pa.layout == 10) return 10;
-    if (pa.layout == 11) return 5;
-    if (pa.layout == 12) return 4;
-    if (pa.layout == 13) return 2;
-    if (pa.layout == 5) return (pa.nr % 4) ? 0 : pa.nr / 4;
-    if (pa.nr % 2) return 0;
-    return pa.nr / 2;
+    // values per piece: four floats (layout 5 and the odd ones of 7 .. 13) or two doubles
+    const int per = (pa.layout == 5 || (pa.layout >= 7 && pa.layout <= 13 && (pa.layout & 1))) ? 4 : 2;
+    return (pa.nr % per) ? 0 : pa.nr / per;
 }
 
 // `launch` false: validate only (the records of this array are already in the packed buffer, see
@@ -2320,22 +2354,23 @@ static void launch_pack(sph_ctx *c, const PackArgs &pa, size_t n)
     }
 }
 
-static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fam, uint32_t flags, bool dest_only = false,
+static int pack_array(sph_ctx *c, int id, size_t off, const RecordLayout &rl, int fam, uint32_t flags, bool dest_only = false,
                       bool launch = true, int seg = 0)
 {
     DevArray &A = c->arr[id];
+    const PackPlan &pl = rl.pl;
     // seg 0: the particles sph_nnps_update binned, through their cell order; seg 1: the ghosts binned after it
     // (sph_nnps_update_ghosts), through theirs, behind the first segment's records
     const size_t nseg = seg ? A.g_n : A.n_binned;
     if (nseg == 0) return SPH_OK;
     PackArgs pa;
+    memset(&pa, 0, sizeof pa);
     pa.perm = seg ? A.g_perm.as<uint32_t>() : A.perm.as<uint32_t>();
     pa.n = nseg;
     pa.off = off + (seg ? A.n_binned : 0);
     pa.x = A.prop[SPH_X]; pa.y = A.prop[SPH_Y]; pa.z = A.prop[SPH_Z]; pa.h = A.prop[SPH_H];
     pa.na = pl.na;
     for (int k = 0; k < MAX_AUX; k++) {
-        pa.src[k] = nullptr;
         if ((k < pl.na || (pl.derived == 3 && k == 18) || (pl.derived == 4 && k == 4)) && pl.props[k] >= 0) {
             pa.src[k] = A.prop[pl.props[k]];
             // a destination that is not among the sources is only read through Fam::load:
@@ -2349,26 +2384,16 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
     pa.derived = pl.derived;
     pa.posh = c->posh.as<double4>();
     pa.aux = c->aux.as<double>();
-    pa.rec = nullptr;
+    pa.rec = wave_tiles(c) ? c->posh.as<double>() : nullptr;
     pa.nr = pl.nr;
-    pa.fpos = nullptr;
+    pa.fpos = wave_tiles(c) ? c->fposb.as<float4>() : nullptr;
     for (int k = 0; k < 3; k++) pa.gmin[k] = c->xmin[k];
     pa.radius_scale = c->radius_scale;
-    if (c->pair_variant >= 2) pa.rec = c->posh.as<double>();
-    if (c->pair_variant >= 3) pa.fpos = c->fposb.as<float4>();
-    pa.layout = (c->pair_variant >= 3 && fam == FAM_WCSPH) ? 1 : (c->pair_variant >= 3 && (fam == FAM_DENSITY || fam == FAM_NBR) && pl.nr == 4) ? 2
-              : (c->pair_variant >= 3 && (fam == FAM_TVF || fam == FAM_EDAC) && (pl.nr == 14 || pl.nr == 12)) ? 3 : 0;
-    if (c->pair_variant >= 3 && (c->record_f32 || c->arith_f32)) pa.layout = 5;
-    pa.umass = 0;
-    pa.hu = 0.0;
-    pa.eos_abs = 0;
-    for (int k = 0; k < 4; k++) pa.eos_par[k] = 0.0;
-    pa.p_out = pa.cs_out = nullptr;
-    if (c->cur_eosf) {
+    pa.layout = pack_layout(rl, fam, wave_tiles(c));
+    if (rl.kind == REC_EOSF) {
         // p, cs (and p / rho^2) are recomputed by the pair kernel: not read here
-        pa.layout = c->arith_f32 ? 7 : 6;
         pa.src[5] = pa.src[6] = nullptr;
-        if (c->cur_umass) { // ... except p / rho^2, which takes the place of the (uniform) mass: derived 1 reads p
+        if (rl.umass) { // ... except p / rho^2, which takes the place of the (uniform) mass: derived 1 reads p
             pa.umass = 1;
             pa.src[3] = nullptr; // the record holds no mass
         } else {
@@ -2379,20 +2404,18 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
         pa.h = nullptr;
         pa.hu = 0.5 * (c->h_uniform + c->h_uniform);
     }
-    if (c->cur_elu) pa.layout = c->arith_f32 ? 11 : 10; // h and m are launch / source constants
-    if (c->cur_eosv) { // p, cs, p / rho^2 recomputed, m a source constant: none of them read here
-        pa.layout = c->arith_f32 ? 13 : 12;
+    // REC_ELU: h and m are launch / source constants
+    if (rl.kind == REC_EOSV) { // p, cs, p / rho^2 recomputed, m a source constant: none of them read here
         pa.src[3] = pa.src[5] = pa.src[6] = pa.src[7] = nullptr;
         pa.derived = 0;
     }
-    if (c->cur_tvff) { // p and V are functions of rho (and the one mass): not read here
-        pa.layout = c->arith_f32 ? 9 : 8;
+    if (rl.kind == REC_TVFF) { // p and V are functions of rho (and the one mass): not read here
         pa.src[7] = pa.src[8] = pa.src[9] = nullptr;
         pa.derived = 0;
     }
-    if (c->cur_eos_abs && (c->cur_eosf || c->cur_eosv)) { // the Tait EOS of this array has not run: p and cs leave from here
+    if (rl.eos_abs) { // the Tait EOS of this array has not run: p and cs leave from here
         pa.eos_abs = 1;
-        for (int k = 0; k < 4; k++) pa.eos_par[k] = c->cur_eos_par[k];
+        for (int k = 0; k < 4; k++) pa.eos_par[k] = rl.eos_par[k];
         pa.p_out = A.prop[SPH_P];
         pa.cs_out = A.prop[SPH_CS];
         pa.src[7] = nullptr; // p is computed, not read
@@ -2410,11 +2433,12 @@ static int pack_array(sph_ctx *c, int id, size_t off, const PackPlan &pl, int fa
 // which emits nothing but the externally linked *_ext functions below for the families listed at the end of the
 // file.  The primary compile only declares them and forwards ids 5..10.
 // ---------------------------------------------------------------------------
-template <class Fam, int K> static int launch_pair_k(sph_ctx *c, const PairArgs<Fam> &a)
+// rec_f32: an fp64 family reads fp32 records (RecordLayout::record_f32)
+template <class Fam, int K> static int launch_pair_k(sph_ctx *c, const PairArgs<Fam> &a, bool rec_f32)
 {
     const bool uh = c->uniform_h && c->use_uniform_h;
     constexpr bool FP32 = sizeof(typename Fam::Real) == 4;
-    if (c->pair_variant == 6) {
+    if (wave_tiles(c)) {
         dim3 g2(div_up(4 * div_up(a.nd, 256), WPB)), b2(64 * WPB);
         // equation flags as a compile-time constant when every source carries the same set
         uint32_t cf = a.src[0].flags;
@@ -2425,7 +2449,7 @@ template <class Fam, int K> static int launch_pair_k(sph_ctx *c, const PairArgs<
         if (uh) { if (cf == Fam::CF0) LAUNCH6F(true, F32V, Fam::CF0); else LAUNCH6F(true, F32V, 0); }  \
         else { if (cf == Fam::CF0) LAUNCH6F(false, F32V, Fam::CF0); else LAUNCH6F(false, F32V, 0); }
         if constexpr (FP32) { LAUNCH6U(true) }
-        else { if (c->record_f32) { LAUNCH6U(true) } else { LAUNCH6U(false) } }
+        else { if (rec_f32) { LAUNCH6U(true) } else { LAUNCH6U(false) } }
 #undef LAUNCH6U
 #undef LAUNCH6F
         return SPH_OK;
@@ -2484,7 +2508,7 @@ template <class Fam, int K> static int launch_interp_k(sph_ctx *c, const PairArg
     return SPH_OK;
 }
 
-template <class Fam, int K> int launch_pair_ext(sph_ctx *c, const PairArgs<Fam> &a);
+template <class Fam, int K> int launch_pair_ext(sph_ctx *c, const PairArgs<Fam> &a, bool rec_f32);
 template <class Fam, bool UHV, int K> int launch_pair_fused_ext(sph_ctx *c, const PairArgs<Fam> &a);
 template <class Fm, int K> int launch_pair_merged_ext(sph_ctx *c, const PairArgs<Fm> &a);
 template <class Fam, int K> int launch_interp_ext(sph_ctx *c, const PairArgs<Fam> &a);
@@ -2527,11 +2551,11 @@ static int check_kernel(const char *who, const sph_kernel *K)
     default: return bad_kernel_kind(WHO, KK);                         \
     }
 
-template <class Fam> static int launch_pair(sph_ctx *c, int kk, const PairArgs<Fam> &a)
+template <class Fam> static int launch_pair(sph_ctx *c, int kk, const PairArgs<Fam> &a, bool rec_f32)
 {
     if (a.nd == 0) return SPH_OK;
-#define L_(K) launch_pair_k<Fam, K>(c, a)
-#define E_(K) launch_pair_ext<Fam, K>(c, a)
+#define L_(K) launch_pair_k<Fam, K>(c, a, rec_f32)
+#define E_(K) launch_pair_ext<Fam, K>(c, a, rec_f32)
     SPH_KERNEL_SWITCH(kk, "pair loop", L_, E_)
 #undef L_
 #undef E_
@@ -2553,6 +2577,8 @@ template <class Fm> static int launch_pair_merged(sph_ctx *c, int kk, const Pair
 #undef L_
 #undef E_
 }
+// a hand-written family on plain fp64 records, whatever the options say (the interpolator's private density sweep)
+template <class Fam> static int launch_pair_fp64(sph_ctx *c, int kk, const PairArgs<Fam> &a) { return launch_pair<Fam>(c, kk, a, false); }
 template <class Fam> static int interp_launch(sph_ctx *c, int kk, const PairArgs<Fam> &a)
 {
     if (a.nd == 0) return SPH_OK;
@@ -2563,13 +2589,14 @@ template <class Fam> static int interp_launch(sph_ctx *c, int kk, const PairArgs
 #undef E_
 }
 
+// nrec: doubles per packed record of this launch (RecordLayout::pl.nr; floats with fp32 records)
 template <class Fam>
-static void fill_common(sph_ctx *c, PairArgs<Fam> &a, const sph_kernel *K, double t)
+static void fill_common(sph_ctx *c, PairArgs<Fam> &a, const sph_kernel *K, double t, double dt, int nrec)
 {
     a.posh = c->posh.as<double4>();
     a.aux = c->aux.as<double>();
     a.rec = c->posh.as<double>();
-    a.nrec = c->cur_nrec;
+    a.nrec = nrec;
     a.fpos = c->fposb.as<float4>();
     a.dom_extent = fmax(fmax(c->xmax[0] - c->xmin[0], c->xmax[1] - c->xmin[1]), c->xmax[2] - c->xmin[2]);
     for (int k = 0; k < 3; k++) { a.nc[k] = c->nc[k]; a.xmin[k] = c->xmin[k]; }
@@ -2579,7 +2606,7 @@ static void fill_common(sph_ctx *c, PairArgs<Fam> &a, const sph_kernel *K, doubl
     a.k.deltap = K->deltap;
     a.k.dim = K->dim;
     a.t = t;
-    a.dt = c->cur_dt;
+    a.dt = dt;
     a.ablate = (int)c->ablate;
     a.dbg = c->count_iters ? c->dbgc.as<unsigned long long>() : nullptr;
     // uniform-h constants, computed as the general path would per pair
@@ -2605,7 +2632,7 @@ template <class Fam> static void set_tile_order(sph_ctx *c, PairArgs<Fam> &a, co
 // the destinations of this launch are exactly the real particles of D's order: wave tiles from D.dlist (no idle ghost lanes)
 template <class Fam> static void use_dest_list(sph_ctx *c, PairArgs<Fam> &a, const DevArray &D)
 {
-    if (!c->dest_list || c->pair_variant != 6 || D.dlist_n == 0 || a.nl_mode || a.face_mode) return;
+    if (!c->dest_list || !wave_tiles(c) || D.dlist_n == 0 || a.nl_mode || a.face_mode) return;
     a.d_list = D.dlist.as<uint32_t>();
     a.nd = (uint32_t)D.dlist_n;
     c->timers[T_N_DLIST].count++; // (pair launches whose wave tiles came from the list: sph_timer_get "n_dest_list")
@@ -2632,30 +2659,20 @@ int nnps_csr_pair_kernel(sph_ctx *c, int src, int dst, uint32_t *count, const ui
     const bool dest_is_src = src == dst;
     const size_t total = S.n + (dest_is_src ? 0 : D.n);
     if (total >= (1ull << 32)) { sph_set_error("too many particles for 32-bit packed indices"); return SPH_ERR_ARG; }
-    PackPlan pl = pack_plan(FAM_NBR);
-    if (uh) pl.nr = 4;
-    const bool was_f32 = c->record_f32 != 0, was_a32 = c->arith_f32 != 0; // lists are exact: fp64 records always
-    c->record_f32 = 0; c->arith_f32 = 0;
-    c->cur_eosf = false;
-    c->cur_eosv = false;
-    c->cur_tvff = false;
-    c->cur_elu = false;
-    c->cur_umass = false;
-    c->cur_nrec = pl.nr;
-    int rc = c->posh.reserve((total + 64) * sizeof(double) * pl.nr);
-    if (rc == SPH_OK) rc = c->aux.reserve(64);
-    if (rc == SPH_OK) rc = c->fposb.reserve((total + 64) * sizeof(float4));
+    RecordLayout rl(FAM_NBR); // lists are exact: fp64 records, whatever the options say
+    if (uh) rl.pl.nr = 4;
     for (auto &pc : c->pack_cache) pc.epoch = 0;
-    if (rc == SPH_OK) rc = pack_array(c, src, 0, pl, FAM_NBR, 1u, false, true, 0);
-    if (rc == SPH_OK && S.g_n > 0) rc = pack_array(c, src, 0, pl, FAM_NBR, 1u, false, true, 1);
-    if (rc == SPH_OK && !dest_is_src) rc = pack_array(c, dst, S.n, pl, FAM_NBR, 1u, true, true, 0);
-    c->record_f32 = was_f32; c->arith_f32 = was_a32;
-    if (rc != SPH_OK) return rc;
+    SPH_TRY(c->posh.reserve((total + 64) * sizeof(double) * rl.pl.nr));
+    SPH_TRY(c->aux.reserve(64));
+    SPH_TRY(c->fposb.reserve((total + 64) * sizeof(float4)));
+    SPH_TRY(pack_array(c, src, 0, rl, FAM_NBR, 1u, false, true, 0));
+    if (S.g_n > 0) SPH_TRY(pack_array(c, src, 0, rl, FAM_NBR, 1u, false, true, 1));
+    if (!dest_is_src) SPH_TRY(pack_array(c, dst, S.n, rl, FAM_NBR, 1u, true, true, 0));
     sph_kernel K;
     K.kind = 1; K.dim = c->dim; K.fac = 1.0; K.radius_scale = c->radius_scale; K.deltap = 0.0;
     PairArgs<FamNbr> a;
     memset(&a, 0, sizeof a);
-    fill_common(c, a, &K, 0.0);
+    fill_common(c, a, &K, 0.0, 0.0, rl.pl.nr);
     a.ablate = 0; a.dbg = nullptr;
     a.nsrc = 1;
     a.src[0] = {S.cell_start.as<uint32_t>(), 0u, 1u, S.fine_start.as<uint32_t>(), 0.0, 0u};
@@ -2679,10 +2696,10 @@ int nnps_csr_pair_kernel(sph_ctx *c, int src, int dst, uint32_t *count, const ui
 // EOS-fused uniform-mass records (uniform h, sph_group.src_eos, gamma = 7, no tensile correction, one mass per class).
 // *done = false: not applicable, the caller takes the per-destination path.
 // ---------------------------------------------------------------------------
-static int eval_group_merged(sph_ctx *c, const sph_kernel *K, const sph_group *g, double t, bool *done)
+static int eval_group_merged(sph_ctx *c, const sph_kernel *K, const sph_group *g, double t, double dt, bool *done)
 {
     *done = false;
-    if (!c->merged_valid || !c->merge_arrays || !c->nnps_valid || c->pair_variant != 6 || c->ablate || c->count_iters) return SPH_OK;
+    if (!c->merged_valid || !c->merge_arrays || !c->nnps_valid || !wave_tiles(c) || c->ablate || c->count_iters) return SPH_OK;
     if (c->merge_blocked || !c->xflag.ptr) return SPH_OK; // a non-positive density was seen: the sign of rho cannot carry the class
     if (g->phase != 0 || c->ghosts_binned) return SPH_OK; // ghost segments: the per-destination path reads them as extra sources
     if (!(g->src_eos == 1 && c->eos_fuse && c->mass_fuse && c->const_flags &&
@@ -2782,8 +2799,6 @@ static int eval_group_merged(sph_ctx *c, const sph_kernel *K, const sph_group *g
         }
         if (cls[a]) pa.cls |= 1u << a;
     }
-    c->cur_eosf = !vh; c->cur_umass = !vh; c->cur_tvff = false; c->cur_elu = false; c->cur_eosv = vh;
-    c->cur_nrec = 8;
     SPH_TRY(c->posh.reserve((M.n + 64) * (f32 ? 32 : 64)));
     SPH_TRY(c->aux.reserve(64));
     SPH_TRY(c->fposb.reserve((M.n + 64) * sizeof(float4)));
@@ -2812,7 +2827,7 @@ static int eval_group_merged(sph_ctx *c, const sph_kernel *K, const sph_group *g
         typedef decltype(tag) Fm;
         PairArgs<Fm> a;
         memset(&a, 0, sizeof a);
-        fill_common(c, a, K, t);
+        fill_common(c, a, K, t, dt, 8); // k_pack_merged: 8 doubles per record, or 8 floats
         a.nsrc = 1;
         a.src[0] = {nullptr, 0u, ct, M.fine_start.as<uint32_t>(), mu[0]};
         a.d_off = 0; a.nd = (uint32_t)M.n;
@@ -2885,10 +2900,643 @@ static int run_pending_eos(sph_ctx *c, const sph_group *g)
     return SPH_OK;
 }
 
+// ---------------------------------------------------------------------------
+// sph_eval_group, one destination at a time: plan -> records -> pack -> neighbour lists -> bind and launch.  Every
+// stage is a function below; what one stage decides reaches the next as a value (DestPlan, RecordLayout), never
+// through the context.
+// ---------------------------------------------------------------------------
+
+// destinations in first-appearance order (acceleration_eval.py:126-131)
+static int resolve_destinations(sph_ctx *c, const sph_group *g, int *dests, int *ndest)
+{
+    *ndest = 0;
+    for (int i = 0; i < g->neq; i++) {
+        int d = g->eqs[i].dest;
+        if (d < 0 || d >= SPH_MAX_ARRAYS || !c->arr[d].used) { sph_set_error("equation %d: bad dest array %d", i, d); return SPH_ERR_ARG; }
+        bool seen = false;
+        for (int j = 0; j < *ndest; j++) seen |= dests[j] == d;
+        if (!seen) dests[(*ndest)++] = d;
+    }
+    if (g->phase < 0 || g->phase > 2 || (g->phase != 0 && *ndest != 1)) {
+        sph_set_error("sph_eval_group: phase %d needs a group with one destination array", g->phase);
+        return SPH_ERR_ARG;
+    }
+    return SPH_OK;
+}
+
+// equations without sources run first (mako :50-58); phase 2: over the particles that arrived since phase 1
+static int run_nosrc_equations(sph_ctx *c, const sph_group *g, int dst, size_t start, size_t stop)
+{
+    const size_t ns_start = g->phase == 2 ? std::max(start, c->arr[dst].n_binned) : start;
+    for (int i = 0; i < g->neq; i++) {
+        const sph_equation &e = g->eqs[i];
+        if (e.dest != dst || e.nsrc != 0) continue;
+        if (!is_nosrc_kind(e.kind)) { sph_set_error("equation kind %d needs sources", e.kind); return SPH_ERR_UNSUPPORTED; }
+        SPH_TRY(run_nosrc(c, e, ns_start, stop));
+        c->pack_cache[dst].epoch = 0; // its properties changed: records packed for an earlier destination are stale
+    }
+    return SPH_OK;
+}
+
+// What the pair loop of one destination evaluates.  plan_destination builds it once (the caller sets dst, ndest, phase,
+// start and stop); every later stage reads it as const.
+struct DestPlan {
+    int dst = -1, ndest = 0, phase = 0;
+    size_t start = 0, stop = 0;           // NP_DEST / D_START_IDX (acceleration_eval_cython_helper.py:259-280)
+    int fam = FAM_NONE;                   // FAM_NONE: this destination has no pair launch
+    int nsrcs = 0, srcs[SPH_MAX_ARRAYS];  // sources in first-appearance order (acceleration_eval.py:136-151) ...
+    uint32_t sflags[SPH_MAX_ARRAYS] = {}; // ... the flags of the equations that read each ...
+    uint32_t dflags = 0;                  // ... and their union
+    const sph_equation *eq_of[64] = {};   // the equation of a kind on this destination ...
+    int eq_pos[64] = {};                  // ... and its position in the group
+    // records in the packed buffer: all of them, the first of every source, the first of the destination
+    size_t total = 0, off_of[SPH_MAX_ARRAYS], d_off = 0;
+    bool dest_is_src = false;
+    bool share = false;                   // one buffer slot per neighbour-grid array, shared by the destinations of a group
+    bool any_ghosts = false;              // a ghost segment (sph_nnps_update_ghosts) among the arrays read
+};
+
+static int plan_destination(sph_ctx *c, const sph_group *g, DestPlan &P)
+{
+    const int dst = P.dst;
+    const DevArray &D = c->arr[dst];
+    // what the equations with sources on this destination say about the family of the ones several families have: an
+    // elastic-rates term; a delta-SPH / laminar-viscosity term (the WCSPH-options family); an EDAC force equation;
+    // ComputeAveragePressure
+    bool elastic = false, wcsphx = false, edac = false, avgp = false;
+    for (int i = 0; i < g->neq; i++) {
+        const int kind = g->eqs[i].kind;
+        if (g->eqs[i].dest != dst || g->eqs[i].nsrc <= 0) continue;
+        elastic |= kind == SPH_EQ_MOMENTUM_WITH_STRESS || kind == SPH_EQ_MONAGHAN_ART_VISCOSITY;
+        wcsphx |= is_wcsph_option_kind(kind);
+        edac |= is_edac_force_kind(kind);
+        avgp |= kind == SPH_EQ_EDAC_AVG_PRESSURE;
+    }
+    for (int i = 0; i < g->neq; i++) {
+        const sph_equation &e = g->eqs[i];
+        if (e.dest != dst || e.nsrc == 0) continue;
+        if (e.kind < 0 || e.kind >= 64) { sph_set_error("bad equation kind %d", e.kind); return SPH_ERR_ARG; }
+        uint32_t flag = 0;
+        int f = eq_family(e.kind, &flag, elastic, wcsphx, edac, avgp);
+        P.eq_pos[e.kind] = i;
+        if (f == FAM_NONE) { sph_set_error("equation kind %d has no hand-written pair kernel", e.kind); return SPH_ERR_UNSUPPORTED; }
+        if (P.fam != FAM_NONE && f != P.fam) {
+            sph_set_error("group mixes equation families on destination %d (kinds are fused per family)", dst);
+            return SPH_ERR_UNSUPPORTED;
+        }
+        P.fam = f;
+        if (P.eq_of[e.kind]) {
+            sph_set_error("equation kind %d appears twice for destination %d in one group", e.kind, dst);
+            return SPH_ERR_UNSUPPORTED;
+        }
+        P.eq_of[e.kind] = &e;
+        for (int k = 0; k < e.nsrc; k++) {
+            int s = e.src[k], pos = -1;
+            if (s < 0 || s >= SPH_MAX_ARRAYS || !c->arr[s].used) { sph_set_error("bad source array %d", s); return SPH_ERR_ARG; }
+            for (int j = 0; j < P.nsrcs; j++) if (P.srcs[j] == s) pos = j;
+            if (pos < 0) { pos = P.nsrcs; P.srcs[P.nsrcs++] = s; }
+            P.sflags[pos] |= flag;
+        }
+    }
+    if (P.fam == FAM_NONE) return SPH_OK;
+    const int fam = P.fam, nsrcs = P.nsrcs;
+    uint32_t *sflags = P.sflags, &dflags = P.dflags;
+    if (!c->nnps_valid) { sph_set_error("sph_eval_group: neighbour grid is stale; call sph_nnps_update"); return SPH_ERR_STATE; }
+    if (D.nnps_slot < 0) { sph_set_error("destination array %d is not part of the neighbour grid", dst); return SPH_ERR_STATE; }
+    SPH_TRY(nnps_need_tables(c)); // the per-destination path reads every array's own cell order
+    for (int j = 0; j < nsrcs; j++) {
+        dflags |= sflags[j];
+        if (c->arr[P.srcs[j]].nnps_slot < 0) { sph_set_error("source array %d is not part of the neighbour grid", P.srcs[j]); return SPH_ERR_STATE; }
+    }
+    if (fam == FAM_WCSPHX) {
+        // the extra terms add into the sums of the Continuity / Momentum equations, whose finish() writes them
+        if ((dflags & F_DCONT) && !(dflags & F_CONT)) { sph_set_error("ContinuityEquationDeltaSPH needs a ContinuityEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        if ((dflags & (F_DMOM | F_LAM | F_LAMD)) && !(dflags & F_MOM)) { sph_set_error("the delta-SPH / laminar viscosity terms need a MomentumEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        if ((dflags & F_LAM) && (dflags & F_LAMD)) { sph_set_error("both LaminarViscosity and LaminarViscosityDeltaSPH on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+    }
+    if (fam == FAM_EDAC) {
+        if (P.eq_of[SPH_EQ_EDAC_MOMENTUM] && P.eq_of[SPH_EQ_EDAC_MOM_PRESSURE]) { sph_set_error("both EDAC pressure-gradient forms on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        if ((dflags & F_EINT) && (dflags & F_EXS)) { sph_set_error("XSPHCorrection next to the internal-flow EDAC pressure gradient on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        if (!(dflags & F_EINT) && (dflags & F_TAS)) { sph_set_error("MomentumEquationArtificialStress next to the external-flow EDAC equations on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
+        // the branch is a property of the destination: one instantiation per branch, and equal flag sets on the
+        // sources of a default group so that the compile-time set applies
+        if (dflags & F_EINT) for (int j = 0; j < nsrcs; j++) sflags[j] |= F_EINT;
+    }
+    if (fam == FAM_DSPRE) {
+        // the moment matrix must be complete before a corrected gradient reads it: a group of its own, as in WCSPHScheme
+        if ((dflags & F_MOMENT) && (dflags & (F_GRADRHO | F_GCORR))) {
+            sph_set_error("GradientCorrectionPreStep shares a group with GradientCorrection / ContinuityEquationDeltaSPHPreStep on destination %d; put it in a group of its own before them", dst);
+            return SPH_ERR_UNSUPPORTED;
+        }
+        // GradientCorrection rewrites DWIJ for the equations AFTER it: behind the pre-step it corrects nothing
+        if ((dflags & F_GCORR) && (!(dflags & F_GRADRHO) || P.eq_pos[SPH_EQ_GRADIENT_CORRECTION] > P.eq_pos[SPH_EQ_CONTINUITY_DELTA_SPH_PRESTEP])) {
+            dflags &= ~(uint32_t)F_GCORR;
+            for (int j = 0; j < nsrcs; j++) sflags[j] &= ~(uint32_t)F_GCORR;
+        }
+        if (!dflags) { P.fam = FAM_NONE; return SPH_OK; }
+        for (int j = 0; j < nsrcs; j++) if ((sflags[j] & F_GCORR) && !(sflags[j] & F_GRADRHO)) sflags[j] &= ~(uint32_t)F_GCORR;
+    }
+    if ((fam == FAM_WCSPH || fam == FAM_WCSPHX) && P.eq_of[SPH_EQ_MOMENTUM] && P.eq_of[SPH_EQ_MOMENTUM]->par[6] != 0.0) {
+        dflags |= F_TENSILE;
+        for (int j = 0; j < nsrcs; j++) if (sflags[j] & F_MOM) sflags[j] |= F_TENSILE;
+    }
+
+    // where the records go: every source, then the destination unless it is a source
+    for (int j = 0; j < nsrcs; j++) { P.off_of[j] = P.total; P.total += c->arr[P.srcs[j]].n; P.dest_is_src |= P.srcs[j] == dst; }
+    P.d_off = P.total;
+    if (!P.dest_is_src) P.total += D.n;
+    else for (int j = 0; j < nsrcs; j++) if (P.srcs[j] == dst) P.d_off = P.off_of[j];
+    // WCSPH groups with several destinations (a dam break: fluid, boundary, obstacle) read the
+    // SAME source records, and nothing the family writes (accelerations) is part of a record:
+    // one buffer slot per neighbour-grid array, each array packed once per group instead of
+    // once per destination that reads it (dam break C2: 7 -> 3 k_pack launches per evaluation).
+    // The host brackets the per-destination calls of one group with option pack_group 1 / 0.
+    P.share = fam == FAM_WCSPH && wave_tiles(c) && (P.ndest > 1 || c->pack_group);
+    if (P.share) {
+        size_t goff[SPH_MAX_ARRAYS] = {};
+        P.total = 0;
+        for (int a = 0; a < c->narrays; a++) { goff[c->ids[a]] = P.total; P.total += c->arr[c->ids[a]].n; }
+        for (int j = 0; j < nsrcs; j++) P.off_of[j] = goff[P.srcs[j]];
+        P.d_off = goff[dst];
+    }
+    if (P.total >= (1ull << 32)) { sph_set_error("too many particles for 32-bit packed indices"); return SPH_ERR_ARG; }
+    // ghost split (sph_nnps_update_ghosts): arrays whose ghosts were binned after the real particles carry them as a
+    // second record segment and a second source; the destinations are the particles the update binned (a
+    // destination-only array is read through its own records only: its ghosts are no destinations)
+    for (int j = 0; j < nsrcs; j++) P.any_ghosts |= c->arr[P.srcs[j]].g_n > 0;
+    P.any_ghosts |= D.g_n > 0;
+    if (P.phase != 0 && !(nsrcs == 1 && P.srcs[0] == dst && !P.share)) {
+        sph_set_error("sph_eval_group: phases need a group over ONE array (destination == its only source)");
+        return SPH_ERR_UNSUPPORTED;
+    }
+    if ((P.any_ghosts || P.phase != 0) && !wave_tiles(c)) {
+        sph_set_error("ghost segments (sph_nnps_update_ghosts) need pair_variant 6");
+        return SPH_ERR_UNSUPPORTED;
+    }
+    return SPH_OK;
+}
+
+// The records of this destination's block.  eos_pending: the Tait EOS the host left to this call (sph_group.src_eos = 3)
+// has not run; RecordLayout::eos_abs says whether the pack of these records takes it over.
+static RecordLayout choose_records(sph_ctx *c, const sph_group *g, const DestPlan &P, bool eos_pending)
+{
+    const int fam = P.fam, nsrcs = P.nsrcs;
+    const uint32_t dflags = P.dflags;
+    const DevArray &D = c->arr[P.dst];
+    const bool wave = wave_tiles(c), uh = c->uniform_h && c->use_uniform_h;
+    RecordLayout rl(fam);
+    PackPlan &pl = rl.pl;
+    rl.record_f32 = c->record_f32 != 0;
+    rl.arith_f32 = c->arith_f32 != 0;
+    if (fam == FAM_WCSPHX && (dflags & F_DCONT)) { // the records carry the sources' gradrho
+        for (int k = 0; k < 3; k++) pl.props[8 + k] = SPH_GRADRHO0 + k;
+        pl.na = 11; pl.nr = 16;
+    }
+    // compact 80-B WCSPH records when neither h nor p of a neighbour is read
+    if (wave && fam == FAM_WCSPH && uh && !(dflags & F_TENSILE)) pl.nr = c->wcsph_nr ? (int)c->wcsph_nr : 10;
+    if (wave && fam == FAM_DENSITY && uh) pl.nr = 4;
+    if (wave && fam == FAM_TVF && uh) pl.nr = (dflags & F_TAV) ? 14 : 12;
+    if (wave && fam == FAM_EDAC && uh) pl.nr = 14; // (m always: load_record_edac)
+    if (wave && (rl.record_f32 || rl.arith_f32)) pl.nr = (4 + pl.na + 3) & ~3; // floats
+    // The caller promised (sph_group.src_eos) that p, cs of every array read here are the Tait EOS of its
+    // rho: with gamma = 7 (powers by multiplication), uniform h and no tensile correction the pair kernel
+    // recomputes them and the records shrink to 64 bytes (32 in fp32).
+    const bool eosf = g->src_eos == 1 && c->eos_fuse && fam == FAM_WCSPH && wave && uh && !(dflags & F_TENSILE) &&
+                      tait_gk(g->eos_par[2]) >= 0 && g->eos_par[0] > 0.0 && !rl.record_f32 && !c->wcsph_nr;
+    if (eosf) pl.nr = 8; // doubles, or floats with arith_f32
+    // ... and when every array read here had ONE mass at the last neighbour update, the record's mass slot
+    // carries p / rho^2 and most of the per-record EOS goes as well (FamWCSPHE_T<T, true>)
+    // (only with the equation flags as a compile-time constant: the run-time-flag kernel of a dam break's three
+    // sources is at its scalar-register limit and 1-3 % slower with a mass per source)
+    bool umass = eosf && c->mass_fuse && c->const_flags;
+    for (int j = 0; j < nsrcs && umass; j++) umass = P.sflags[j] == FamWCSPH::CF0;
+    if (umass) c->want_mrange = true; // the reduction of the neighbour updates from now on includes m (8 B per particle)
+    for (int j = 0; j < nsrcs && umass; j++) umass = c->arr[P.srcs[j]].m_known;
+    // ... and with VARIABLE h the same promise plus one mass per source array gives 64-byte records [x y z h u v w rho]
+    bool eosv = !eosf && g->src_eos == 1 && c->eos_fuse && c->mass_fuse && fam == FAM_WCSPH && wave && !uh &&
+                !(dflags & F_TENSILE) && tait_gk(g->eos_par[2]) == 3 && g->eos_par[0] > 0.0 && !rl.record_f32 && !c->wcsph_nr;
+    if (eosv) c->want_mrange = true;
+    for (int j = 0; j < nsrcs && eosv; j++) eosv = c->arr[P.srcs[j]].m_known;
+    if (eosv) pl.nr = 8;
+    // TVF force pass after StateEquation + density summation (sph_group.src_eos = 2): p and V leave the records
+    // when every array read here has ONE mass (V = rho / m)
+    bool tvff = g->src_eos == 2 && c->eos_fuse && c->mass_fuse && fam == FAM_TVF && wave && uh && !rl.record_f32 &&
+                g->eos_par[1] != 0.0; // (the artificial viscosity's m_j is the source's one mass)
+    if (tvff) c->want_mrange = true;
+    for (int j = 0; j < nsrcs && tvff; j++) tvff = c->arr[P.srcs[j]].m_known;
+    if (tvff && !P.dest_is_src) tvff = D.m_known;
+    if (tvff) pl.nr = rl.arith_f32 ? ((dflags & F_TAS) ? 12 : 8) : ((dflags & F_TAS) ? 10 : 8);
+    // elastic rates: uniform h and ONE mass per source array -> neither travels in the records
+    bool elu = fam == FAM_ELASTIC && c->mass_fuse && wave && uh && !rl.record_f32;
+    if (elu) c->want_mrange = true;
+    for (int j = 0; j < nsrcs && elu; j++) elu = c->arr[P.srcs[j]].m_known;
+    if (elu) pl.nr = 20; // doubles, or floats with arith_f32
+    rl.kind = eosf ? REC_EOSF : eosv ? REC_EOSV : tvff ? REC_TVFF : elu ? REC_ELU : REC_PLAIN; // (one family each: exclusive)
+    rl.umass = umass;
+    // The pending Tait EOS is absorbed by the records when they are the EOS-fused ones of ONE array and the pack
+    // launches visit every particle of it (both segments) (gamma = 7 only: the other odd exponents keep the EOS kernel)
+    rl.eos_abs = eos_pending && rl.eos_fused() && c->eos_absorb && tait_gk(g->eos_par[2]) == 3 && P.phase == 0 && P.ndest == 1 &&
+                 nsrcs == 1 && P.srcs[0] == P.dst && D.n > 0 && D.n_binned + D.g_n == D.n;
+    if (rl.eos_abs) for (int k = 0; k < 4; k++) rl.eos_par[k] = g->eos_par[k];
+    return rl;
+}
+
+// Room for the records, then the pack launches: every source and the destination's own record, once per group where the
+// destinations of a group share them (the pack cache), per segment in a split evaluation
+static int pack_records(sph_ctx *c, const DestPlan &P, const RecordLayout &rl)
+{
+    const int phase = P.phase, fam = P.fam;
+    const void *rec_was = c->posh.ptr, *fpos_was = c->fposb.ptr;
+    // phase 1 leaves room for the ghosts phase 2 packs behind the real particles' records (the array's capacity bounds
+    // them); phase 2 keeps what phase 1 packed should the buffers have to grow after all
+    const size_t total_res = phase == 1 ? std::max(P.total, c->arr[P.dst].cap) : P.total;
+    SPH_TRY(c->posh.reserve((total_res + 64) * sizeof(double) * (wave_tiles(c) ? rl.pl.nr : 4), phase == 2, c->stream));
+    SPH_TRY(c->aux.reserve((total_res + 64) * sizeof(double) * rl.pl.na));
+    if (wave_tiles(c)) SPH_TRY(c->fposb.reserve((total_res + 64) * sizeof(float4), phase == 2, c->stream));
+    if (c->posh.ptr != rec_was || c->fposb.ptr != fpos_was) // the buffers moved: nothing packed earlier is there
+        for (auto &pc : c->pack_cache) pc.epoch = 0;
+    ScopedTimer tm(c, T_PACK);
+    const int sig = rl.sig();
+    // The shared slots live in the same buffers every other unit packs into from offset 0:
+    // a unit that does not share (another family, a single-destination call), or one whose
+    // record layout differs from what the cache holds, overwrites them -- nothing cached survives.
+    // a split evaluation: the second half must read the layout the first half packed -- when what is known of the
+    // masses changed in between (a ghost with another mass: sph_nnps_update_ghosts), it packs both segments again
+    if (phase == 1) c->phase_sig = sig;
+    const bool repack = phase == 2 && c->phase_sig != sig;
+    bool keep = P.share;
+    if (P.share)
+        for (auto &pc : c->pack_cache)
+            if (pc.epoch == c->pack_epoch && (pc.fam != fam || pc.sig != sig)) keep = false;
+    if (!keep)
+        for (auto &pc : c->pack_cache) pc.epoch = 0;
+    auto pack_once = [&](int id, size_t off, uint32_t fl, bool dest_only) -> int {
+        PackCache &pc = c->pack_cache[id];
+        const bool hit = P.share && pc.epoch == c->pack_epoch && pc.fam == fam && pc.sig == sig;
+        // phase 1: the particles present (the real ones); phase 2: the ghosts that arrived since; else both segments
+        if (phase != 2 || repack) SPH_TRY(pack_array(c, id, off, rl, fam, fl, dest_only, !hit, 0)); // a hit still validates
+        if (phase != 1 && c->arr[id].g_n > 0) SPH_TRY(pack_array(c, id, off, rl, fam, fl, dest_only, !hit, 1));
+        pc.epoch = P.share ? c->pack_epoch : 0; pc.fam = fam; pc.sig = sig;
+        return SPH_OK;
+    };
+    // a source must hold what ITS equations read; the destination's own record what all of them read
+    for (int j = 0; j < P.nsrcs; j++) SPH_TRY(pack_once(P.srcs[j], P.off_of[j], P.srcs[j] == P.dst ? P.dflags : P.sflags[j], false));
+    if (!P.dest_is_src) SPH_TRY(pack_once(P.dst, P.d_off, P.dflags, true));
+    return SPH_OK;
+}
+
+// Neighbour-list reuse between the pair passes of one evaluation (sph_group.nl_mode): one source,
+// the wave-tile kernel, same grid.  A pass that keeps its lists (1) records what they belong to; a pass
+// that wants them (2) gets them only if that record matches -- otherwise it runs its own phase 1.
+static int choose_nl_mode(sph_ctx *c, const sph_group *g, const DestPlan &P, int *nl_mode)
+{
+    const DevArray &D = c->arr[P.dst];
+    *nl_mode = 0;
+    if (c->nl_reuse && !c->row_lds && wave_tiles(c) && P.nsrcs == 1 && g->nl_mode && !c->ablate && !P.any_ghosts && P.phase == 0) {
+        const size_t n_wt = (size_t)4 * div_up(D.n, 256);
+        if (g->nl_mode == 1) {
+            SPH_TRY(c->nlbuf.reserve(n_wt * NLW * sizeof(uint32_t)));
+            c->nl.valid = true; c->nl.epoch = c->nnps_epoch; c->nl.dst = P.dst; c->nl.src = P.srcs[0];
+            c->nl.start = P.start; c->nl.stop = P.stop; c->nl.nd = D.n;
+            *nl_mode = 1;
+        } else if (g->nl_mode == 2 && c->nl.valid && c->nl.epoch == c->nnps_epoch && c->nl.dst == P.dst && c->nl.src == P.srcs[0] &&
+                   c->nl.nd == D.n && c->nl.start <= P.start && c->nl.stop >= P.stop && c->nlbuf.bytes >= n_wt * NLW * sizeof(uint32_t)) {
+            *nl_mode = 2;
+        }
+    } else if (g->nl_mode != 2) {
+        c->nl.valid = c->nl.valid && !(g->nl_mode == 1); // a keeping pass that could not keep: nothing to reuse
+    }
+    return SPH_OK;
+}
+
+// one pair launch of sph_eval_group: what the family binders below read
+struct PairLaunch {
+    sph_ctx *c;
+    const sph_kernel *K;
+    const sph_group *g;
+    double t, dt;
+    const DestPlan &P;
+    const RecordLayout &rl;
+    int nl_mode;
+};
+
+// the launch arguments of a family, zeroed, with the part every family shares filled in
+template <class F> static PairArgs<F> pair_args(const PairLaunch &L)
+{
+    sph_ctx *c = L.c;
+    const DestPlan &P = L.P;
+    const sph_group *g = L.g;
+    const DevArray &D = c->arr[P.dst];
+    PairArgs<F> a;
+    memset(&a, 0, sizeof a);
+    fill_common(c, a, L.K, L.t, L.dt, L.rl.pl.nr);
+    for (int j = 0; j < P.nsrcs; j++) {
+        const DevArray &S = c->arr[P.srcs[j]];
+        a.src[a.nsrc++] = {S.cell_start.as<uint32_t>(), (uint32_t)P.off_of[j], P.sflags[j], S.fine_start.as<uint32_t>(), S.m_value, 0u};
+    }
+    for (int j = 0; j < P.nsrcs && P.phase != 1; j++) { // the ghost segments, after every array's first segment
+        const DevArray &S = c->arr[P.srcs[j]];
+        if (S.g_n == 0) continue;
+        a.src[a.nsrc++] = {S.g_cell_start.as<uint32_t>(), (uint32_t)(P.off_of[j] + S.n_binned), P.sflags[j],
+                           S.g_fine_start.as<uint32_t>(), S.m_value, 1u};
+    }
+    a.face_mode = c->split_pair ? P.phase : 0;
+    a.d_off = (uint32_t)P.d_off; a.nd = (uint32_t)D.n_binned;
+    a.d_mu = D.m_value;
+    a.d_keys = D.keys_sorted.as<uint32_t>(); a.d_fkeys = D.fkeys_sorted.as<uint32_t>(); a.d_perm = D.perm.as<uint32_t>();
+    set_tile_order(c, a, D);
+    a.d_start = (uint32_t)P.start; a.d_stop = (uint32_t)P.stop; a.dflags = P.dflags;
+    a.nl_mode = L.nl_mode;
+    if (L.nl_mode) a.nl = c->nlbuf.as<uint32_t>();
+    // Group.real = True without start / stop: the destinations are the real particles
+    if (P.start == 0 && P.stop == D.n_real && D.n_binned == D.n && !P.any_ghosts) use_dest_list(c, a, D);
+    if (L.rl.eos_fused()) {
+        a.e_rho01 = 1.0 / g->eos_par[0]; a.e_c0 = g->eos_par[1];
+        a.e_B = g->eos_par[0] * g->eos_par[1] * g->eos_par[1] / g->eos_par[2];
+        a.e_gk = tait_gk(g->eos_par[2]);
+        a.e_p0 = g->eos_par[3];
+    }
+    if (L.rl.kind == REC_TVFF) { a.e_p0 = g->eos_par[0]; a.e_rho01 = 1.0 / g->eos_par[1]; a.e_B = g->eos_par[2]; } // StateEquation: p0 rho0 b
+    return a;
+}
+
+// output properties of the destination: created where missing, then bound to the launch arguments
+struct OutBind { int prop; double **to; };
+static int bind_out(const PairLaunch &L, std::initializer_list<OutBind> outs)
+{
+    for (const OutBind &o : outs) SPH_TRY(sph_array_ensure_prop(L.c, L.P.dst, o.prop));
+    for (const OutBind &o : outs) *o.to = L.c->arr[L.P.dst].prop[o.prop];
+    return SPH_OK;
+}
+
+// Continuity / Momentum / XSPH: parameters and outputs, the same for the WCSPH families and the WCSPH-options family
+template <class F> static int bind_wcsph(const PairLaunch &L, PairArgs<F> &a)
+{
+    const uint32_t dflags = L.P.dflags;
+    const sph_equation *me = L.P.eq_of[SPH_EQ_MOMENTUM], *xe = L.P.eq_of[SPH_EQ_XSPH];
+    if (me) { a.p.c0 = me->par[0]; a.p.alpha = me->par[1]; a.p.beta = me->par[2]; a.p.gx = me->par[3]; a.p.gy = me->par[4]; a.p.gz = me->par[5]; }
+    if (xe) a.p.eps = xe->par[0];
+    if (dflags & F_CONT) SPH_TRY(bind_out(L, {{SPH_ARHO, &a.p.arho}}));
+    if (dflags & F_MOM)
+        SPH_TRY(bind_out(L, {{SPH_AU, &a.p.au}, {SPH_AV, &a.p.av}, {SPH_AW, &a.p.aw}, {SPH_DT_CFL, &a.p.dt_cfl}, {SPH_DT_FORCE, &a.p.dt_force}}));
+    if (dflags & F_XSPH) SPH_TRY(bind_out(L, {{SPH_AX, &a.p.ax}, {SPH_AY, &a.p.ay}, {SPH_AZ, &a.p.az}}));
+    return SPH_OK;
+}
+template <class F> static int run_wcsph(const PairLaunch &L)
+{
+    PairArgs<F> a = pair_args<F>(L);
+    SPH_TRY(bind_wcsph(L, a));
+    if constexpr (std::is_same<F, FamWCSPHV_T<typename F::Real>>::value) return launch_pair_fused<F, false>(L.c, L.K->kind, a);
+    else if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(L.c, L.K->kind, a);
+    else return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+// the WCSPH-options family: FamWCSPH_T's arguments + the parameters of the extra terms
+template <class F> static int run_wcsphx(const PairLaunch &L)
+{
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *dc = L.P.eq_of[SPH_EQ_CONTINUITY_DELTA_SPH], *dm = L.P.eq_of[SPH_EQ_MOMENTUM_DELTA_SPH],
+                       *lv = L.P.eq_of[SPH_EQ_LAMINAR_VISCOSITY], *ld = L.P.eq_of[SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH];
+    if (dc) a.p.dfac = dc->par[1] * dc->par[0];                  // par c0 delta
+    if (dm) a.p.mfac = dm->par[2] * dm->par[1] * dm->par[0];     // par rho0 c0 alpha
+    if (lv) { a.p.nu4 = 4.0 * lv->par[0]; a.p.eta = lv->par[1]; } // par nu eta
+    if (ld) a.p.lfac = 2.0 * (ld->par[0] + 2.0) * ld->par[2] * ld->par[1]; // par dim rho0 nu
+    SPH_TRY(bind_wcsph(L, a));
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+// the delta-SPH pre-passes: the moment matrix, or the (renormalised) density gradient
+template <class F> static int run_dspre(const PairLaunch &L)
+{
+    const uint32_t dflags = L.P.dflags;
+    const DevArray &D = L.c->arr[L.P.dst];
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *pe = L.P.eq_of[SPH_EQ_GRADIENT_CORRECTION_PRESTEP], *ge = L.P.eq_of[SPH_EQ_GRADIENT_CORRECTION];
+    a.p.mdim = pe ? (int)pe->par[0] : 0;
+    a.p.n = 0;
+    if (dflags & F_GCORR) { a.p.n = (int)ge->par[0]; a.p.tol = ge->par[1]; }
+    if (a.p.mdim < 0 || a.p.mdim > 3 || ((dflags & F_GCORR) && (a.p.n < 1 || a.p.n > 3))) {
+        sph_set_error("GradientCorrection / GradientCorrectionPreStep: dim must be 1, 2 or 3");
+        return SPH_ERR_ARG;
+    }
+    if (dflags & (F_MOMENT | F_GCORR)) {
+        for (int k = 0; k < 9; k++) {
+            const int pid = SPH_MMAT0 + k;
+            if (dflags & F_MOMENT) SPH_TRY(sph_array_ensure_prop(L.c, L.P.dst, pid));
+            else if (!D.prop[pid]) return need_prop(L.c, L.P.dst, pid, "GradientCorrection (m_mat)");
+            a.p.mm[k] = D.prop[pid];
+        }
+    }
+    if (dflags & F_GRADRHO)
+        for (int k = 0; k < 3; k++) SPH_TRY(bind_out(L, {{SPH_GRADRHO0 + k, &a.p.gr[k]}}));
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+template <class F> static int run_density(const PairLaunch &L)
+{
+    const uint32_t dflags = L.P.dflags;
+    PairArgs<F> a = pair_args<F>(L);
+    SPH_TRY(bind_out(L, {{SPH_RHO, &a.p.rho}}));
+    if (dflags & F_TVFSD) SPH_TRY(bind_out(L, {{SPH_VOL, &a.p.V}}));
+    if ((dflags & F_SD) && (dflags & F_TVFSD)) { sph_set_error("both SummationDensity flavours on one destination"); return SPH_ERR_UNSUPPORTED; }
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+template <class F> static int run_vgrad(const PairLaunch &L)
+{
+    const uint32_t dflags = L.P.dflags;
+    PairArgs<F> a = pair_args<F>(L);
+    static const int vp[9] = {SPH_V00, SPH_V01, SPH_V02, SPH_V10, SPH_V11, SPH_V12, SPH_V20, SPH_V21, SPH_V22};
+    if ((dflags & F_VG2) && (dflags & F_VG3)) { sph_set_error("both VelocityGradient2D and 3D on one destination"); return SPH_ERR_UNSUPPORTED; }
+    for (int k = 0; k < 9; k++) {
+        const bool used = (dflags & F_VG3) || (k == 0 || k == 1 || k == 3 || k == 4);
+        if (used) SPH_TRY(bind_out(L, {{vp[k], &a.p.v[k]}}));
+    }
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+template <class F> static int run_elastic(const PairLaunch &L)
+{
+    sph_ctx *c = L.c;
+    const DestPlan &P = L.P;
+    const uint32_t dflags = P.dflags;
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *se = P.eq_of[SPH_EQ_MOMENTUM_WITH_STRESS], *ae = P.eq_of[SPH_EQ_MONAGHAN_ART_VISCOSITY],
+                       *xe = P.eq_of[SPH_EQ_XSPH];
+    if (se) { a.p.wdeltap = se->par[0]; a.p.n = se->par[1]; }
+    a.p.tension = nullptr;
+    if (L.rl.kind == REC_ELU && c->tension_flag && P.nsrcs == 1 && c->arr[P.srcs[0]].tflag_valid && c->arr[P.srcs[0]].tflag.ptr) {
+        a.p.tension = c->arr[P.srcs[0]].tflag.as<uint32_t>();
+        c->timers[T_N_TFLAG].count++;
+    }
+    if (ae) { a.p.alpha = ae->par[0]; a.p.beta = ae->par[1]; }
+    if (xe) a.p.eps = xe->par[0];
+    if (dflags & F_ECONT) SPH_TRY(bind_out(L, {{SPH_ARHO, &a.p.arho}}));
+    if (dflags & (F_ESTRESS | F_EAV)) SPH_TRY(bind_out(L, {{SPH_AU, &a.p.au}, {SPH_AV, &a.p.av}, {SPH_AW, &a.p.aw}}));
+    if (dflags & F_EXSPH) SPH_TRY(bind_out(L, {{SPH_AX, &a.p.ax}, {SPH_AY, &a.p.ay}, {SPH_AZ, &a.p.az}}));
+    if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(c, L.K->kind, a);
+    else return launch_pair<F>(c, L.K->kind, a, L.rl.record_f32);
+}
+// The TVF force terms, which the EDAC force group carries too.  pe: the family's pressure-gradient equation of the
+// transport-velocity form (par pb gx gy gz tdamp); force / hat: the launch writes au av aw / auhat avhat awhat
+template <class F> static int bind_tvf(const PairLaunch &L, PairArgs<F> &a, const sph_equation *pe, bool force, bool hat)
+{
+    const sph_equation *ve = L.P.eq_of[SPH_EQ_TVF_MOM_VISCOSITY], *ae = L.P.eq_of[SPH_EQ_TVF_MOM_ART_VISCOSITY];
+    if (pe) { a.p.pb = pe->par[0]; a.p.gx = pe->par[1]; a.p.gy = pe->par[2]; a.p.gz = pe->par[3]; a.p.tdamp = pe->par[4]; }
+    if (ve) a.p.nu = ve->par[0];
+    if (ae) { a.p.c0 = ae->par[0]; a.p.alpha = ae->par[1]; }
+    if (force) SPH_TRY(bind_out(L, {{SPH_AU, &a.p.au}, {SPH_AV, &a.p.av}, {SPH_AW, &a.p.aw}}));
+    a.p.m = L.c->arr[L.P.dst].prop[SPH_M];
+    if (hat) SPH_TRY(bind_out(L, {{SPH_AUHAT, &a.p.auhat}, {SPH_AVHAT, &a.p.avhat}, {SPH_AWHAT, &a.p.awhat}}));
+    return SPH_OK;
+}
+template <class F> static int run_tvf(const PairLaunch &L)
+{
+    PairArgs<F> a = pair_args<F>(L);
+    SPH_TRY(bind_tvf(L, a, L.P.eq_of[SPH_EQ_TVF_MOM_PRESSURE], true, (L.P.dflags & F_TP) != 0));
+    if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(L.c, L.K->kind, a);
+    else return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+// the EDAC force group: parameters of its up to six equations; ap and pavg are user properties by name
+template <class F> static int run_edac(const PairLaunch &L)
+{
+    sph_ctx *c = L.c;
+    const DestPlan &P = L.P;
+    const uint32_t dflags = P.dflags;
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *me = P.eq_of[SPH_EQ_EDAC_MOMENTUM], *ee = P.eq_of[SPH_EQ_EDAC], *xe = P.eq_of[SPH_EQ_XSPH];
+    if (me) { a.p.gx = me->par[1]; a.p.gy = me->par[2]; a.p.gz = me->par[3]; a.p.tdamp = me->par[4]; } // par c0 gx gy gz tdamp
+    if (ee) { a.p.cs2 = ee->par[0] * ee->par[0]; a.p.enu = ee->par[1]; } // par cs nu rho0
+    if (xe) a.p.eps = xe->par[0];
+    SPH_TRY(bind_tvf(L, a, P.eq_of[SPH_EQ_EDAC_MOM_PRESSURE], (dflags & (F_EP | F_TVISC | F_TAV | F_TAS)) != 0, (dflags & F_EINT) != 0));
+    if (dflags & F_EINT) {
+        const int ppavg = sph_prop_register("pavg");
+        if (ppavg < 0) return ppavg;
+        SPH_TRY(need_prop(c, P.dst, ppavg, "MomentumEquationPressureGradient of EDAC (pavg)"));
+        a.p.pavg = c->arr[P.dst].prop[ppavg];
+    }
+    if (dflags & F_EDAC) {
+        const int pap = sph_prop_register("ap");
+        if (pap < 0) return pap;
+        SPH_TRY(bind_out(L, {{pap, &a.p.ap}}));
+    }
+    if (dflags & F_EXS) SPH_TRY(bind_out(L, {{SPH_AX, &a.p.ax}, {SPH_AY, &a.p.ay}, {SPH_AZ, &a.p.az}}));
+    return launch_pair<F>(c, L.K->kind, a, L.rl.record_f32);
+}
+template <class F> static int run_avgp(const PairLaunch &L)
+{
+    const uint32_t dflags = L.P.dflags;
+    PairArgs<F> a = pair_args<F>(L);
+    if ((dflags & F_SD) && (dflags & F_TVFSD)) { sph_set_error("both SummationDensity flavours on one destination"); return SPH_ERR_UNSUPPORTED; }
+    if (dflags & (F_SD | F_TVFSD)) SPH_TRY(bind_out(L, {{SPH_RHO, &a.p.rho}}));
+    if (dflags & F_TVFSD) SPH_TRY(bind_out(L, {{SPH_VOL, &a.p.V}}));
+    const int ppavg = sph_prop_register("pavg"), pnn = sph_prop_register("nnbr");
+    if (ppavg < 0 || pnn < 0) return SPH_ERR_ARG;
+    SPH_TRY(bind_out(L, {{ppavg, &a.p.pavg}, {pnn, &a.p.nnbr}}));
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+// the gas-dynamics density sweep: when it iterates, the convergence word is cleared before the launch and read
+// back behind it (one word, one synchronise per call), and h counts as written
+template <class F> static int run_gassd(const PairLaunch &L)
+{
+    sph_ctx *c = L.c;
+    const int dst = L.P.dst;
+    DevArray &D = c->arr[dst];
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *se = L.P.eq_of[SPH_EQ_GASD_SUMMATION_DENSITY]; // par dim k htol density_iterations iterate_only_once
+    a.p.dim = se->par[0]; a.p.k = se->par[1]; a.p.htol = se->par[2];
+    a.p.iterate = se->par[3] != 0.0; a.p.once = se->par[4] != 0.0;
+    const char *names[5] = {"grhox", "grhoy", "grhoz", "dwdh", "div"};
+    int ids[5];
+    for (int k = 0; k < 5; k++) { ids[k] = sph_prop_register(names[k]); if (ids[k] < 0) return ids[k]; }
+    SPH_TRY(bind_out(L, {{SPH_RHO, &a.p.rho}, {SPH_ARHO, &a.p.arho}, {ids[0], &a.p.grhox}, {ids[1], &a.p.grhoy},
+                              {ids[2], &a.p.grhoz}, {ids[3], &a.p.dwdh}, {ids[4], &a.p.div}}));
+    if (a.p.iterate) {
+        const int ph0 = sph_prop_register("h0"), pom = sph_prop_register("omega"), pah = sph_prop_register("ah"),
+                  pcv = sph_prop_register("converged");
+        if (ph0 < 0 || pom < 0 || pah < 0 || pcv < 0) return SPH_ERR_ARG;
+        SPH_TRY(need_prop(c, dst, ph0, "SummationDensity of gas dynamics (h0)"));
+        SPH_TRY(need_prop(c, dst, pcv, "SummationDensity of gas dynamics (converged)"));
+        SPH_TRY(need_prop(c, dst, SPH_M, "SummationDensity of gas dynamics (m)"));
+        SPH_TRY(bind_out(L, {{pom, &a.p.omega}, {pah, &a.p.ah}}));
+        a.p.m = D.prop[SPH_M]; a.p.h0 = D.prop[ph0]; a.p.h = D.prop[SPH_H];
+        a.p.converged = D.prop[pcv];
+        if (c->gasd_skip && wave_tiles(c)) {
+            // the raw arho of every row is kept by every sweep; a repeated call may use what the previous one kept
+            const bool had = D.gasd_araw.ptr && D.gasd_araw.bytes >= D.n * sizeof(double);
+            SPH_TRY(D.gasd_araw.reserve(D.n * sizeof(double), true, c->stream));
+            a.p.araw = D.gasd_araw.as<double>();
+            a.p.skip = c->gasd_repeat && had;
+        }
+        SPH_TRY(c->gen_state.reserve(SPH_GEN_MAX_STATE * sizeof(double)));
+        a.p.flag = c->gen_state.as<uint32_t>();
+        HIP_TRY(hipMemsetAsync(a.p.flag, 0, 2 * sizeof(uint32_t), c->stream));
+    }
+    SPH_TRY(launch_pair<F>(c, L.K->kind, a, L.rl.record_f32));
+    if (a.p.iterate) {
+        uint32_t word[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(word, a.p.flag, sizeof word, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->gasd_unconverged |= word[0];
+        c->timers[T_N_GASD_SKIP].count += word[1];
+        // h changed behind the neighbour grid (as UpdateSmoothingLengthFerrari in run_nosrc)
+        sph_mark_written(D, SPH_H);
+        c->uniform_h = false;
+    }
+    return SPH_OK;
+}
+template <class F> static int run_mpm(const PairLaunch &L)
+{
+    const DevArray &D = L.c->arr[L.P.dst];
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *me = L.P.eq_of[SPH_EQ_MPM_ACCELERATIONS]; // par beta sigma alpha1_min alpha2_min update_alpha1 update_alpha2
+    a.p.beta = me->par[0]; a.p.sigma = me->par[1]; a.p.alpha1_min = me->par[2]; a.p.alpha2_min = me->par[3];
+    a.p.update_alpha1 = me->par[4] != 0.0; a.p.update_alpha2 = me->par[5] != 0.0;
+    const int pa1 = sph_prop_register("alpha1"), pa2 = sph_prop_register("alpha2"), paa1 = sph_prop_register("aalpha1"),
+              paa2 = sph_prop_register("aalpha2"), pd2 = sph_prop_register("del2e"), pdv = sph_prop_register("div"),
+              pom = sph_prop_register("omega");
+    if (pa1 < 0 || pa2 < 0 || paa1 < 0 || paa2 < 0 || pd2 < 0 || pdv < 0 || pom < 0) return SPH_ERR_ARG; // (the records carry omega, alpha1, alpha2)
+    SPH_TRY(bind_out(L, {{SPH_AU, &a.p.au}, {SPH_AV, &a.p.av}, {SPH_AW, &a.p.aw}, {SPH_AE, &a.p.ae}, {SPH_DT_CFL, &a.p.dt_cfl},
+                              {paa1, &a.p.aalpha1}, {paa2, &a.p.aalpha2}, {pd2, &a.p.del2e}}));
+    if (a.p.update_alpha1) SPH_TRY(need_prop(L.c, L.P.dst, pdv, "MPMAccelerations (div)"));
+    a.p.h = D.prop[SPH_H]; a.p.cs = D.prop[SPH_CS]; a.p.e = D.prop[SPH_E]; a.p.div = D.prop[pdv];
+    a.p.alpha1 = D.prop[pa1]; a.p.alpha2 = D.prop[pa2];
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+
+// the family instantiation the plan and the records name, in the arithmetic type of the records
+static int launch_family(const PairLaunch &L)
+{
+    const int fam = L.P.fam;
+    const RecordKind kind = L.rl.kind;
+    const bool g7 = tait_gk(L.g->eos_par[2]) == 3; // the usual exponent: kernels that fold it
+// RUN(binder, family in T): T = float with fp32 arithmetic (option arith_f32), else double
+#define RUN(BIND, ...)                                                      \
+    do {                                                                    \
+        if (L.rl.arith_f32) { using T = float; return BIND<__VA_ARGS__>(L); } \
+        else { using T = double; return BIND<__VA_ARGS__>(L); }               \
+    } while (0)
+    if (fam == FAM_WCSPH && kind == REC_EOSF && L.rl.umass && g7) RUN(run_wcsph, FamWCSPHE_T<T, true>);
+    if (fam == FAM_WCSPH && kind == REC_EOSF && g7) RUN(run_wcsph, FamWCSPHE_T<T>);
+    if (fam == FAM_WCSPH && kind == REC_EOSF && L.rl.umass) RUN(run_wcsph, FamWCSPHEG_T<T, true>);
+    if (fam == FAM_WCSPH && kind == REC_EOSF) RUN(run_wcsph, FamWCSPHEG_T<T>);
+    if (fam == FAM_WCSPH && kind == REC_EOSV) RUN(run_wcsph, FamWCSPHV_T<T>);
+    if (fam == FAM_WCSPH) RUN(run_wcsph, FamWCSPH_T<T>);
+    if (fam == FAM_WCSPHX && (L.P.dflags & F_DCONT)) RUN(run_wcsphx, FamWCSPHX_T<T, true>); // (the records carry gradrho)
+    if (fam == FAM_WCSPHX) RUN(run_wcsphx, FamWCSPHX_T<T, false>);
+    if (fam == FAM_DSPRE) RUN(run_dspre, FamDSPre_T<T>);
+    if (fam == FAM_DENSITY) RUN(run_density, FamDensity_T<T>);
+    if (fam == FAM_AVGP) RUN(run_avgp, FamAvgP_T<T>);
+    if (fam == FAM_GASSD) RUN(run_gassd, FamGasSD_T<T>);
+    if (fam == FAM_MPM) RUN(run_mpm, FamMPM_T<T>);
+    if (fam == FAM_EDAC && (L.P.dflags & F_EINT)) RUN(run_edac, FamEDAC_T<T, true>);
+    if (fam == FAM_EDAC) RUN(run_edac, FamEDAC_T<T, false>);
+    if (fam == FAM_VGRAD) RUN(run_vgrad, FamVGrad_T<T>);
+    if (fam == FAM_ELASTIC && kind == REC_ELU) RUN(run_elastic, FamElasticU_T<T>);
+    if (fam == FAM_ELASTIC) RUN(run_elastic, FamElastic_T<T>);
+    if (kind == REC_TVFF) RUN(run_tvf, FamTVFE_T<T>);
+    RUN(run_tvf, FamTVF_T<T>);
+#undef RUN
+}
+
 extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *g, double t, double dt)
 {
     if (!c || !K || !g) { sph_set_error("sph_eval_group: NULL argument"); return SPH_ERR_ARG; }
-    c->cur_dt = dt;
     c->gasd_unconverged = 0;
     if (g->neq > SPH_MAX_EQS) { sph_set_error("sph_eval_group: too many equations"); return SPH_ERR_ARG; }
     SPH_TRY(check_kernel("sph_eval_group", K));
@@ -2898,7 +3546,6 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
     // they are packed (pack_array); everything else runs it here, first, and goes on as for 1.
     sph_group g_run;
     bool eos_pending = false;
-    c->cur_eos_abs = false;
     if (g->src_eos == 3) {
         g_run = *g;
         g_run.src_eos = 1;
@@ -2908,647 +3555,55 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
     }
     {
         bool done = false;
-        SPH_TRY(eval_group_merged(c, K, g, t, &done));
+        SPH_TRY(eval_group_merged(c, K, g, t, dt, &done));
         if (done) return SPH_OK;
     }
-
-    // destinations in first-appearance order (acceleration_eval.py:126-131)
     int dests[SPH_MAX_ARRAYS], ndest = 0;
-    for (int i = 0; i < g->neq; i++) {
-        int d = g->eqs[i].dest;
-        if (d < 0 || d >= SPH_MAX_ARRAYS || !c->arr[d].used) { sph_set_error("equation %d: bad dest array %d", i, d); return SPH_ERR_ARG; }
-        bool seen = false;
-        for (int j = 0; j < ndest; j++) seen |= dests[j] == d;
-        if (!seen) dests[ndest++] = d;
-    }
-    const int phase = g->phase;
-    if (phase < 0 || phase > 2 || (phase != 0 && ndest != 1)) {
-        sph_set_error("sph_eval_group: phase %d needs a group with one destination array", phase);
-        return SPH_ERR_ARG;
-    }
+    SPH_TRY(resolve_destinations(c, g, dests, &ndest));
     for (int di = 0; di < ndest; di++) {
-        const int dst = dests[di];
-        DevArray &D = c->arr[dst];
-        // NP_DEST / D_START_IDX (acceleration_eval_cython_helper.py:259-280)
-        size_t start = g->start_idx > 0 ? (size_t)g->start_idx : 0;
-        size_t stop = g->stop_idx >= 0 ? (size_t)g->stop_idx : (g->real ? D.n_real : D.n);
-        if (stop > D.n) stop = D.n;
-
-        // 1. equations without sources run first (mako :50-58); phase 2: over the particles that arrived since phase 1
-        const size_t ns_start = phase == 2 ? std::max(start, D.n_binned) : start;
-        for (int i = 0; i < g->neq; i++) {
-            const sph_equation &e = g->eqs[i];
-            if (e.dest != dst || e.nsrc != 0) continue;
-            if (!is_nosrc_kind(e.kind)) { sph_set_error("equation kind %d needs sources", e.kind); return SPH_ERR_UNSUPPORTED; }
-            SPH_TRY(run_nosrc(c, e, ns_start, stop));
-            c->pack_cache[dst].epoch = 0; // its properties changed: records packed for an earlier destination are stale
-        }
-
-        // 2. sources in first-appearance order with their equation flags (acceleration_eval.py:136-151)
-        int srcs[SPH_MAX_ARRAYS], nsrcs = 0;
-        uint32_t sflags[SPH_MAX_ARRAYS] = {};
-        int fam = FAM_NONE;
-        const sph_equation *eq_of[64] = {};
-        bool elastic = false;
-        for (int i = 0; i < g->neq; i++) {
-            const sph_equation &e = g->eqs[i];
-            if (e.dest == dst && e.nsrc > 0 &&
-                (e.kind == SPH_EQ_MOMENTUM_WITH_STRESS || e.kind == SPH_EQ_MONAGHAN_ART_VISCOSITY))
-                elastic = true;
-        }
-        bool wcsphx = false; // a delta-SPH / laminar-viscosity term on this destination: the WCSPH-options family
-        for (int i = 0; i < g->neq; i++) wcsphx |= g->eqs[i].dest == dst && g->eqs[i].nsrc > 0 && is_wcsph_option_kind(g->eqs[i].kind);
-        bool edac = false, avgp = false; // an EDAC force equation / ComputeAveragePressure on this destination
-        for (int i = 0; i < g->neq; i++) {
-            const bool here = g->eqs[i].dest == dst && g->eqs[i].nsrc > 0;
-            edac |= here && is_edac_force_kind(g->eqs[i].kind);
-            avgp |= here && g->eqs[i].kind == SPH_EQ_EDAC_AVG_PRESSURE;
-        }
-        int eq_pos[64] = {};
-        for (int i = 0; i < g->neq; i++) {
-            const sph_equation &e = g->eqs[i];
-            if (e.dest != dst || e.nsrc == 0) continue;
-            if (e.kind < 0 || e.kind >= 64) { sph_set_error("bad equation kind %d", e.kind); return SPH_ERR_ARG; }
-            uint32_t flag = 0;
-            int f = eq_family(e.kind, &flag, elastic, wcsphx, edac, avgp);
-            eq_pos[e.kind] = i;
-            if (f == FAM_NONE) { sph_set_error("equation kind %d has no hand-written pair kernel", e.kind); return SPH_ERR_UNSUPPORTED; }
-            if (fam != FAM_NONE && f != fam) {
-                sph_set_error("group mixes equation families on destination %d (kinds are fused per family)", dst);
-                return SPH_ERR_UNSUPPORTED;
-            }
-            fam = f;
-            if (eq_of[e.kind]) {
-                sph_set_error("equation kind %d appears twice for destination %d in one group", e.kind, dst);
-                return SPH_ERR_UNSUPPORTED;
-            }
-            eq_of[e.kind] = &e;
-            for (int k = 0; k < e.nsrc; k++) {
-                int s = e.src[k], pos = -1;
-                if (s < 0 || s >= SPH_MAX_ARRAYS || !c->arr[s].used) { sph_set_error("bad source array %d", s); return SPH_ERR_ARG; }
-                for (int j = 0; j < nsrcs; j++) if (srcs[j] == s) pos = j;
-                if (pos < 0) { pos = nsrcs; srcs[nsrcs++] = s; }
-                sflags[pos] |= flag;
-            }
-        }
-        if (fam == FAM_NONE) continue;
-        if (!c->nnps_valid) { sph_set_error("sph_eval_group: neighbour grid is stale; call sph_nnps_update"); return SPH_ERR_STATE; }
-        if (D.nnps_slot < 0) { sph_set_error("destination array %d is not part of the neighbour grid", dst); return SPH_ERR_STATE; }
-        SPH_TRY(nnps_need_tables(c)); // the per-destination path reads every array's own cell order
-        uint32_t dflags = 0;
-        for (int j = 0; j < nsrcs; j++) {
-            dflags |= sflags[j];
-            if (c->arr[srcs[j]].nnps_slot < 0) { sph_set_error("source array %d is not part of the neighbour grid", srcs[j]); return SPH_ERR_STATE; }
-        }
-        if (fam == FAM_WCSPHX) {
-            // the extra terms add into the sums of the Continuity / Momentum equations, whose finish() writes them
-            if ((dflags & F_DCONT) && !(dflags & F_CONT)) { sph_set_error("ContinuityEquationDeltaSPH needs a ContinuityEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
-            if ((dflags & (F_DMOM | F_LAM | F_LAMD)) && !(dflags & F_MOM)) { sph_set_error("the delta-SPH / laminar viscosity terms need a MomentumEquation on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
-            if ((dflags & F_LAM) && (dflags & F_LAMD)) { sph_set_error("both LaminarViscosity and LaminarViscosityDeltaSPH on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
-        }
-        if (fam == FAM_EDAC) {
-            if (eq_of[SPH_EQ_EDAC_MOMENTUM] && eq_of[SPH_EQ_EDAC_MOM_PRESSURE]) { sph_set_error("both EDAC pressure-gradient forms on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
-            if ((dflags & F_EINT) && (dflags & F_EXS)) { sph_set_error("XSPHCorrection next to the internal-flow EDAC pressure gradient on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
-            if (!(dflags & F_EINT) && (dflags & F_TAS)) { sph_set_error("MomentumEquationArtificialStress next to the external-flow EDAC equations on destination %d", dst); return SPH_ERR_UNSUPPORTED; }
-            // the branch is a property of the destination: one instantiation per branch, and equal flag sets on the
-            // sources of a default group so that the compile-time set applies
-            if (dflags & F_EINT) for (int j = 0; j < nsrcs; j++) sflags[j] |= F_EINT;
-        }
-        if (fam == FAM_DSPRE) {
-            // the moment matrix must be complete before a corrected gradient reads it: a group of its own, as in WCSPHScheme
-            if ((dflags & F_MOMENT) && (dflags & (F_GRADRHO | F_GCORR))) {
-                sph_set_error("GradientCorrectionPreStep shares a group with GradientCorrection / ContinuityEquationDeltaSPHPreStep on destination %d; put it in a group of its own before them", dst);
-                return SPH_ERR_UNSUPPORTED;
-            }
-            // GradientCorrection rewrites DWIJ for the equations AFTER it: behind the pre-step it corrects nothing
-            if ((dflags & F_GCORR) && (!(dflags & F_GRADRHO) || eq_pos[SPH_EQ_GRADIENT_CORRECTION] > eq_pos[SPH_EQ_CONTINUITY_DELTA_SPH_PRESTEP])) {
-                dflags &= ~(uint32_t)F_GCORR;
-                for (int j = 0; j < nsrcs; j++) sflags[j] &= ~(uint32_t)F_GCORR;
-            }
-            if (!dflags) continue;
-            for (int j = 0; j < nsrcs; j++) if ((sflags[j] & F_GCORR) && !(sflags[j] & F_GRADRHO)) sflags[j] &= ~(uint32_t)F_GCORR;
-        }
-        if ((fam == FAM_WCSPH || fam == FAM_WCSPHX) && eq_of[SPH_EQ_MOMENTUM] && eq_of[SPH_EQ_MOMENTUM]->par[6] != 0.0) {
-            dflags |= F_TENSILE;
-            for (int j = 0; j < nsrcs; j++) if (sflags[j] & F_MOM) sflags[j] |= F_TENSILE;
-        }
-
-        // 3. pack destination + sources into cell order
-        size_t total = 0, off_of[SPH_MAX_ARRAYS];
-        bool dest_is_src = false;
-        for (int j = 0; j < nsrcs; j++) { off_of[j] = total; total += c->arr[srcs[j]].n; dest_is_src |= srcs[j] == dst; }
-        size_t d_off = total;
-        if (!dest_is_src) total += D.n;
-        else for (int j = 0; j < nsrcs; j++) if (srcs[j] == dst) d_off = off_of[j];
-        // WCSPH groups with several destinations (a dam break: fluid, boundary, obstacle) read the
-        // SAME source records, and nothing the family writes (accelerations) is part of a record:
-        // one buffer slot per neighbour-grid array, each array packed once per group instead of
-        // once per destination that reads it (dam break C2: 7 -> 3 k_pack launches per evaluation).
-        // The host brackets the per-destination calls of one group with option pack_group 1 / 0.
-        const bool share = fam == FAM_WCSPH && c->pair_variant >= 3 && (ndest > 1 || c->pack_group);
-        if (share) {
-            size_t goff[SPH_MAX_ARRAYS] = {};
-            total = 0;
-            for (int a = 0; a < c->narrays; a++) { goff[c->ids[a]] = total; total += c->arr[c->ids[a]].n; }
-            for (int j = 0; j < nsrcs; j++) off_of[j] = goff[srcs[j]];
-            d_off = goff[dst];
-        }
-        if (total >= (1ull << 32)) { sph_set_error("too many particles for 32-bit packed indices"); return SPH_ERR_ARG; }
-        // ghost split (sph_nnps_update_ghosts): arrays whose ghosts were binned after the real particles carry them as a
-        // second record segment and a second source; the destinations are the particles the update binned
-        bool any_ghosts = false;
-        for (int j = 0; j < nsrcs; j++) any_ghosts |= c->arr[srcs[j]].g_n > 0;
-        any_ghosts |= D.g_n > 0;
-        if (phase != 0 && !(nsrcs == 1 && srcs[0] == dst && !share)) {
-            sph_set_error("sph_eval_group: phases need a group over ONE array (destination == its only source)");
-            return SPH_ERR_UNSUPPORTED;
-        }
-        if ((any_ghosts || phase != 0) && c->pair_variant != 6) {
-            sph_set_error("ghost segments (sph_nnps_update_ghosts) need pair_variant 6");
-            return SPH_ERR_UNSUPPORTED;
-        }
-        if (!dest_is_src && D.n_binned != D.n) {
-            // a destination-only array is read through its own records only: its ghosts are no destinations
-        }
-        PackPlan pl = pack_plan(fam);
-        const bool wx_ds = fam == FAM_WCSPHX && (dflags & F_DCONT); // the records carry the sources' gradrho
-        if (wx_ds) {
-            for (int k = 0; k < 3; k++) pl.props[8 + k] = SPH_GRADRHO0 + k;
-            pl.na = 11; pl.nr = 16;
-        }
-        // compact 80-B WCSPH records when neither h nor p of a neighbour is read
-        if (c->pair_variant >= 3 && fam == FAM_WCSPH && c->uniform_h && c->use_uniform_h && !(dflags & F_TENSILE)) pl.nr = c->wcsph_nr ? (int)c->wcsph_nr : 10;
-        if (c->pair_variant >= 3 && fam == FAM_DENSITY && c->uniform_h && c->use_uniform_h) pl.nr = 4;
-        if (c->pair_variant >= 3 && fam == FAM_TVF && c->uniform_h && c->use_uniform_h) pl.nr = (dflags & F_TAV) ? 14 : 12;
-        if (c->pair_variant >= 3 && fam == FAM_EDAC && c->uniform_h && c->use_uniform_h) pl.nr = 14; // (m always: load_record_edac)
-        if (c->pair_variant >= 3 && (c->record_f32 || c->arith_f32)) pl.nr = (4 + pl.na + 3) & ~3; // floats
-        // The caller promised (sph_group.src_eos) that p, cs of every array read here are the Tait EOS of its
-        // rho: with gamma = 7 (powers by multiplication), uniform h and no tensile correction the pair kernel
-        // recomputes them and the records shrink to 64 bytes (32 in fp32).
-        const bool eosf = g->src_eos == 1 && c->eos_fuse && fam == FAM_WCSPH && c->pair_variant == 6 && c->uniform_h &&
-                          c->use_uniform_h && !(dflags & F_TENSILE) && tait_gk(g->eos_par[2]) >= 0 &&
-                          g->eos_par[0] > 0.0 && !c->record_f32 && !c->wcsph_nr;
-        if (eosf) pl.nr = 8; // doubles, or floats with arith_f32
-        // ... and when every array read here had ONE mass at the last neighbour update, the record's mass slot
-        // carries p / rho^2 and most of the per-record EOS goes as well (FamWCSPHE_T<T, true>)
-        // (only with the equation flags as a compile-time constant: the run-time-flag kernel of a dam break's three
-        // sources is at its scalar-register limit and 1-3 % slower with a mass per source)
-        bool umass = eosf && c->mass_fuse && c->const_flags;
-        for (int j = 0; j < nsrcs && umass; j++) umass = sflags[j] == FamWCSPH::CF0;
-        if (umass) c->want_mrange = true; // the reduction of the neighbour updates from now on includes m (8 B per particle)
-        for (int j = 0; j < nsrcs && umass; j++) umass = c->arr[srcs[j]].m_known;
-        // ... and with VARIABLE h the same promise plus one mass per source array gives 64-byte records [x y z h u v w rho]
-        bool eosv = !eosf && g->src_eos == 1 && c->eos_fuse && c->mass_fuse && fam == FAM_WCSPH && c->pair_variant == 6 &&
-                    !(c->uniform_h && c->use_uniform_h) && !(dflags & F_TENSILE) && tait_gk(g->eos_par[2]) == 3 && g->eos_par[0] > 0.0 &&
-                    !c->record_f32 && !c->wcsph_nr;
-        if (eosv) c->want_mrange = true;
-        for (int j = 0; j < nsrcs && eosv; j++) eosv = c->arr[srcs[j]].m_known;
-        if (eosv) pl.nr = 8;
-        c->cur_eosv = eosv;
-        // TVF force pass after StateEquation + density summation (sph_group.src_eos = 2): p and V leave the records
-        // when every array read here has ONE mass (V = rho / m)
-        bool tvff = g->src_eos == 2 && c->eos_fuse && c->mass_fuse && fam == FAM_TVF && c->pair_variant == 6 && c->uniform_h &&
-                    c->use_uniform_h && !c->record_f32 && g->eos_par[1] != 0.0; // (the artificial viscosity's m_j is the source's one mass)
-        if (tvff) c->want_mrange = true;
-        for (int j = 0; j < nsrcs && tvff; j++) tvff = c->arr[srcs[j]].m_known;
-        if (tvff && !dest_is_src) tvff = D.m_known;
-        if (tvff) pl.nr = c->arith_f32 ? ((dflags & F_TAS) ? 12 : 8) : ((dflags & F_TAS) ? 10 : 8);
-        // elastic rates: uniform h and ONE mass per source array -> neither travels in the records
-        bool elu = fam == FAM_ELASTIC && c->mass_fuse && c->pair_variant == 6 && c->uniform_h && c->use_uniform_h && !c->record_f32;
-        if (elu) c->want_mrange = true;
-        for (int j = 0; j < nsrcs && elu; j++) elu = c->arr[srcs[j]].m_known;
-        if (elu) pl.nr = 20; // doubles, or floats with arith_f32
-        c->cur_elu = elu;
-        c->cur_tvff = tvff;
-        c->cur_umass = umass;
-        c->cur_eosf = eosf;
-        c->cur_nrec = pl.nr;
-        // The Tait EOS the host left to this call: absorbed by the records when they are the EOS-fused ones of ONE array
-        // and the pack launches below visit every particle of it (both segments); else run now, over all of every array
-        c->cur_eos_abs = false;
-        if (eos_pending) {
+        DestPlan plan;
+        plan.dst = dests[di]; plan.ndest = ndest; plan.phase = g->phase;
+        const DevArray &D = c->arr[plan.dst];
+        plan.start = g->start_idx > 0 ? (size_t)g->start_idx : 0;
+        plan.stop = g->stop_idx >= 0 ? (size_t)g->stop_idx : (g->real ? D.n_real : D.n);
+        if (plan.stop > D.n) plan.stop = D.n;
+        SPH_TRY(run_nosrc_equations(c, g, plan.dst, plan.start, plan.stop));
+        SPH_TRY(plan_destination(c, g, plan));
+        const DestPlan &P = plan;
+        if (P.fam == FAM_NONE) continue;
+        const RecordLayout rl = choose_records(c, g, P, eos_pending);
+        if (eos_pending) { // the Tait EOS the host left to this call: with the records (pack_array), or now, over all of every array
             eos_pending = false;
-            // (gamma = 7 only: the other odd exponents keep the EOS kernel)
-            const bool absorb = (eosf || eosv) && c->eos_absorb && tait_gk(g->eos_par[2]) == 3 && phase == 0 && ndest == 1 &&
-                                nsrcs == 1 && srcs[0] == dst && D.n > 0 && D.n_binned + D.g_n == D.n;
-            if (absorb) {
-                SPH_TRY(need_prop(c, dst, SPH_RHO, "EOS"));
-                SPH_TRY(sph_array_ensure_prop(c, dst, SPH_P));
-                SPH_TRY(sph_array_ensure_prop(c, dst, SPH_CS));
-                c->cur_eos_abs = true;
-                for (int k = 0; k < 4; k++) c->cur_eos_par[k] = g->eos_par[k];
-                c->pack_cache[dst].epoch = 0; // the records are packed now, whatever an earlier destination left
+            if (rl.eos_abs) {
+                SPH_TRY(need_prop(c, P.dst, SPH_RHO, "EOS"));
+                SPH_TRY(sph_array_ensure_prop(c, P.dst, SPH_P));
+                SPH_TRY(sph_array_ensure_prop(c, P.dst, SPH_CS));
+                c->pack_cache[P.dst].epoch = 0; // the records are packed now, whatever an earlier destination left
                 c->timers[T_N_EOSABS].count++;
             } else {
                 SPH_TRY(run_pending_eos(c, g));
             }
         }
-        const void *rec_was = c->posh.ptr, *fpos_was = c->fposb.ptr;
-        // phase 1 leaves room for the ghosts phase 2 packs behind the real particles' records (the array's capacity bounds
-        // them); phase 2 keeps what phase 1 packed should the buffers have to grow after all
-        const size_t total_res = phase == 1 ? std::max(total, D.cap) : total;
-        SPH_TRY(c->posh.reserve((total_res + 64) * sizeof(double) * (c->pair_variant >= 2 ? pl.nr : 4), phase == 2, c->stream));
-        SPH_TRY(c->aux.reserve((total_res + 64) * sizeof(double) * pl.na));
-        if (c->pair_variant >= 3) SPH_TRY(c->fposb.reserve((total_res + 64) * sizeof(float4), phase == 2, c->stream));
-        if (c->posh.ptr != rec_was || c->fposb.ptr != fpos_was) // the buffers moved: nothing packed earlier is there
-            for (auto &pc : c->pack_cache) pc.epoch = 0;
-        {
-            ScopedTimer tm(c, T_PACK);
-            // a source must hold what ITS equations read; the destination's own record what all of them read
-            const int sig = pl.nr * 32 + (c->record_f32 ? 1 : 0) + (c->arith_f32 ? 2 : 0) + (eosf ? 4 : 0) + (umass ? 8 : 0) + (tvff || elu || eosv ? 16 : 0);
-            // The shared slots live in the same buffers every other unit packs into from offset 0:
-            // a unit that does not share (another family, a single-destination call), or one whose
-            // record layout differs from what the cache holds, overwrites them -- nothing cached survives.
-            // a split evaluation: the second half must read the layout the first half packed -- when what is known of the
-            // masses changed in between (a ghost with another mass: sph_nnps_update_ghosts), it packs both segments again
-            if (phase == 1) c->phase_sig = sig;
-            const bool repack = phase == 2 && c->phase_sig != sig;
-            bool keep = share;
-            if (share)
-                for (auto &pc : c->pack_cache)
-                    if (pc.epoch == c->pack_epoch && (pc.fam != fam || pc.sig != sig)) keep = false;
-            if (!keep)
-                for (auto &pc : c->pack_cache) pc.epoch = 0;
-            auto pack_once = [&](int id, size_t off, uint32_t fl, bool dest_only) -> int {
-                PackCache &pc = c->pack_cache[id];
-                const bool hit = share && pc.epoch == c->pack_epoch && pc.fam == fam && pc.sig == sig;
-                // phase 1: the particles present (the real ones); phase 2: the ghosts that arrived since; else both segments
-                if (phase != 2 || repack) SPH_TRY(pack_array(c, id, off, pl, fam, fl, dest_only, !hit, 0)); // a hit still validates
-                if (phase != 1 && c->arr[id].g_n > 0) SPH_TRY(pack_array(c, id, off, pl, fam, fl, dest_only, !hit, 1));
-                pc.epoch = share ? c->pack_epoch : 0; pc.fam = fam; pc.sig = sig;
-                return SPH_OK;
-            };
-            for (int j = 0; j < nsrcs; j++) SPH_TRY(pack_once(srcs[j], off_of[j], srcs[j] == dst ? dflags : sflags[j], false));
-            if (!dest_is_src) SPH_TRY(pack_once(dst, d_off, dflags, true));
-        }
-        c->cur_eos_abs = false;
-
-        // Neighbour-list reuse between the pair passes of one evaluation (sph_group.nl_mode): one source,
-        // the wave-tile kernel, same grid.  A pass that keeps its lists (1) records what they belong to; a pass
-        // that wants them (2) gets them only if that record matches -- otherwise it runs its own phase 1.
+        SPH_TRY(pack_records(c, P, rl));
         int nl_mode = 0;
-        if (c->nl_reuse && !c->row_lds && c->pair_variant == 6 && nsrcs == 1 && g->nl_mode && !c->ablate && !any_ghosts && phase == 0) {
-            const size_t n_wt = (size_t)4 * div_up(D.n, 256);
-            if (g->nl_mode == 1) {
-                SPH_TRY(c->nlbuf.reserve(n_wt * NLW * sizeof(uint32_t)));
-                c->nl.valid = true; c->nl.epoch = c->nnps_epoch; c->nl.dst = dst; c->nl.src = srcs[0];
-                c->nl.start = start; c->nl.stop = stop; c->nl.nd = D.n;
-                nl_mode = 1;
-            } else if (g->nl_mode == 2 && c->nl.valid && c->nl.epoch == c->nnps_epoch && c->nl.dst == dst && c->nl.src == srcs[0] &&
-                       c->nl.nd == D.n && c->nl.start <= start && c->nl.stop >= stop && c->nlbuf.bytes >= n_wt * NLW * sizeof(uint32_t)) {
-                nl_mode = 2;
-            }
-        } else if (g->nl_mode != 2) {
-            c->nl.valid = c->nl.valid && !(g->nl_mode == 1); // a keeping pass that could not keep: nothing to reuse
-        }
-
+        SPH_TRY(choose_nl_mode(c, g, P, &nl_mode));
         // Split evaluations (sph_group.phase): by default the first half only prepares (equations without sources, records
         // of the particles present) and the second half launches EVERY wave tile once the ghosts are in -- the ghost
         // segments guarded per wavefront; option split_pair 1: the interior tiles in the first half, the face tiles in
         // the second (hides a transfer longer than the neighbour update + packing; costs a second, sparse launch)
-        if (phase == 1 && !c->split_pair) continue;
-        // 4. fused pair kernel, in the arithmetic type of the context (fp64, or fp32 with option arith_f32)
+        if (P.phase == 1 && !c->split_pair) continue;
+        // the fused pair kernel, in the arithmetic type of the records (fp64, or fp32 with option arith_f32)
         ScopedTimer tm(c, T_PAIR);
-        ScopedTimer tmf(c, T_PAIR_FAM + fam);
-        if (phase == 2) c->timers[T_N_PHASE2].count++;
-        if (eosf || tvff || eosv) c->timers[T_N_EOSF].count++;
-        if (umass || tvff || elu || eosv) c->timers[T_N_UMASS].count++;
+        ScopedTimer tmf(c, T_PAIR_FAM + P.fam);
+        if (P.phase == 2) c->timers[T_N_PHASE2].count++;
+        if (rl.eos_fused() || rl.kind == REC_TVFF) c->timers[T_N_EOSF].count++;
+        if (rl.umass || rl.kind == REC_TVFF || rl.kind == REC_ELU || rl.kind == REC_EOSV) c->timers[T_N_UMASS].count++;
         if (nl_mode == 1) c->timers[T_N_NLKEEP].count++;
         if (nl_mode == 2) c->timers[T_N_NLREUSE].count++;
-        // the part of the launch arguments every family shares
-        {
-            int nseg = nsrcs;
-            for (int j = 0; j < nsrcs; j++) nseg += c->arr[srcs[j]].g_n > 0 && phase != 1;
-            if (nseg > SPH_MAX_ARRAYS) { sph_set_error("too many source segments (%d arrays with ghost segments)", nsrcs); return SPH_ERR_UNSUPPORTED; }
-        }
-        auto common = [&](auto &a) {
-            fill_common(c, a, K, t);
-            a.nsrc = 0;
-            for (int j = 0; j < nsrcs; j++) {
-                const DevArray &S = c->arr[srcs[j]];
-                a.src[a.nsrc++] = {S.cell_start.as<uint32_t>(), (uint32_t)off_of[j], sflags[j], S.fine_start.as<uint32_t>(), S.m_value, 0u};
-            }
-            for (int j = 0; j < nsrcs && phase != 1; j++) { // the ghost segments, after every array's first segment
-                const DevArray &S = c->arr[srcs[j]];
-                if (S.g_n == 0) continue;
-                a.src[a.nsrc++] = {S.g_cell_start.as<uint32_t>(), (uint32_t)(off_of[j] + S.n_binned), sflags[j],
-                                   S.g_fine_start.as<uint32_t>(), S.m_value, 1u};
-            }
-            a.face_mode = c->split_pair ? phase : 0;
-            a.d_off = (uint32_t)d_off; a.nd = (uint32_t)D.n_binned;
-            a.d_mu = D.m_value;
-            a.d_keys = D.keys_sorted.as<uint32_t>(); a.d_fkeys = D.fkeys_sorted.as<uint32_t>(); a.d_perm = D.perm.as<uint32_t>();
-            set_tile_order(c, a, D);
-            a.d_start = (uint32_t)start; a.d_stop = (uint32_t)stop; a.dflags = dflags;
-            a.nl = nullptr; a.nl_mode = nl_mode;
-            if (nl_mode) a.nl = c->nlbuf.as<uint32_t>();
-            // Group.real = True without start / stop: the destinations are the real particles
-            if (start == 0 && stop == D.n_real && D.n_binned == D.n && !any_ghosts) use_dest_list(c, a, D);
-            if (eosf || eosv) {
-                a.e_rho01 = 1.0 / g->eos_par[0]; a.e_c0 = g->eos_par[1];
-                a.e_B = g->eos_par[0] * g->eos_par[1] * g->eos_par[1] / g->eos_par[2];
-        a.e_gk = tait_gk(g->eos_par[2]);
-                a.e_p0 = g->eos_par[3];
-            }
-            if (tvff) { a.e_p0 = g->eos_par[0]; a.e_rho01 = 1.0 / g->eos_par[1]; a.e_B = g->eos_par[2]; } // StateEquation: p0 rho0 b
-        };
-        auto run_wcsph = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *me = eq_of[SPH_EQ_MOMENTUM], *xe = eq_of[SPH_EQ_XSPH];
-            if (me) { a.p.c0 = me->par[0]; a.p.alpha = me->par[1]; a.p.beta = me->par[2]; a.p.gx = me->par[3]; a.p.gy = me->par[4]; a.p.gz = me->par[5]; }
-            if (xe) a.p.eps = xe->par[0];
-            if (dflags & F_CONT) { SPH_TRY(ensure_out(c, dst, {SPH_ARHO})); a.p.arho = D.prop[SPH_ARHO]; }
-            if (dflags & F_MOM) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW, SPH_DT_CFL, SPH_DT_FORCE}));
-                a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
-                a.p.dt_cfl = D.prop[SPH_DT_CFL]; a.p.dt_force = D.prop[SPH_DT_FORCE];
-            }
-            if (dflags & F_XSPH) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AX, SPH_AY, SPH_AZ}));
-                a.p.ax = D.prop[SPH_AX]; a.p.ay = D.prop[SPH_AY]; a.p.az = D.prop[SPH_AZ];
-            }
-            if constexpr (std::is_same<F, FamWCSPHV_T<typename F::Real>>::value) return launch_pair_fused<F, false>(c, K->kind, a);
-            else if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(c, K->kind, a);
-            else return launch_pair<F>(c, K->kind, a);
-        };
-        // the WCSPH-options family: FamWCSPH_T's arguments + the parameters of the extra terms
-        auto run_wcsphx = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *me = eq_of[SPH_EQ_MOMENTUM], *xe = eq_of[SPH_EQ_XSPH];
-            const sph_equation *dc = eq_of[SPH_EQ_CONTINUITY_DELTA_SPH], *dm = eq_of[SPH_EQ_MOMENTUM_DELTA_SPH],
-                               *lv = eq_of[SPH_EQ_LAMINAR_VISCOSITY], *ld = eq_of[SPH_EQ_LAMINAR_VISCOSITY_DELTA_SPH];
-            if (me) { a.p.c0 = me->par[0]; a.p.alpha = me->par[1]; a.p.beta = me->par[2]; a.p.gx = me->par[3]; a.p.gy = me->par[4]; a.p.gz = me->par[5]; }
-            if (xe) a.p.eps = xe->par[0];
-            if (dc) a.p.dfac = dc->par[1] * dc->par[0];                  // par c0 delta
-            if (dm) a.p.mfac = dm->par[2] * dm->par[1] * dm->par[0];     // par rho0 c0 alpha
-            if (lv) { a.p.nu4 = 4.0 * lv->par[0]; a.p.eta = lv->par[1]; } // par nu eta
-            if (ld) a.p.lfac = 2.0 * (ld->par[0] + 2.0) * ld->par[2] * ld->par[1]; // par dim rho0 nu
-            if (dflags & F_CONT) { SPH_TRY(ensure_out(c, dst, {SPH_ARHO})); a.p.arho = D.prop[SPH_ARHO]; }
-            if (dflags & F_MOM) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW, SPH_DT_CFL, SPH_DT_FORCE}));
-                a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
-                a.p.dt_cfl = D.prop[SPH_DT_CFL]; a.p.dt_force = D.prop[SPH_DT_FORCE];
-            }
-            if (dflags & F_XSPH) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AX, SPH_AY, SPH_AZ}));
-                a.p.ax = D.prop[SPH_AX]; a.p.ay = D.prop[SPH_AY]; a.p.az = D.prop[SPH_AZ];
-            }
-            return launch_pair<F>(c, K->kind, a);
-        };
-        // the delta-SPH pre-passes: the moment matrix, or the (renormalised) density gradient
-        auto run_dspre = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *pe = eq_of[SPH_EQ_GRADIENT_CORRECTION_PRESTEP], *ge = eq_of[SPH_EQ_GRADIENT_CORRECTION];
-            a.p.mdim = pe ? (int)pe->par[0] : 0;
-            a.p.n = 0;
-            if (dflags & F_GCORR) { a.p.n = (int)ge->par[0]; a.p.tol = ge->par[1]; }
-            if (a.p.mdim < 0 || a.p.mdim > 3 || ((dflags & F_GCORR) && (a.p.n < 1 || a.p.n > 3))) {
-                sph_set_error("GradientCorrection / GradientCorrectionPreStep: dim must be 1, 2 or 3");
-                return SPH_ERR_ARG;
-            }
-            if (dflags & (F_MOMENT | F_GCORR)) {
-                for (int k = 0; k < 9; k++) {
-                    const int pid = SPH_MMAT0 + k;
-                    if (dflags & F_MOMENT) SPH_TRY(sph_array_ensure_prop(c, dst, pid));
-                    else if (!D.prop[pid]) return need_prop(c, dst, pid, "GradientCorrection (m_mat)");
-                    a.p.mm[k] = D.prop[pid];
-                }
-            }
-            if (dflags & F_GRADRHO) {
-                for (int k = 0; k < 3; k++) {
-                    const int pid = SPH_GRADRHO0 + k;
-                    SPH_TRY(sph_array_ensure_prop(c, dst, pid));
-                    a.p.gr[k] = D.prop[pid];
-                }
-            }
-            return launch_pair<F>(c, K->kind, a);
-        };
-        auto run_density = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            SPH_TRY(ensure_out(c, dst, {SPH_RHO}));
-            a.p.rho = D.prop[SPH_RHO];
-            if (dflags & F_TVFSD) { SPH_TRY(ensure_out(c, dst, {SPH_VOL})); a.p.V = D.prop[SPH_VOL]; }
-            if ((dflags & F_SD) && (dflags & F_TVFSD)) { sph_set_error("both SummationDensity flavours on one destination"); return SPH_ERR_UNSUPPORTED; }
-            return launch_pair<F>(c, K->kind, a);
-        };
-        auto run_vgrad = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            static const int vp[9] = {SPH_V00, SPH_V01, SPH_V02, SPH_V10, SPH_V11, SPH_V12, SPH_V20, SPH_V21, SPH_V22};
-            if ((dflags & F_VG2) && (dflags & F_VG3)) { sph_set_error("both VelocityGradient2D and 3D on one destination"); return SPH_ERR_UNSUPPORTED; }
-            for (int k = 0; k < 9; k++) {
-                const bool used = (dflags & F_VG3) || (k == 0 || k == 1 || k == 3 || k == 4);
-                if (used) { SPH_TRY(sph_array_ensure_prop(c, dst, vp[k])); a.p.v[k] = D.prop[vp[k]]; }
-            }
-            return launch_pair<F>(c, K->kind, a);
-        };
-        auto run_elastic = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *se = eq_of[SPH_EQ_MOMENTUM_WITH_STRESS], *ae = eq_of[SPH_EQ_MONAGHAN_ART_VISCOSITY],
-                               *xe = eq_of[SPH_EQ_XSPH];
-            if (se) { a.p.wdeltap = se->par[0]; a.p.n = se->par[1]; }
-            a.p.tension = nullptr;
-            if (elu && c->tension_flag && nsrcs == 1 && c->arr[srcs[0]].tflag_valid && c->arr[srcs[0]].tflag.ptr) {
-                a.p.tension = c->arr[srcs[0]].tflag.as<uint32_t>();
-                c->timers[T_N_TFLAG].count++;
-            }
-            if (ae) { a.p.alpha = ae->par[0]; a.p.beta = ae->par[1]; }
-            if (xe) a.p.eps = xe->par[0];
-            if (dflags & F_ECONT) { SPH_TRY(ensure_out(c, dst, {SPH_ARHO})); a.p.arho = D.prop[SPH_ARHO]; }
-            if (dflags & (F_ESTRESS | F_EAV)) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW}));
-                a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
-            }
-            if (dflags & F_EXSPH) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AX, SPH_AY, SPH_AZ}));
-                a.p.ax = D.prop[SPH_AX]; a.p.ay = D.prop[SPH_AY]; a.p.az = D.prop[SPH_AZ];
-            }
-            if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(c, K->kind, a);
-            else return launch_pair<F>(c, K->kind, a);
-        };
-        auto run_tvf = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *pe = eq_of[SPH_EQ_TVF_MOM_PRESSURE], *ve = eq_of[SPH_EQ_TVF_MOM_VISCOSITY],
-                               *ae = eq_of[SPH_EQ_TVF_MOM_ART_VISCOSITY];
-            if (pe) { a.p.pb = pe->par[0]; a.p.gx = pe->par[1]; a.p.gy = pe->par[2]; a.p.gz = pe->par[3]; a.p.tdamp = pe->par[4]; }
-            if (ve) a.p.nu = ve->par[0];
-            if (ae) { a.p.c0 = ae->par[0]; a.p.alpha = ae->par[1]; }
-            SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW}));
-            a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
-            a.p.m = D.prop[SPH_M];
-            if (dflags & F_TP) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AUHAT, SPH_AVHAT, SPH_AWHAT}));
-                a.p.auhat = D.prop[SPH_AUHAT]; a.p.avhat = D.prop[SPH_AVHAT]; a.p.awhat = D.prop[SPH_AWHAT];
-            }
-            if constexpr (fam_eosf<F>::value) return launch_pair_fused<F>(c, K->kind, a);
-            else return launch_pair<F>(c, K->kind, a);
-        };
-        // the EDAC force group: parameters of its up to six equations; ap and pavg are user properties by name
-        auto run_edac = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *pe = eq_of[SPH_EQ_EDAC_MOM_PRESSURE], *me = eq_of[SPH_EQ_EDAC_MOMENTUM], *ee = eq_of[SPH_EQ_EDAC],
-                               *ve = eq_of[SPH_EQ_TVF_MOM_VISCOSITY], *ae = eq_of[SPH_EQ_TVF_MOM_ART_VISCOSITY], *xe = eq_of[SPH_EQ_XSPH];
-            if (pe) { a.p.pb = pe->par[0]; a.p.gx = pe->par[1]; a.p.gy = pe->par[2]; a.p.gz = pe->par[3]; a.p.tdamp = pe->par[4]; }
-            if (me) { a.p.gx = me->par[1]; a.p.gy = me->par[2]; a.p.gz = me->par[3]; a.p.tdamp = me->par[4]; } // par c0 gx gy gz tdamp
-            if (ve) a.p.nu = ve->par[0];
-            if (ae) { a.p.c0 = ae->par[0]; a.p.alpha = ae->par[1]; }
-            if (ee) { a.p.cs2 = ee->par[0] * ee->par[0]; a.p.enu = ee->par[1]; } // par cs nu rho0
-            if (xe) a.p.eps = xe->par[0];
-            a.p.m = D.prop[SPH_M];
-            if (dflags & (F_EP | F_TVISC | F_TAV | F_TAS)) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW}));
-                a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW];
-            }
-            if (dflags & F_EINT) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AUHAT, SPH_AVHAT, SPH_AWHAT}));
-                a.p.auhat = D.prop[SPH_AUHAT]; a.p.avhat = D.prop[SPH_AVHAT]; a.p.awhat = D.prop[SPH_AWHAT];
-                const int ppavg = sph_prop_register("pavg");
-                if (ppavg < 0) return ppavg;
-                SPH_TRY(need_prop(c, dst, ppavg, "MomentumEquationPressureGradient of EDAC (pavg)"));
-                a.p.pavg = D.prop[ppavg];
-            }
-            if (dflags & F_EDAC) {
-                const int pap = sph_prop_register("ap");
-                if (pap < 0) return pap;
-                SPH_TRY(ensure_out(c, dst, {pap}));
-                a.p.ap = D.prop[pap];
-            }
-            if (dflags & F_EXS) {
-                SPH_TRY(ensure_out(c, dst, {SPH_AX, SPH_AY, SPH_AZ}));
-                a.p.ax = D.prop[SPH_AX]; a.p.ay = D.prop[SPH_AY]; a.p.az = D.prop[SPH_AZ];
-            }
-            return launch_pair<F>(c, K->kind, a);
-        };
-        auto run_avgp = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            if ((dflags & F_SD) && (dflags & F_TVFSD)) { sph_set_error("both SummationDensity flavours on one destination"); return SPH_ERR_UNSUPPORTED; }
-            if (dflags & (F_SD | F_TVFSD)) { SPH_TRY(ensure_out(c, dst, {SPH_RHO})); a.p.rho = D.prop[SPH_RHO]; }
-            if (dflags & F_TVFSD) { SPH_TRY(ensure_out(c, dst, {SPH_VOL})); a.p.V = D.prop[SPH_VOL]; }
-            const int ppavg = sph_prop_register("pavg"), pnn = sph_prop_register("nnbr");
-            if (ppavg < 0 || pnn < 0) return SPH_ERR_ARG;
-            SPH_TRY(ensure_out(c, dst, {ppavg, pnn}));
-            a.p.pavg = D.prop[ppavg]; a.p.nnbr = D.prop[pnn];
-            return launch_pair<F>(c, K->kind, a);
-        };
-        // the gas-dynamics density sweep: when it iterates, the convergence word is cleared before the launch and read
-        // back behind it (one word, one synchronise per call), and h counts as written
-        auto run_gassd = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *se = eq_of[SPH_EQ_GASD_SUMMATION_DENSITY]; // par dim k htol density_iterations iterate_only_once
-            a.p.dim = se->par[0]; a.p.k = se->par[1]; a.p.htol = se->par[2];
-            a.p.iterate = se->par[3] != 0.0; a.p.once = se->par[4] != 0.0;
-            const char *names[5] = {"grhox", "grhoy", "grhoz", "dwdh", "div"};
-            int ids[5];
-            for (int k = 0; k < 5; k++) { ids[k] = sph_prop_register(names[k]); if (ids[k] < 0) return ids[k]; }
-            SPH_TRY(ensure_out(c, dst, {SPH_RHO, SPH_ARHO, ids[0], ids[1], ids[2], ids[3], ids[4]}));
-            a.p.rho = D.prop[SPH_RHO]; a.p.arho = D.prop[SPH_ARHO];
-            a.p.grhox = D.prop[ids[0]]; a.p.grhoy = D.prop[ids[1]]; a.p.grhoz = D.prop[ids[2]];
-            a.p.dwdh = D.prop[ids[3]]; a.p.div = D.prop[ids[4]];
-            if (a.p.iterate) {
-                const int ph0 = sph_prop_register("h0"), pom = sph_prop_register("omega"), pah = sph_prop_register("ah"),
-                          pcv = sph_prop_register("converged");
-                if (ph0 < 0 || pom < 0 || pah < 0 || pcv < 0) return SPH_ERR_ARG;
-                SPH_TRY(need_prop(c, dst, ph0, "SummationDensity of gas dynamics (h0)"));
-                SPH_TRY(need_prop(c, dst, pcv, "SummationDensity of gas dynamics (converged)"));
-                SPH_TRY(need_prop(c, dst, SPH_M, "SummationDensity of gas dynamics (m)"));
-                SPH_TRY(ensure_out(c, dst, {pom, pah}));
-                a.p.m = D.prop[SPH_M]; a.p.h0 = D.prop[ph0]; a.p.h = D.prop[SPH_H];
-                a.p.omega = D.prop[pom]; a.p.ah = D.prop[pah]; a.p.converged = D.prop[pcv];
-                if (c->gasd_skip && c->pair_variant == 6) {
-                    // the raw arho of every row is kept by every sweep; a repeated call may use what the previous one kept
-                    const bool had = D.gasd_araw.ptr && D.gasd_araw.bytes >= D.n * sizeof(double);
-                    SPH_TRY(D.gasd_araw.reserve(D.n * sizeof(double), true, c->stream));
-                    a.p.araw = D.gasd_araw.as<double>();
-                    a.p.skip = c->gasd_repeat && had;
-                }
-                SPH_TRY(c->gen_state.reserve(SPH_GEN_MAX_STATE * sizeof(double)));
-                a.p.flag = c->gen_state.as<uint32_t>();
-                HIP_TRY(hipMemsetAsync(a.p.flag, 0, 2 * sizeof(uint32_t), c->stream));
-            }
-            SPH_TRY(launch_pair<F>(c, K->kind, a));
-            if (a.p.iterate) {
-                uint32_t word[2] = {0, 0};
-                HIP_TRY(hipMemcpyAsync(word, a.p.flag, sizeof word, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                c->gasd_unconverged |= word[0];
-                c->timers[T_N_GASD_SKIP].count += word[1];
-                // h changed behind the neighbour grid (as UpdateSmoothingLengthFerrari in run_nosrc)
-                sph_mark_written(D, SPH_H);
-                c->uniform_h = false;
-            }
-            return SPH_OK;
-        };
-        auto run_mpm = [&](auto tag) -> int {
-            typedef decltype(tag) F;
-            PairArgs<F> a;
-            memset(&a, 0, sizeof a);
-            common(a);
-            const sph_equation *me = eq_of[SPH_EQ_MPM_ACCELERATIONS]; // par beta sigma alpha1_min alpha2_min update_alpha1 update_alpha2
-            a.p.beta = me->par[0]; a.p.sigma = me->par[1]; a.p.alpha1_min = me->par[2]; a.p.alpha2_min = me->par[3];
-            a.p.update_alpha1 = me->par[4] != 0.0; a.p.update_alpha2 = me->par[5] != 0.0;
-            const int pa1 = sph_prop_register("alpha1"), pa2 = sph_prop_register("alpha2"), paa1 = sph_prop_register("aalpha1"),
-                      paa2 = sph_prop_register("aalpha2"), pd2 = sph_prop_register("del2e"), pdv = sph_prop_register("div"),
-                      pom = sph_prop_register("omega");
-            if (pa1 < 0 || pa2 < 0 || paa1 < 0 || paa2 < 0 || pd2 < 0 || pdv < 0 || pom < 0) return SPH_ERR_ARG; // (the records carry omega, alpha1, alpha2)
-            SPH_TRY(ensure_out(c, dst, {SPH_AU, SPH_AV, SPH_AW, SPH_AE, SPH_DT_CFL, paa1, paa2, pd2}));
-            if (a.p.update_alpha1) SPH_TRY(need_prop(c, dst, pdv, "MPMAccelerations (div)"));
-            a.p.h = D.prop[SPH_H]; a.p.cs = D.prop[SPH_CS]; a.p.e = D.prop[SPH_E]; a.p.div = D.prop[pdv];
-            a.p.alpha1 = D.prop[pa1]; a.p.alpha2 = D.prop[pa2];
-            a.p.au = D.prop[SPH_AU]; a.p.av = D.prop[SPH_AV]; a.p.aw = D.prop[SPH_AW]; a.p.ae = D.prop[SPH_AE];
-            a.p.del2e = D.prop[pd2]; a.p.dt_cfl = D.prop[SPH_DT_CFL]; a.p.aalpha1 = D.prop[paa1]; a.p.aalpha2 = D.prop[paa2];
-            return launch_pair<F>(c, K->kind, a);
-        };
-        const bool f32 = c->arith_f32 != 0;
-        const bool g7 = tait_gk(g->eos_par[2]) == 3; // the usual exponent: kernels that fold it
-        if (fam == FAM_WCSPH && eosf && umass && g7) SPH_TRY(f32 ? run_wcsph(FamWCSPHE_T<float, true>()) : run_wcsph(FamWCSPHE_T<double, true>()));
-        else if (fam == FAM_WCSPH && eosf && g7) SPH_TRY(f32 ? run_wcsph(FamWCSPHE_T<float>()) : run_wcsph(FamWCSPHE_T<double>()));
-        else if (fam == FAM_WCSPH && eosf && umass) SPH_TRY(f32 ? run_wcsph(FamWCSPHEG_T<float, true>()) : run_wcsph(FamWCSPHEG_T<double, true>()));
-        else if (fam == FAM_WCSPH && eosf) SPH_TRY(f32 ? run_wcsph(FamWCSPHEG_T<float>()) : run_wcsph(FamWCSPHEG_T<double>()));
-        else if (fam == FAM_WCSPH && eosv) SPH_TRY(f32 ? run_wcsph(FamWCSPHV_T<float>()) : run_wcsph(FamWCSPHV_T<double>()));
-        else if (fam == FAM_WCSPH) SPH_TRY(f32 ? run_wcsph(FamWCSPH_T<float>()) : run_wcsph(FamWCSPH()));
-        else if (fam == FAM_WCSPHX && wx_ds) SPH_TRY(f32 ? run_wcsphx(FamWCSPHX_T<float, true>()) : run_wcsphx(FamWCSPHX_T<double, true>()));
-        else if (fam == FAM_WCSPHX) SPH_TRY(f32 ? run_wcsphx(FamWCSPHX_T<float, false>()) : run_wcsphx(FamWCSPHX_T<double, false>()));
-        else if (fam == FAM_DSPRE) SPH_TRY(f32 ? run_dspre(FamDSPre_T<float>()) : run_dspre(FamDSPre_T<double>()));
-        else if (fam == FAM_DENSITY) SPH_TRY(f32 ? run_density(FamDensity_T<float>()) : run_density(FamDensity()));
-        else if (fam == FAM_AVGP) SPH_TRY(f32 ? run_avgp(FamAvgP_T<float>()) : run_avgp(FamAvgP_T<double>()));
-        else if (fam == FAM_GASSD) SPH_TRY(f32 ? run_gassd(FamGasSD_T<float>()) : run_gassd(FamGasSD_T<double>()));
-        else if (fam == FAM_MPM) SPH_TRY(f32 ? run_mpm(FamMPM_T<float>()) : run_mpm(FamMPM_T<double>()));
-        else if (fam == FAM_EDAC && (dflags & F_EINT)) SPH_TRY(f32 ? run_edac(FamEDAC_T<float, true>()) : run_edac(FamEDAC_T<double, true>()));
-        else if (fam == FAM_EDAC) SPH_TRY(f32 ? run_edac(FamEDAC_T<float, false>()) : run_edac(FamEDAC_T<double, false>()));
-        else if (fam == FAM_VGRAD) SPH_TRY(f32 ? run_vgrad(FamVGrad_T<float>()) : run_vgrad(FamVGrad()));
-        else if (fam == FAM_ELASTIC && elu) SPH_TRY(f32 ? run_elastic(FamElasticU_T<float>()) : run_elastic(FamElasticU_T<double>()));
-        else if (fam == FAM_ELASTIC) SPH_TRY(f32 ? run_elastic(FamElastic_T<float>()) : run_elastic(FamElastic()));
-        else if (tvff) SPH_TRY(f32 ? run_tvf(FamTVFE_T<float>()) : run_tvf(FamTVFE_T<double>()));
-        else SPH_TRY(f32 ? run_tvf(FamTVF_T<float>()) : run_tvf(FamTVF()));
+        int nseg = P.nsrcs;
+        for (int j = 0; j < P.nsrcs; j++) nseg += c->arr[P.srcs[j]].g_n > 0 && P.phase != 1;
+        if (nseg > SPH_MAX_ARRAYS) { sph_set_error("too many source segments (%d arrays with ghost segments)", P.nsrcs); return SPH_ERR_UNSUPPORTED; }
+        SPH_TRY(launch_family(PairLaunch{c, K, g, t, dt, P, rl, nl_mode}));
     }
     if (eos_pending) SPH_TRY(run_pending_eos(c, g)); // (no destination came as far as its records)
     HIP_TRY(hipGetLastError());
@@ -3903,12 +3958,12 @@ static int reduce_minmax(sph_ctx *c, int id, int prop, double *out, bool want_ma
 // (a family missing here is an undefined symbol when libsphhip.so is linked: the Makefile links with -z defs)
 // ---------------------------------------------------------------------------
 #if !SPH_PRIMARY_UNIT
-template <class Fam, int K> int launch_pair_ext(sph_ctx *c, const PairArgs<Fam> &a) { return launch_pair_k<Fam, K>(c, a); }
+template <class Fam, int K> int launch_pair_ext(sph_ctx *c, const PairArgs<Fam> &a, bool rec_f32) { return launch_pair_k<Fam, K>(c, a, rec_f32); }
 template <class Fam, bool UHV, int K> int launch_pair_fused_ext(sph_ctx *c, const PairArgs<Fam> &a) { return launch_pair_fused_k<Fam, UHV, K>(c, a); }
 template <class Fm, int K> int launch_pair_merged_ext(sph_ctx *c, const PairArgs<Fm> &a) { return launch_pair_merged_k<Fm, K>(c, a); }
 template <class Fam, int K> int launch_interp_ext(sph_ctx *c, const PairArgs<Fam> &a) { return launch_interp_k<Fam, K>(c, a); }
 
-#define UNIT_PAIR(F) template int launch_pair_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
+#define UNIT_PAIR(F) template int launch_pair_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &, bool)
 #define UNIT_FUSED(F, UHV) template int launch_pair_fused_ext<F, UHV, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
 #define UNIT_MERGED(F) template int launch_pair_merged_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)
 #define UNIT_INTERP(F) template int launch_interp_ext<F, SPH_KERNEL_UNIT>(sph_ctx *, const PairArgs<F> &)

@@ -281,7 +281,6 @@ struct sph_ctx {
     long record_f32 = 0;    // packed records in fp32 (inputs rounded, arithmetic fp64): aggregated kernel only
     long tile_block_rows = 8; // destination tiles are traversed in blocks of this many cell rows (y) through all z planes; 0: memory order
     long row_mod3 = 3;        // the pair kernel visits a wavefront's 3x3 rows of cells in (y mod 3, z mod 3) order (PairArgs::row_mod3)
-    double cur_dt = 0.0;    // dt of the sph_eval_group call being set up
     long gasd_skip = 0;     // wavefronts of an iterating density sweep whose destinations have all converged skip their neighbour work
     long gasd_repeat = 0;   // ... the host says: this call repeats the previous one inside an iterated group (nothing else ran in between)
     uint32_t gasd_unconverged = 0; // the last sph_eval_group call: an iterating gas-dynamics density sweep left particles unconverged
@@ -291,19 +290,11 @@ struct sph_ctx {
     PackCache pack_cache[SPH_MAX_ARRAYS];
     long wcsph_nr = 0;      // profiling: doubles per compact WCSPH record (default 10; 12/14/16 pad the stride)
     long lds_pad = 0;       // profiling: extra dynamic LDS per pair-kernel workgroup (limits wavefronts per CU)
-    int cur_nrec = 0;       // doubles per packed record of the pair launch being set up
-    bool cur_eosf = false;  // the pair launch being set up reads the 64-byte WCSPH records (EOS recomputed per record)
-    bool cur_umass = false; // ... with p / rho^2 in the mass slot (every source array has one mass)
-    bool cur_eosv = false;  // ... the 64-byte variable-h WCSPH records [x y z h u v w rho] (one mass per source array)
-    bool cur_elu = false;   // ... the elastic-rates records without h and m (uniform h, one mass per source array)
-    bool cur_tvff = false;  // the pair launch being set up reads the state-fused TVF records (p and V recomputed from rho)
-    long mass_fuse = 1;     // allow that
+    long mass_fuse = 1;     // allow the records that hold no mass (one mass per source array: sph_eval.hip RecordLayout)
     bool want_mrange = false; // an evaluation could have used uniform-mass records: the next neighbour updates look at the masses
     long block_sorted_outputs = 0;
     long eos_fuse = 1;      // honour sph_group.src_eos (64-byte WCSPH records, p and cs recomputed from rho)
     long eos_absorb = 1;    // the host may leave the Tait EOS before a WCSPH pair group to that group (sph_group.src_eos = 3)
-    bool cur_eos_abs = false;      // the records being packed absorb the Tait EOS (PackArgs::eos_abs) ...
-    double cur_eos_par[4] = {};    // ... with these parameters: rho0 c0 gamma p0
     long nl_reuse = 0;      // honour sph_group.nl_mode (neighbour lists kept between the pair passes of one evaluation): built,
                             // bit-identical, and measured SLOWER on MI355X (phase 1 overlaps other wavefronts' gathers)
     long fill_holes = 1;    // sph_halo_remove_selected moves the tail's kept rows into the holes when few particles leave (0: always the stable compaction)
@@ -352,4 +343,7 @@ int nnps_csr_pair_kernel(sph_ctx *c, int src, int dst, uint32_t *count, const ui
 int sph_rigid_stage(sph_ctx *c, int id, int stepper, int stage, double dt);
 
 // eval.hip helpers
+// the pair kernels run the wave-tile schedule (option pair_variant 6, the default; 0: the direct per-lane walk over records
+// [x y z h] + aux, which has no compact layout, no fp32, no ghost segments)
+static inline bool wave_tiles(const sph_ctx *c) { return c->pair_variant == 6; }
 static inline unsigned div_up(size_t a, unsigned b) { return (unsigned)((a + b - 1) / b); }

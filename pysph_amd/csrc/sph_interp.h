@@ -272,19 +272,13 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
     for (int j = 0; j < nsrc; j++)
         if (c->arr[srcs[j]].nnps_slot < 0) { sph_set_error("sph_interpolate: source array %d is not part of the neighbour grid", srcs[j]); return SPH_ERR_STATE; }
     if (c->ghosts_binned) { sph_set_error("sph_interpolate does not read ghost segments (ghost split): use the plain exchange -> sph_nnps_update order"); return SPH_ERR_UNSUPPORTED; }
-    if (c->pair_variant != 6) { sph_set_error("sph_interpolate needs pair_variant 6"); return SPH_ERR_UNSUPPORTED; }
+    if (!wave_tiles(c)) { sph_set_error("sph_interpolate needs pair_variant 6"); return SPH_ERR_UNSUPPORTED; }
     HIP_TRY(hipSetDevice(c->device));
     SPH_TRY(nnps_need_tables(c));
     if (host_out && n_pull > D.n) { sph_set_error("sph_interpolate: n_pull %zu > %zu points", n_pull, D.n); return SPH_ERR_ARG; }
     if (D.n == 0) return SPH_OK;
 
-    // fp64 only: arith_f32 / record_f32 do not apply here
-    struct Fp64Only {
-        sph_ctx *c; long r, a;
-        Fp64Only(sph_ctx *c_) : c(c_), r(c_->record_f32), a(c_->arith_f32) { c->record_f32 = 0; c->arith_f32 = 0; }
-        ~Fp64Only() { c->record_f32 = r; c->arith_f32 = a; }
-    } fp64_only(c);
-    c->cur_eosf = c->cur_eosv = c->cur_tvff = c->cur_elu = c->cur_umass = false;
+    // fp64 only: arith_f32 / record_f32 do not apply here (the records are packed and read as fp64 whatever they say)
     c->nl.valid = false;
 
     size_t total = 0, off_of[SPH_MAX_ARRAYS];
@@ -298,8 +292,7 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
     for (auto &pc : c->pack_cache) pc.epoch = 0; // these records overwrite the shared WCSPH slots
 
     auto common = [&](auto &a, int nrec, uint32_t flags) {
-        c->cur_nrec = nrec;
-        fill_common(c, a, K, 0.0);
+        fill_common(c, a, K, 0.0, 0.0, nrec);
         a.ablate = 0; a.dbg = nullptr;
         a.nsrc = 0;
         for (int j = 0; j < nsrc; j++) {
@@ -307,7 +300,6 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
             if (S.n == 0) continue;
             a.src[a.nsrc++] = {S.cell_start.as<uint32_t>(), (uint32_t)off_of[j], flags, S.fine_start.as<uint32_t>(), 0.0, 0u};
         }
-        a.nrec = nrec;
         a.d_off = (uint32_t)d_off; a.nd = (uint32_t)D.n;
         a.d_keys = D.keys_sorted.as<uint32_t>(); a.d_fkeys = D.fkeys_sorted.as<uint32_t>(); a.d_perm = D.perm.as<uint32_t>();
         set_tile_order(c, a, D);
@@ -337,19 +329,18 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
             SPH_TRY(c->interp_mom.reserve((D.n + 64) * 16 * sizeof(double)));
             // SummationDensity(dest = every source, sources = all of them, real = False) with the library's density
             // kernel into private buffers: the sources' own rho stays what it is
-            PackPlan pl = pack_plan(FAM_DENSITY);
-            if (c->uniform_h && c->use_uniform_h) pl.nr = 4;
-            c->cur_nrec = pl.nr;
+            RecordLayout rl(FAM_DENSITY);
+            if (c->uniform_h && c->use_uniform_h) rl.pl.nr = 4;
             {
                 ScopedTimer tm(c, T_PACK);
-                for (int j = 0; j < nsrc; j++) SPH_TRY(pack_array(c, srcs[j], off_of[j], pl, FAM_DENSITY, F_SD, false, true, 0));
+                for (int j = 0; j < nsrc; j++) SPH_TRY(pack_array(c, srcs[j], off_of[j], rl, FAM_DENSITY, F_SD, false, true, 0));
             }
             for (int i = 0; i < nsrc; i++) {
                 DevArray &S = c->arr[srcs[i]];
                 if (S.n == 0) continue;
                 PairArgs<FamDensity> a;
                 memset(&a, 0, sizeof a);
-                fill_common(c, a, K, 0.0);
+                fill_common(c, a, K, 0.0, 0.0, rl.pl.nr);
                 a.ablate = 0; a.dbg = nullptr;
                 for (int j = 0; j < nsrc; j++) {
                     const DevArray &T = c->arr[srcs[j]];
@@ -363,7 +354,7 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
                 a.d_start = 0; a.d_stop = (uint32_t)S.n; a.dflags = F_SD;
                 a.p.rho = c->interp_rho[srcs[i]].as<double>();
                 ScopedTimer tm(c, T_PAIR);
-                SPH_TRY(launch_pair<FamDensity>(c, K->kind, a));
+                SPH_TRY(launch_pair_fp64<FamDensity>(c, K->kind, a));
                 hipLaunchKernelGGL(k_interp_vol, dim3(div_up(S.n, 256)), dim3(256), 0, c->stream, S.prop[SPH_M],
                                    c->interp_rho[srcs[i]].as<double>(), c->interp_vol1[srcs[i]].as<double>(), S.n);
             }

@@ -5,6 +5,9 @@ Both forms run ONE device function for p and cs and the same expression for p / 
 bit for bit (the doubles as uint64: NaN and the sign of zero count).  The cases that cannot absorb the equation --
 several arrays, h and m that vary, an exponent other than 7, the HG-corrected EOS, a split evaluation -- must fall
 back to the EOS kernel, with the same bits again and counter n_eos_absorbed unchanged."""
+import ctypes as C
+import functools
+
 import numpy as np
 import pytest
 
@@ -223,6 +226,112 @@ def test_fallback_split_evaluation():
     assert c_on['n_eos_absorbed'] == 0 and c_off['n_eos_absorbed'] == 0, (c_on, c_off)
     assert c_on['n_phase2'] == 2 and c_on['eos'] == c_off['eos'] > 0, (c_on, c_off)
     assert_same_bits(on, off, 'compute_begin / compute_end')
+
+
+def _step_around_fp64_calls(n, opts=(), middle=True, lacking=None):
+    """One array of n jittered-lattice points, device-resident: evaluate the TaitEOS + Continuity / Momentum step, then
+    (`middle`) the calls that are fp64 by contract on the same context -- neighbour lists, a Shepard and an order-1
+    interpolation -- then update and evaluate again.  `lacking`: a property the pair loop requires, left off the device
+    for the first evaluation -- which must fail with SPH_ERR_MISSING_PROP once its records are chosen -- and pushed
+    before the second.  -> {'out': outputs of the second evaluation, 'lists': (start, nbrs), 'interp': [values]}"""
+    from pysph_amd import device as dev
+    from pysph_amd import kernels as K
+    from pysph_amd.interpolator import _METHOD_IDS
+    from pysph_amd.nnps import HipNNPS
+    from pysph_amd.particle_array import get_particle_array
+    pa, dx = lattice_array(n)
+    pa.p[:] = -1.0
+    pa.cs[:] = -1.0
+    kernel = K.WendlandQuintic(dim=3)
+    a_eval, nnps, ctx = make_eval([pa], cube_equations(dx), kernel, 3, 6, sync='manual')
+    res = {}
+    try:
+        for k, v in opts:
+            ctx.set_option(k, v)
+        pa.gpu.push(*[k for k in pa.properties if dev.prop_id(k) >= 0 and k != lacking])
+        nnps.sync = False
+        nnps.update()
+        if lacking:
+            with pytest.raises(dev.SphError, match='error -5'):
+                a_eval.compute(0.0, 1e-5)
+            assert ctx.timer_get('n_eos_absorbed')[1] == 1      # the records that absorb the EOS were chosen already
+        else:
+            a_eval.compute(0.0, 1e-5)
+        if middle:
+            res['lists'] = nnps.get_csr(0, 0)
+            m1 = int(np.ceil(n ** (1.0 / 3.0) - 1e-9))
+            pts = np.random.default_rng(11).uniform(-0.5 * dx, (m1 - 0.5) * dx, (3, 24))
+            # (through the C-ABI: the Interpolator class sizes a default mesh from the sources' extent, which one point lacks)
+            pts_pa = get_particle_array(name='interpolate', x=pts[0], y=pts[1], z=pts[2], h=pa.h[0] * np.ones(24))
+            hd = dev.attach(pts_pa, ctx)
+            hd.push('x', 'y', 'z', 'h')
+            HipNNPS(3, [pa, pts_pa], radius_scale=kernel.radius_scale, ctx=ctx, sync=False)
+            ck = dev.SphKernel(K.kernel_id(kernel), 3, kernel.fac, kernel.radius_scale, kernel.get_deltap())
+            src, prop = (C.c_int * 1)(pa.gpu.array_id), (C.c_int * 1)(dev.prop_id('u'))
+            res['interp'] = []
+            for method, nout in (('shepard', 1), ('order1', 4)):
+                host = np.empty((nout, 24))
+                dev._check(ctx.lib.sph_interpolate(ctx._h, C.byref(ck), _METHOD_IDS[method], hd.array_id, 1, src, 1, prop, None,
+                                                   host.ctypes.data_as(dev._PD), 24))
+                res['interp'] += list(host)
+        if lacking:
+            pa.gpu.push(lacking)
+        nnps.update()
+        a_eval.compute(0.0, 1e-5)
+        a_eval.c_acceleration_eval.pull_outputs()
+        pa.gpu.pull('p', 'cs')
+        res['out'] = {('fluid', k): np.array(pa.properties[k]) for k in OUT}
+        res['x'] = np.stack([pa.x, pa.y, pa.z], axis=1)
+        res['hr'] = kernel.radius_scale * pa.h[0]
+    finally:
+        ctx.close()
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def _fp64_reference(n):
+    """the same sequence on a context whose options arith_f32 and record_f32 are 0"""
+    return _step_around_fp64_calls(n)
+
+
+def _assert_fp64_calls_same_bits(got, want, what):
+    for a, b in zip(got['lists'], want['lists']):
+        assert np.array_equal(a, b), (what, 'neighbour lists')
+    assert len(got['interp']) == len(want['interp']) == 5
+    for k, (a, b) in enumerate(zip(got['interp'], want['interp'])):
+        assert np.array_equal(_bits(a), _bits(b)), (what, 'interpolation', k)
+
+
+# below, at and above one wavefront, and above one 256-thread pack block
+SMALL_N = [1, 64, 65, 257]
+
+
+@pytest.mark.parametrize('option', ['arith_f32', 'record_f32'])
+@pytest.mark.parametrize('n', SMALL_N)
+def test_precision_options_do_not_leak_into_fp64_calls(n, option):
+    """neighbour lists and the interpolator are fp64 whatever arith_f32 / record_f32 say, and leave both options and
+    the records of the evaluation around them as they were"""
+    opts = ((option, 1),)
+    with_calls = _step_around_fp64_calls(n, opts)
+    without = _step_around_fp64_calls(n, opts, middle=False)
+    assert_same_bits([with_calls['out']], [without['out']], (n, option, 'second evaluation'))
+    _assert_fp64_calls_same_bits(with_calls, _fp64_reference(n), (n, option))
+    if n > 1:       # the option is in force: the outputs are not those of the fp64 context
+        assert any((_bits(with_calls['out'][k]) != _bits(_fp64_reference(n)['out'][k])).any() for k in with_calls['out'])
+
+
+@pytest.mark.parametrize('n', SMALL_N)
+def test_failed_evaluation_leaves_nothing_behind(n):
+    """the absorbable group on an array whose device copy lacks w: SPH_ERR_MISSING_PROP after the EOS-absorbing records
+    were chosen; the fp64 calls behind it, and the same group once w is there, are those of a context that never failed"""
+    failed = _step_around_fp64_calls(n, lacking='w')
+    x, (start, nbrs) = failed['x'], failed['lists']
+    d2 = ((x[:, None, :] - x[None, :, :]) ** 2).sum(axis=2)
+    near = d2 < failed['hr'] ** 2
+    assert np.array_equal(start, np.concatenate([[0], np.cumsum(near.sum(axis=1))]))
+    assert np.array_equal(nbrs, np.nonzero(near)[1])            # (rows in ascending order, as get_csr returns them)
+    _assert_fp64_calls_same_bits(failed, _fp64_reference(n), n)
+    assert_same_bits([failed['out']], [_fp64_reference(n)['out']], (n, 'evaluation after the failed one'))
 
 
 def test_plan_marks_the_absorbable_group_only():
