@@ -299,6 +299,15 @@ int sph_nnps_get_csr(sph_ctx *ctx, int src, int dst, uint32_t *start, size_t sta
  * index), n entries: get_spatially_ordered_indices
  * (linked_list_nnps.pyx:198-209).                                          */
 int sph_nnps_get_order(sph_ctx *ctx, int array_id, uint32_t *perm);
+/* One table of the last sph_nnps_update as its sort left it, when ONE sort
+ * ordered all arrays (the merged order of several arrays, or the one
+ * non-empty array): sorted position -> index (uint32, n), sorted fine keys
+ * (uint32, n), fine_start (uint32, fine keys + 1), cell_start (uint32,
+ * cells + 1), the array slot of every sorted particle (uint8, n; merged order
+ * only, else 0 bytes).  *bytes: the table's size; out == NULL only asks for
+ * it.  For tests and tools: a device->host copy and a synchronisation.      */
+enum { SPH_TABLE_PERM = 0, SPH_TABLE_FINE_KEYS = 1, SPH_TABLE_FINE_START = 2, SPH_TABLE_CELL_START = 3, SPH_TABLE_SLOT = 4 };
+int sph_nnps_read_table(sph_ctx *ctx, int which, void *out, size_t cap_bytes, size_t *bytes);
 
 /* Physically reorder EVERY device property of `array_id` into the cell order
  * of the last sph_nnps_update (new[i] = old[perm[i]]): the device-resident

@@ -150,7 +150,7 @@ int sph_ctx_destroy(sph_ctx *c)
     for (auto &R : c->rigid) { R.state.release(); R.order.release(); R.chunk.release(); R.chunk_start.release(); R.partial.release(); }
     c->io_counts.release();
     for (DevBuf *b : {&c->dbgc, &c->gapq, &c->cub_tmp, &c->red_part, &c->red_out, &c->posh, &c->aux, &c->fposb, &c->dkeys, &c->dperm,
-                      &c->tmp_u32a, &c->tmp_u32b, &c->gen_state, &c->nlbuf, &c->splitcnt, &c->scan_part, &c->bigq, &c->sort_tab, &c->xflag, &c->dom_counts})
+                      &c->tmp_u32a, &c->tmp_u32b, &c->gen_state, &c->nlbuf, &c->splitcnt, &c->scan_part, &c->bigq, &c->sort_tab, &c->place_buf, &c->xflag, &c->dom_counts})
         b->release();
     for (auto &b : c->csr_start) b.release();
     for (auto &b : c->csr_nbrs) b.release();
@@ -163,7 +163,6 @@ int sph_ctx_destroy(sph_ctx *c)
         for (auto &pr : t.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->pin_async) (void)hipHostFree(c->pin_async);
-    if (c->lag_ev) (void)hipEventDestroy(c->lag_ev);
     if (c->dom_pin) (void)hipHostFree(c->dom_pin);
     if (c->dom_ev) (void)hipEventDestroy(c->dom_ev);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -383,6 +382,7 @@ int sph_set_option(sph_ctx *c, const char *key, long value)
     if (strcmp(key, "tension_flag") == 0) { c->tension_flag = value ? 1 : 0; return SPH_OK; }
     if (strcmp(key, "lazy_tables") == 0) { c->lazy_tables = value ? 1 : 0; c->nnps_valid = false; return SPH_OK; }
     if (strcmp(key, "async_update") == 0) { c->async_update = value ? 1 : 0; return SPH_OK; }
+    if (strcmp(key, "sort_place") == 0) { c->sort_place = value ? 1 : 0; return SPH_OK; }
     if (strcmp(key, "via_unordered") == 0) { c->via_unordered = value ? 1 : 0; return SPH_OK; }
     if (strcmp(key, "sort_lbits") == 0) { // 0: from the mean density; 9..11: fixed low key bits of the particle sort (profiling / tests)
         if (value != 0 && (value < 9 || value > 11)) { sph_set_error("sort_lbits must be 0 or 9..11"); return SPH_ERR_ARG; }
@@ -461,7 +461,7 @@ int sph_timer_get(sph_ctx *c, const char *key, double *ms, long *count)
     static const char *names[T_COUNT] = {"nnps", "pack", "eos", "pair", "stage",
                                          "pair_none", "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad", "pair_elastic",
                                          "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure", "pair_gasd_density", "pair_gasd_mpm",
-                                         "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep", "n_eos_absorbed", "n_gasd_skipped"};
+                                         "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep", "n_eos_absorbed", "n_gasd_skipped", "n_placed", "n_place_overflow"};
     SPH_TRY(timer_drain(c));
     for (int i = 0; i < T_COUNT; i++)
         if (strcmp(key, names[i]) == 0) {

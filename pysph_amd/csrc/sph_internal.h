@@ -136,7 +136,7 @@ struct RigidState {
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
 // T_N_*: launch counters only (no time): pair launches on EOS-fused records, launches that kept / reused neighbour lists
 // T_N_INTERP_MOM / _SWEEP: moment passes / property sweeps of sph_interpolate
-enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 13, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_N_GASD_SKIP, T_COUNT };
+enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 13, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_N_GASD_SKIP, T_N_PLACED, T_N_PLACE_OVF, T_COUNT };
 
 struct Timer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -244,13 +244,13 @@ struct sph_ctx {
     // looking (DevArray::h_dirty / m_dirty) only the bounds of the positions are missing for the grid -- and ANY grid
     // whose cells are at least radius_scale * hmax wide gives the same neighbours (particles outside it are clamped into
     // its outermost cells).  Such an update bins on the grid of the PREVIOUS update's bounds (they arrived long ago) in
-    // the same pass that reduces this update's bounds; those travel to `pin_async` behind an event nobody waits for.
+    // the same pass that reduces this update's bounds; those are stored into `pin_async` by the kernel that reduces them; nobody waits.
     // The grid REPORTED (sph_nnps_info: cell_size, xmin, xmax, n_cells -- the reference's values, exactly) is computed
     // from this update's bounds when somebody asks.
     long async_update = 1;
     struct {
-        bool valid = false;      // pin_async holds (or will hold, once `ev` has passed) the bounds of the last update
-        bool pending = false;    // ... behind `ev`
+        bool valid = false;      // pin_async holds (or will hold, once its sequence number has arrived) the bounds of the last update
+        bool pending = false;    // ... on their way (lag_wait)
         int dim = 0, narrays = 0, ids[SPH_MAX_ARRAYS] = {};
         double radius_scale = 0, cell_size_in = 0, extend[3] = {}, hr[2] = {};
     } lag;
@@ -260,11 +260,31 @@ struct sph_ctx {
     double *dom_pin = nullptr;    // pinned: SPH_MAX_ARRAYS * 6 doubles
     hipEvent_t dom_ev = nullptr;
     bool dom_queued = false;
-    hipEvent_t lag_ev = nullptr;
     double *pin_async = nullptr;  // pinned: 64 doubles
     GridHost rep;                 // the reported grid of the last update
     bool rep_valid = false;       // ... computed (else: from pin_async on demand)
     long n_async_updates = 0;     // updates that ran without a round trip (sph_timer_get "n_async")
+    // The bounds of a lagged update reach `pin_async` by plain stores of the kernel that reduces them (the buffer is
+    // host-coherent): payload, a system-scope fence, then `lag_seq` in a spare slot.  lag_wait reads that word and falls
+    // back to a stream synchronisation when the number has not arrived yet.
+    unsigned long long lag_seq = 0; // sequence number of the last lagged update launched
+    // The PLACED update (option sort_place, default 1): an update on the grid of the update before it places its (key,
+    // index) pairs with that update's bucket table (`bstart`, `cur` of sort_tab are ping-pong pairs) in the key pass itself
+    // -- k_bin_place -> k_bucket_sort, two launches.  Pairs beyond a bucket's old size go through an overflow list.
+    long sort_place = 1;
+    struct {
+        bool valid = false;      // sort_tab holds the bucket table of the last update, in the form k_bin_place reads
+        int pp = 0;              // ... in this half of the ping-pong pairs
+        unsigned char grid[96] = {}; // the binning grid of that update (a GridDesc)
+        size_t n_fine = 0, n_cat = 0;
+        int lbits = 0, narrays = 0, ids[SPH_MAX_ARRAYS] = {};
+        uint32_t nbuckets = 0, n[SPH_MAX_ARRAYS] = {};
+        bool merged = false;
+        uint32_t ovf_seen = 0;   // pairs of the last placed update that went through the list, as the host last saw them
+    } place;
+    DevArray *sorted_T = nullptr; // what the ONE sort of the last update sorted (sph_nnps_read_table), n and fine keys of it
+    size_t sorted_n = 0, sorted_n_fine = 0;
+    DevBuf place_buf;             // [n pairs: the overflow list][n pairs: overflowing buckets gathered for their sort]
 
     // scratch
     DevBuf cub_tmp, red_part, red_out, posh, aux, fposb, dkeys, dperm, tmp_u32a, tmp_u32b, gen_state, gapq;

@@ -115,7 +115,8 @@ __device__ __forceinline__ uint32_t fine_key_of(double x, double y, double z, co
 //                     (= what a stable sort gives: deterministic, bit-identical to the radix sort it replaces) and --
 //                     the scan of a bucket's histogram IS its slice of fine_start -- the cell tables and the merged
 //                     order's slot / index split written on the way
-// Four launches per neighbour update.
+// Four launches per neighbour update -- or two, k_bin_place -> k_bucket_sort<..., PLACED>, when the update can place its pairs
+// with the bucket table the previous update left (sph_ctx::place, sort_placed below).
 #define SORT_LMIN 9
 #define SORT_LMAX 11
 #define SORT_BK_CAP 3840   // (lo, index) pairs a bucket's workgroup stages in LDS (four workgroups per CU: 4 x 38.6 KB); a larger bucket is sorted in global memory
@@ -128,6 +129,10 @@ enum { MM_XYZ = 1, MM_H = 2, MM_M = 4 };
 #define MM_OUT_GROUPS 43   // atomic groups k_bin_keys formed (one per bucket a wavefront's 64 particles hit): n / 64 * 1..2 for
                            // particles in cell order, n for particles in no spatial order
 #define MM_OUT_N 44
+// ... and, in the mailbox of a lagged update (sph_ctx::pin_async) only:
+#define MM_OUT_OVF 44      // pairs a placed update sent through its overflow list (0: the four-launch path)
+#define MM_MAIL_N 45       // payload doubles of the mailbox
+#define MM_OUT_SEQ 45      // the update's sequence number (sph_ctx::lag_seq, a 64-bit integer), stored LAST
 
 struct BinArrays {   // the arrays of one update, concatenated in slot order
     const double *x[SPH_MAX_ARRAYS], *y[SPH_MAX_ARRAYS], *z[SPH_MAX_ARRAYS], *h[SPH_MAX_ARRAYS], *m[SPH_MAX_ARRAYS];
@@ -148,6 +153,24 @@ struct BinWork {
     const uint32_t *xflag;       // the context's flag word, copied to out[MM_OUT_XFLAG]
     uint32_t nbuckets;
     int lbits, mm;
+    uint32_t *cur2, *ovfc;       // the other half of the cursors' ping-pong pair and the two overflow counters: left zeroed too
+    double *mail;                // (optional) the host-coherent mailbox of a lagged update: out[] lands there as well, then `seq`
+    unsigned long long seq;
+    // the placed update (k_bin_place): the previous update's bucket starts, the pairs, the overflow list and its counter
+    const uint32_t *bprev;
+    uint2 *pairs, *ovf;
+    uint32_t *ovfcur;
+    uint32_t ncat;               // particles of the concatenation = capacity of `pairs` and of `ovf`
+};
+// what the finishing workgroup of an update needs from its launch (k_bucket_sort's service workgroup: no BinArrays there)
+struct FinishArgs {
+    const double *part, *parta;
+    const uint32_t *grp, *xflag;
+    double *out, *mail;
+    unsigned long long seq;
+    uint32_t first[SPH_MAX_ARRAYS + 1];
+    int narrays, mm;
+    uint32_t nblk;
 };
 
 template <class T> __device__ __forceinline__ T wave_incl_scan(T x, int lane)
@@ -254,52 +277,79 @@ __global__ __launch_bounds__(256) void k_bin_keys(BinArrays t, GridDesc g, BinWo
     }
 }
 
-// One workgroup after k_bin_keys: the partials reduced, the bucket histogram G scanned into the bucket starts, G and the
-// cursors left zeroed for the next sort.  (A kernel of its own rather than the last workgroup of k_bin_keys behind a
-// ticket: the agent-scope fence that pattern needs writes back an XCD's L2 once per wavefront -- measured 200 us at 4 M.)
-__global__ __launch_bounds__(1024) void k_bin_finish(BinArrays t, BinWork w, uint32_t nblk, int have_keys)
+// The reductions that finish an update: the partials of the key pass reduced into f.out (and the h and m range of every
+// array, the flag word, the count of atomic groups, `ovf` = the pairs that went through the overflow list).  With a
+// mailbox the values are then stored to the host as well: payload, a system-scope fence, the sequence number last -- one
+// wavefront does all of it, so the fence orders the number behind every payload store.
+// NT threads, all of them call it; sred: NT doubles, sg: NT / 64 words of LDS.
+template <int NT>
+__device__ __forceinline__ void finish_reduce(const FinishArgs &f, int have_keys, uint32_t ovf, double *sred, uint32_t *sg)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (w.mm) {
-        __shared__ double sred[128][8];
+    constexpr int NG = NT / 8;
+    if (f.mm) {
         const int k = threadIdx.x & 7, gq = threadIdx.x >> 3;
         double v = (k < 4) ? DBL_MAX : -DBL_MAX;
 #pragma unroll 8
-        for (uint32_t b = gq; b < nblk; b += 128) { // (independent loads: unrolled, they are in flight together)
-            const double q = w.part[(size_t)b * 8 + k];
+        for (uint32_t b = gq; b < f.nblk; b += NG) { // (independent loads: unrolled, they are in flight together)
+            const double q = f.part[(size_t)b * 8 + k];
             v = (k < 4) ? fmin(v, q) : fmax(v, q);
         }
-        sred[gq][k] = v;
+        sred[gq * 8 + k] = v;
         __syncthreads();
         if (threadIdx.x < 8) {
-            for (int q = 1; q < 128; q++) v = (k < 4) ? fmin(v, sred[q][k]) : fmax(v, sred[q][k]);
-            w.out[k] = v;
+            for (int q = 1; q < NG; q++) v = (k < 4) ? fmin(v, sred[q * 8 + k]) : fmax(v, sred[q * 8 + k]);
+            f.out[k] = v;
         }
         // the h and m range of every array: one wavefront per array
-        if (wv < t.narrays) {
-            const int a2 = wv;
+        for (int a2 = wv; a2 < f.narrays; a2 += NT / 64) {
             double hl = DBL_MAX, hh = -DBL_MAX, ml = DBL_MAX, mh = -DBL_MAX;
 #pragma unroll 8
-            for (uint32_t b = t.first[a2] + lane; b < t.first[a2 + 1]; b += 64) {
-                hl = fmin(hl, w.parta[(size_t)b * 4 + 0]); hh = fmax(hh, w.parta[(size_t)b * 4 + 1]);
-                ml = fmin(ml, w.parta[(size_t)b * 4 + 2]); mh = fmax(mh, w.parta[(size_t)b * 4 + 3]);
+            for (uint32_t b = f.first[a2] + lane; b < f.first[a2 + 1]; b += 64) {
+                hl = fmin(hl, f.parta[(size_t)b * 4 + 0]); hh = fmax(hh, f.parta[(size_t)b * 4 + 1]);
+                ml = fmin(ml, f.parta[(size_t)b * 4 + 2]); mh = fmax(mh, f.parta[(size_t)b * 4 + 3]);
             }
             hl = wave_min(hl); hh = wave_max(hh); ml = wave_min(ml); mh = wave_max(mh);
-            if (lane == 0) { w.out[8 + 4 * a2] = ml; w.out[9 + 4 * a2] = mh; w.out[10 + 4 * a2] = hl; w.out[11 + 4 * a2] = hh; }
+            if (lane == 0) { f.out[8 + 4 * a2] = ml; f.out[9 + 4 * a2] = mh; f.out[10 + 4 * a2] = hl; f.out[11 + 4 * a2] = hh; }
         }
     }
-    if (threadIdx.x == 0) w.out[MM_OUT_XFLAG] = (double)*w.xflag;
+    if (threadIdx.x == 0) f.out[MM_OUT_XFLAG] = (double)*f.xflag;
     if (have_keys) { // atomic groups of the key pass, summed over its workgroups
-        __shared__ uint32_t sg[16];
         uint32_t gsum = 0;
-        for (uint32_t b = threadIdx.x; b < nblk; b += 1024) gsum += w.grp[b];
+        for (uint32_t b = threadIdx.x; b < f.nblk; b += NT) gsum += f.grp[b];
         for (int o2 = 32; o2 > 0; o2 >>= 1) gsum += __shfl_xor(gsum, o2, 64);
         if (lane == 0) sg[wv] = gsum;
         __syncthreads();
-        if (threadIdx.x == 0) { uint32_t tot = 0; for (int q = 0; q < 16; q++) tot += sg[q]; w.out[MM_OUT_GROUPS] = (double)tot; }
+        if (threadIdx.x == 0) { uint32_t tot = 0; for (int q = 0; q < NT / 64; q++) tot += sg[q]; f.out[MM_OUT_GROUPS] = (double)tot; }
     } else if (threadIdx.x == 0) {
-        w.out[MM_OUT_GROUPS] = 0.0;
+        f.out[MM_OUT_GROUPS] = 0.0;
     }
+    if (f.mail) {
+        __syncthreads(); // f.out is complete (written by several wavefronts of this workgroup)
+        if (threadIdx.x < 64) {
+            if (threadIdx.x < MM_OUT_N) f.mail[threadIdx.x] = f.out[threadIdx.x];
+            if (threadIdx.x == MM_OUT_OVF) f.mail[MM_OUT_OVF] = (double)ovf;
+            __threadfence_system();
+            if (threadIdx.x == 0)
+                __hip_atomic_store(reinterpret_cast<unsigned long long *>(f.mail + MM_OUT_SEQ), f.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// One workgroup after k_bin_keys: the partials reduced, the bucket histogram G scanned into the bucket starts, G and the
+// cursors (both halves of their ping-pong pair, and the overflow counters) left zeroed for the next sort -- the form in
+// which a placed update (k_bin_place) finds the tables.  (A kernel of its own rather than the last workgroup of k_bin_keys
+// behind a ticket: the agent-scope fence that pattern needs writes back an XCD's L2 once per wavefront -- measured 200 us
+// at 4 M.)
+__global__ __launch_bounds__(1024) void k_bin_finish(FinishArgs f, BinWork w, int have_keys)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    {
+        __shared__ double sred[1024];
+        __shared__ uint32_t sg[16];
+        finish_reduce<1024>(f, have_keys, 0u, sred, sg);
+    }
+    if (have_keys && threadIdx.x < 2) w.ovfc[threadIdx.x] = 0u;
     if (have_keys) { // bucket starts = exclusive scan of G; G and the cursors zeroed
         // 32 consecutive buckets per thread and round (one round up to 32 Ki buckets: the loads of a round are in flight
         // together; a sparse grid -- the slab of a dam break's tank -- has tens of thousands of buckets)
@@ -329,7 +379,7 @@ __global__ __launch_bounds__(1024) void k_bin_finish(BinArrays t, BinWork w, uin
 #pragma unroll
             for (int q = 0; q < PT; q++) {
                 const uint32_t idx = i0 + q;
-                if (idx < w.nbuckets) { w.bstart[idx] = off; off += v[q]; w.G[idx] = 0u; w.cur[idx] = 0u; }
+                if (idx < w.nbuckets) { w.bstart[idx] = off; off += v[q]; w.G[idx] = 0u; w.cur[idx] = 0u; w.cur2[idx] = 0u; }
             }
             carry += tot;
             __syncthreads();
@@ -375,6 +425,108 @@ __global__ __launch_bounds__(256) void k_bucket_scatter(const uint32_t *__restri
         const uint32_t i = i0 + q * 256u;
         const uint32_t b = __shfl(base[q], leader[q], 64);
         if (i < n) pairs[(size_t)bs[q] + b + rank[q]] = make_uint2(key[q], via ? via[i] : i);
+    }
+}
+
+// The key pass of a PLACED update: k_bin_keys (same traversal, same partials, same count of atomic groups) that also puts
+// every (key, index) pair where the bucket table of the PREVIOUS update -- same grid, same arrays -- has room for it:
+//   the leader of every wavefront-aggregated group takes `cnt` places of bucket d with ONE returning atomic on w.cur[d];
+//   place p of bucket d is pairs[bprev[d] + p] while p < bprev[d + 1] - bprev[d], the bucket's size in the previous update;
+//   a pair beyond that goes to the overflow list (one aggregated cursor atomic per wavefront and trip).
+// w.cur[d] ends as the bucket's true count, overflow included; k_bucket_sort derives the new starts from the counts.
+// No key array, no histogram.  No `via` traversal (the host takes the four-launch path for it).
+__global__ __launch_bounds__(256) void k_bin_place(BinArrays t, GridDesc g, BinWork w)
+{
+    int a = 0;
+    for (int k = 1; k < SPH_MAX_ARRAYS; k++) if (k < t.narrays && blockIdx.x >= t.first[k]) a = k;
+    const double *__restrict__ x = t.x[a], *__restrict__ y = t.y[a], *__restrict__ z = t.z[a];
+    const uint32_t n = t.n[a], lb = blockIdx.x - t.first[a], nba = t.first[a + 1] - t.first[a];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+    const bool mmx = (w.mm & MM_XYZ) != 0;
+    uint32_t ngroups = 0; // (wave-uniform)
+    double mn[3] = {DBL_MAX, DBL_MAX, DBL_MAX};
+    double mx[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+    for (size_t ib = (size_t)lb * 256; ib < n; ib += (size_t)nba * 256 * BIN_U) { // the trip count is uniform over the workgroup
+        double qx[BIN_U], qy[BIN_U], qz[BIN_U];
+#pragma unroll
+        for (int u = 0; u < BIN_U; u++) {
+            const size_t i = ib + (size_t)u * nba * 256 + threadIdx.x;
+            const bool valid = i < n;
+            qx[u] = valid ? x[i] : 0.0; qy[u] = valid ? y[i] : 0.0; qz[u] = valid ? z[i] : 0.0;
+        }
+        uint32_t key[BIN_U], rank[BIN_U], base[BIN_U], bs[BIN_U], cap[BIN_U];
+        int leader[BIN_U];
+        // the cursor atomics of the BIN_U trips are in flight together (as k_bucket_scatter's)
+#pragma unroll
+        for (int u = 0; u < BIN_U; u++) {
+            const size_t i = ib + (size_t)u * nba * 256 + threadIdx.x;
+            const bool valid = i < n;
+            const double px = qx[u], py = qy[u], pz = qz[u];
+            const bool counts = valid && !is_parked(px);
+            if (counts && mmx) {
+                mn[0] = raw_min(mn[0], px); mx[0] = raw_max(mx[0], px);
+                mn[1] = raw_min(mn[1], py); mx[1] = raw_max(mx[1], py);
+                mn[2] = raw_min(mn[2], pz); mx[2] = raw_max(mx[2], pz);
+            }
+            key[u] = valid ? fine_key_of(px, py, pz, g, (size_t)t.off[a] + i) : 0u;
+            const uint32_t d = min(key[u] >> w.lbits, w.nbuckets - 1u); // (a key is below n_fine: the clamp never acts)
+            unsigned long long todo = __ballot(valid);
+            uint32_t cnt = 0;
+            leader[u] = lane; rank[u] = 0; base[u] = 0;
+            while (todo) {
+                const int l = __builtin_ctzll(todo);
+                const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)d, l);
+                const unsigned long long mk = __ballot(valid && d == dl);
+                if (valid && d == dl) { leader[u] = l; rank[u] = (uint32_t)__builtin_popcountll(mk & lt); cnt = (uint32_t)__builtin_popcountll(mk); }
+                todo &= ~mk;
+                ngroups++;
+            }
+            bs[u] = valid ? w.bprev[d] : 0u;
+            cap[u] = valid ? w.bprev[d + 1] - bs[u] : 0u;
+            if (valid && lane == leader[u]) base[u] = atomicAdd(&w.cur[d], cnt); // every group's leader at once
+        }
+#pragma unroll
+        for (int u = 0; u < BIN_U; u++) {
+            const size_t i = ib + (size_t)u * nba * 256 + threadIdx.x;
+            const bool valid = i < n;
+            const uint32_t p = (uint32_t)__shfl((int)base[u], leader[u], 64) + rank[u];
+            const uint2 pr = make_uint2(key[u], t.off[a] + (uint32_t)i);
+            // (the second test never fails on a table the host called valid: it keeps a store inside the buffer regardless)
+            const bool fits = valid && p < cap[u] && bs[u] + p < w.ncat;
+            if (fits) w.pairs[(size_t)bs[u] + p] = pr;
+            const unsigned long long om = __ballot(valid && !fits);
+            if (om) { // (wave-uniform) the wavefront's pairs without a place: one cursor atomic
+                uint32_t ob = 0;
+                const int ol = __builtin_ctzll(om);
+                if (lane == ol) ob = atomicAdd(w.ovfcur, (uint32_t)__builtin_popcountll(om));
+                ob = (uint32_t)__shfl((int)ob, ol, 64) + (uint32_t)__builtin_popcountll(om & lt);
+                if (valid && !fits && ob < w.ncat) w.ovf[ob] = pr;
+            }
+        }
+    }
+    __shared__ double s[4][6];
+    {
+        __shared__ uint32_t sgrp[4];
+        if (lane == 0) sgrp[wv] = ngroups;
+        __syncthreads();
+        if (threadIdx.x == 0) w.grp[blockIdx.x] = sgrp[0] + sgrp[1] + sgrp[2] + sgrp[3];
+    }
+    if (w.mm) { // (a placed update reduces positions only: h and m are known without looking)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double lo = wave_min(mn[k]), hi = wave_max(mx[k]);
+            if (lane == 0) { s[wv][k] = lo; s[wv][3 + k] = hi; }
+        }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            const int k = threadIdx.x;
+            double v = s[0][k];
+            for (int q = 1; q < 4; q++) v = k < 3 ? fmin(v, s[q][k]) : fmax(v, s[q][k]);
+            w.part[(size_t)blockIdx.x * 8 + (k < 3 ? k : k + 1)] = v;
+        }
+        if (threadIdx.x >= 6 && threadIdx.x < 8) w.part[(size_t)blockIdx.x * 8 + (threadIdx.x == 6 ? 3 : 7)] = threadIdx.x == 6 ? DBL_MAX : -DBL_MAX;
+        if (threadIdx.x >= 8 && threadIdx.x < 12) w.parta[(size_t)blockIdx.x * 4 + (threadIdx.x - 8)] = (threadIdx.x & 1) ? -DBL_MAX : DBL_MAX;
     }
 }
 
@@ -582,28 +734,120 @@ __device__ __forceinline__ void bucket_unit_global(const uint2 *__restrict__ src
 // that fit (each filtered from the bucket's pairs), and only a sub-range that still does not fit -- thousands of
 // particles in a few cells -- is sorted in global memory.
 // (MULTI: the one-bucket kernel keeps its 32 registers, the loop costs the other one 64 + spills)
-template <bool MULTI, int BS, int CAP>
+//
+// PLACED (behind k_bin_place): `bstart` is the PREVIOUS update's table, by which the pairs were placed, and `ps.cnt` the
+// true count of every bucket.  A workgroup derives its output start itself, as the sum of the counts in front of its first
+// bucket, and writes this update's table, ps.bnew (what the next update places on), on the way; it zeroes the OTHER half
+// of the cursors' ping-pong pair for its buckets (nobody reads that half in this launch).  A bucket that outgrew its
+// old size gathers its pairs -- those in place and its entries of the overflow list, filtered by key >> lbits -- into a
+// slice of ps.gather and is sorted from there: the sort restores ascending index order inside every fine key whatever
+// the arrival order, so the output is what the four-launch path writes.  One more workgroup, the first of the grid, is the
+// SERVICE workgroup: what k_bin_finish does for the four-launch path (finish_reduce) and the overflow counter of the
+// next update zeroed.  Every dependency is the kernel boundary behind k_bin_place.
+struct PlaceSort {
+    const uint32_t *cnt;      // cursors of k_bin_place: the buckets' counts
+    uint32_t *bnew, *czero;   // this update's bucket starts [nbuckets + 1]; the other cursors
+    const uint2 *ovf;         // the overflow list ...
+    const uint32_t *ovfn;     // ... and its length
+    uint32_t *ovfzero;        // the other overflow counter
+    uint2 *gather;            // n pairs
+    uint32_t ncat;
+    FinishArgs f;
+};
+template <bool MULTI, int BS, int CAP, bool PLACED>
 __global__ __launch_bounds__(BS, 8) void k_bucket_sort(const uint2 *__restrict__ pairs, const uint32_t *__restrict__ bstart, int lbits,
-                                                       BucketOut o, uint32_t nbuckets, uint32_t bpb)
+                                                       BucketOut o, uint32_t nbuckets, uint32_t bpb, PlaceSort ps)
 {
     __shared__ uint32_t tab[1 << SORT_LMAX];
     __shared__ uint2 stage[CAP];
     __shared__ uint32_t ws[BS / 64], bigq[SORT_BIGQ], nbig;
     const uint32_t tid = threadIdx.x, NL = 1u << lbits, mask = NL - 1u;
-    const uint32_t bk0 = MULTI ? blockIdx.x * bpb : blockIdx.x, bk1 = MULTI ? min(nbuckets, (blockIdx.x + 1) * bpb) : blockIdx.x + 1;
+    // the service workgroup is the FIRST of the grid: dispatched first, its reductions and its stores to the host run under
+    // the buckets' work (as the last one it was the kernel's tail: +11 us at 4 M)
+    if (PLACED && blockIdx.x == 0) { // (the stage is its scratch)
+        static_assert(!PLACED || (size_t)CAP * sizeof(uint2) >= (size_t)BS * sizeof(double), "stage too small for the reduction");
+        const uint32_t novf = min(*ps.ovfn, ps.ncat);
+        finish_reduce<BS>(ps.f, 1, novf, reinterpret_cast<double *>(stage), ws);
+        if (tid == 0) *ps.ovfzero = 0u;
+        return;
+    }
+    const uint32_t blk = PLACED ? blockIdx.x - 1u : blockIdx.x;
+    const uint32_t bk0 = MULTI ? blk * bpb : blk, bk1 = MULTI ? min(nbuckets, (blk + 1) * bpb) : blk + 1;
+    uint32_t out_next = 0; // PLACED: the output start of the next bucket (uniform)
+    uint32_t pb_first = 0, pe_first = 0, cnt_first = 0;
+    if (PLACED) {
+        // what the first bucket needs from the tables, requested in front of the sum's barriers (behind them these loads
+        // were one more L2 latency in a workgroup's dependent chain, and a CU runs eight rounds of workgroups)
+        if (bk0 < nbuckets) { pb_first = bstart[bk0]; pe_first = bstart[bk0 + 1]; cnt_first = ps.cnt[bk0]; }
+        // (16-byte loads, four per thread in flight together: one trip up to 8 Ki buckets; one load at a time the sum
+        // was a chain of up to 16 L2 latencies in front of every bucket -- 11 us on the kernel at 4 M)
+        uint32_t part = 0;
+        const uint4 *__restrict__ c4 = reinterpret_cast<const uint4 *>(ps.cnt); // (sort_tables: 16-byte aligned)
+        const uint32_t nv = bk0 >> 2;
+        for (uint32_t b0 = 0; b0 < nv; b0 += 4u * BS) {
+            uint4 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) { const uint32_t i = b0 + q * BS + tid; v[q] = i < nv ? c4[i] : make_uint4(0u, 0u, 0u, 0u); }
+#pragma unroll
+            for (int q = 0; q < 4; q++) part += v[q].x + v[q].y + v[q].z + v[q].w;
+        }
+        if (tid < (bk0 & 3u)) part += ps.cnt[(nv << 2) + tid];
+        for (int o2 = 32; o2 > 0; o2 >>= 1) part += __shfl_xor(part, o2, 64);
+        if ((tid & 63) == 0) ws[tid >> 6] = part;
+        __syncthreads();
+        for (int q = 0; q < BS / 64; q++) out_next += ws[q];
+        __syncthreads(); // ws serves bucket_unit next
+    }
     for (uint32_t bk = bk0; bk < bk1; bk++) {
-        const uint32_t base = bstart[bk], s = bstart[bk + 1] - base;
+        uint32_t base, s, out0;
+        const uint2 *src;
+        if (PLACED) {
+            const bool first = !MULTI || bk == bk0;
+            const uint32_t pb = first ? pb_first : bstart[bk], cap = (first ? pe_first : bstart[bk + 1]) - pb;
+            s = first ? cnt_first : ps.cnt[bk];
+            out0 = out_next;
+            out_next += s;
+            if (tid == 0) {
+                ps.bnew[bk] = out0;
+                ps.czero[bk] = 0u;
+                if (bk == nbuckets - 1u) ps.bnew[nbuckets] = out0 + s;
+            }
+            base = pb;
+            src = pairs + pb;
+            if (s > cap) { // (uniform) the bucket outgrew its old size: its pairs gathered into one slice
+                uint2 *dst = ps.gather + out0;
+                const bool room = (size_t)out0 + s <= ps.ncat; // (always, on counts that sum to n: keeps the stores inside the buffer)
+                if (tid == 0) nbig = 0u;
+                __syncthreads();
+                if (room) {
+                    for (uint32_t i = tid; i < cap; i += BS) dst[i] = pairs[(size_t)pb + i];
+                    const uint32_t novf = min(*ps.ovfn, ps.ncat);
+                    for (uint32_t i = tid; i < novf; i += BS) {
+                        const uint2 p = ps.ovf[i];
+                        if ((p.x >> lbits) == bk) { const uint32_t q = cap + atomicAdd(&nbig, 1u); if (q < s) dst[q] = p; }
+                    }
+                }
+                __syncthreads(); // the slice is complete (and nbig free again) before the workgroup reads it
+                src = room ? dst : src;
+                s = room ? s : min(s, cap);
+            }
+        } else {
+            base = bstart[bk]; s = bstart[bk + 1] - base;
+            out0 = base;
+            src = pairs + base;
+        }
+        (void)base;
         const size_t fk0 = (size_t)bk * NL;
         if (s == 0) { // an empty bucket (the air of a dam break's tank): its slice of the tables is one value
             for (uint32_t k = tid; k < NL; k += BS) {
                 const size_t fk = fk0 + k;
-                if (fk <= o.n_fine) { o.fine_start[fk] = base; if (fk % SPH_NSUB == 0) o.cell_start[fk / SPH_NSUB] = base; }
+                if (fk <= o.n_fine) { o.fine_start[fk] = out0; if (fk % SPH_NSUB == 0) o.cell_start[fk / SPH_NSUB] = out0; }
             }
             continue;
         }
         bool over = false;
         if (s <= (uint32_t)CAP) {
-            bucket_unit<BS, CAP, true>(pairs + base, s, 0u, NL, NL, mask, fk0, base, o, tab, stage, ws, bigq, &nbig, over);
+            bucket_unit<BS, CAP, true>(src, s, 0u, NL, NL, mask, fk0, out0, o, tab, stage, ws, bigq, &nbig, over);
         } else {
             // sub-ranges of the bins: as many as would fit the stage 1.5 times over if the pairs were spread evenly
             uint32_t parts = 2;
@@ -612,9 +856,9 @@ __global__ __launch_bounds__(BS, 8) void k_bucket_sort(const uint2 *__restrict__
             uint32_t done = 0;
             for (uint32_t r = 0; r < parts; r++) {
                 __syncthreads();
-                const uint32_t t = bucket_unit<BS, CAP, false>(pairs + base, s, r * width, (r + 1) * width, NL, mask, fk0, base + done, o, tab,
+                const uint32_t t = bucket_unit<BS, CAP, false>(src, s, r * width, (r + 1) * width, NL, mask, fk0, out0 + done, o, tab,
                                                                stage, ws, bigq, &nbig, over);
-                if (over) bucket_unit_global<BS>(pairs + base, s, r * width, (r + 1) * width, mask, fk0, base + done, t, o, tab, bigq, &nbig);
+                if (over) bucket_unit_global<BS>(src, s, r * width, (r + 1) * width, mask, fk0, out0 + done, t, o, tab, bigq, &nbig);
                 done += t;
             }
         }
@@ -770,50 +1014,80 @@ static int bin_arrays(sph_ctx *c, int narrays, const int *ids, BinArrays *ba, si
     return SPH_OK;
 }
 
-// tables of the sort: [G: cap][bstart: cap + 1][cur: cap]; G must be zero between sorts (k_bin_finish leaves it so)
-static int sort_tables(sph_ctx *c, uint32_t nbuckets, BinWork *w)
+// tables of the sort: [G][bstart: cap + 1 used][cur][bstart'][cur'][overflow counters: 2], cap + 1 rounded up to a multiple
+// of four words each.  G must be
+// zero between sorts (k_bin_finish leaves it so); bstart / cur are ping-pong pairs, `pp` names the half this sort writes
+// (the four-launch path always takes half 0; a placed update the half the previous update did not write).  Between
+// updates the half that is not the last one's has zero cursors, and so has the overflow counter of that half.
+static int sort_tables(sph_ctx *c, uint32_t nbuckets, BinWork *w, int pp = 0)
 {
     const size_t cap = std::max<size_t>(c->sort_tab_entries, 1024);
     if (!c->sort_tab.ptr || nbuckets + 1 > cap) {
         size_t ncap = std::max<size_t>((size_t)nbuckets + 1 + nbuckets / 4, 1024);
         DevBuf nb_;
-        SPH_TRY(nb_.reserve((3 * ncap + 8) * 4));
+        SPH_TRY(nb_.reserve((5 * (ncap + 4) + 8) * 4));
         HIP_TRY(hipMemsetAsync(nb_.ptr, 0, nb_.bytes, c->stream));
         if (c->sort_tab.ptr) { HIP_TRY(hipStreamSynchronize(c->stream)); c->sort_tab.release(); }
         c->sort_tab = nb_;
         c->sort_tab_entries = ncap;
+        c->place.valid = false; // (a regrown table holds nobody's bucket starts)
     }
     uint32_t *t = c->sort_tab.as<uint32_t>();
-    const size_t e = c->sort_tab_entries;
-    w->G = t; w->bstart = t + e; w->cur = t + 2 * e + 1;
+    const size_t e = (c->sort_tab_entries + 4) & ~(size_t)3; // every table starts on a 16-byte boundary (vector loads of G and of the cursors)
+    uint32_t *bstart[2] = {t + e, t + 3 * e}, *cur[2] = {t + 2 * e, t + 4 * e};
+    w->G = t; w->bstart = bstart[pp]; w->cur = cur[pp];
+    w->bprev = bstart[1 - pp]; w->cur2 = cur[1 - pp];
+    w->ovfc = t + 5 * e; w->ovfcur = w->ovfc + pp;
     w->nbuckets = nbuckets;
+    return SPH_OK;
+}
+
+static void finish_args(const BinArrays &ba, const BinWork &w, uint32_t nblocks, FinishArgs *f)
+{
+    memset(f, 0, sizeof *f);
+    f->part = w.part; f->parta = w.parta; f->grp = w.grp; f->xflag = w.xflag;
+    f->out = w.out; f->mail = w.mail; f->seq = w.seq;
+    for (int a = 0; a <= SPH_MAX_ARRAYS; a++) f->first[a] = ba.first[a];
+    f->narrays = ba.narrays; f->mm = w.mm; f->nblk = nblocks;
+}
+
+// the work areas of a key pass (k_bin_keys or k_bin_place) over `nblocks` workgroups; `mail`: a lagged update, whose
+// reduced values go to the host's mailbox under the next sequence number
+static int bin_work(sph_ctx *c, uint32_t nblocks, int mm, int lbits, bool mail, BinWork *w)
+{
+    SPH_TRY(c->red_part.reserve((size_t)nblocks * 13 * sizeof(double)));
+    SPH_TRY(c->red_out.reserve(64 * sizeof(double)));
+    w->part = c->red_part.as<double>();
+    w->parta = w->part + (size_t)nblocks * 8;
+    w->grp = reinterpret_cast<uint32_t *>(w->part + (size_t)nblocks * 12);
+    w->out = c->red_out.as<double>();
+    if (!c->xflag.ptr) {
+        SPH_TRY(c->xflag.reserve(16));
+        HIP_TRY(hipMemsetAsync(c->xflag.ptr, 0, 16, c->stream));
+    }
+    w->xflag = c->xflag.as<uint32_t>();
+    w->lbits = lbits;
+    w->mm = mm;
+    w->mail = mail ? c->pin_async : nullptr;
+    w->seq = mail ? ++c->lag_seq : 0ull;
     return SPH_OK;
 }
 
 // One k_bin_keys launch: `mm` = what to reduce (MM_*), `keys` = null (bounds only) or the key buffer of the concatenation.
 // The reduced values land in c->red_out (device); the caller copies them where it wants them.
 static int launch_bin_keys(sph_ctx *c, const BinArrays &ba, uint32_t nblocks, const GridDesc &g, int mm, uint32_t *keys, uint32_t nbuckets,
-                           int lbits)
+                           int lbits, bool mail = false)
 {
     BinWork w;
     memset(&w, 0, sizeof w);
+    c->place.valid = false; // (the caller that leaves a table a placed update can read says so afterwards)
     SPH_TRY(sort_tables(c, keys ? nbuckets : 1, &w));
-    SPH_TRY(c->red_part.reserve((size_t)nblocks * 13 * sizeof(double)));
-    SPH_TRY(c->red_out.reserve(64 * sizeof(double)));
+    SPH_TRY(bin_work(c, nblocks, mm, lbits, mail, &w));
     w.keys = keys;
-    w.part = c->red_part.as<double>();
-    w.parta = w.part + (size_t)nblocks * 8;
-    w.grp = reinterpret_cast<uint32_t *>(w.part + (size_t)nblocks * 12);
-    w.out = c->red_out.as<double>();
-    if (!c->xflag.ptr) {
-        SPH_TRY(c->xflag.reserve(16));
-        HIP_TRY(hipMemsetAsync(c->xflag.ptr, 0, 16, c->stream));
-    }
-    w.xflag = c->xflag.as<uint32_t>();
-    w.lbits = lbits;
-    w.mm = mm;
+    FinishArgs f;
+    finish_args(ba, w, nblocks, &f);
     hipLaunchKernelGGL(k_bin_keys, dim3(nblocks), dim3(256), 0, c->stream, ba, g, w);
-    hipLaunchKernelGGL(k_bin_finish, dim3(1), dim3(1024), 0, c->stream, ba, w, nblocks, keys ? 1 : 0);
+    hipLaunchKernelGGL(k_bin_finish, dim3(1), dim3(1024), 0, c->stream, f, w, keys ? 1 : 0);
     return SPH_OK;
 }
 
@@ -986,8 +1260,57 @@ static int sort_finish(sph_ctx *c, size_t n, size_t n_fine, long n_cells, int lb
     const uint2 *pp = (const uint2 *)pairs;
     const uint32_t *bs = (const uint32_t *)w.bstart;
     const dim3 grid(div_up(nbuckets, bpb));
-    if (bpb > 1) hipLaunchKernelGGL((k_bucket_sort<true, SORT_BS, SORT_BK_CAP>), grid, dim3(SORT_BS), 0, c->stream, pp, bs, lbits, o, nbuckets, bpb);
-    else hipLaunchKernelGGL((k_bucket_sort<false, SORT_BS, SORT_BK_CAP>), grid, dim3(SORT_BS), 0, c->stream, pp, bs, lbits, o, nbuckets, 1u);
+    PlaceSort ps;
+    memset(&ps, 0, sizeof ps);
+    if (bpb > 1) hipLaunchKernelGGL((k_bucket_sort<true, SORT_BS, SORT_BK_CAP, false>), grid, dim3(SORT_BS), 0, c->stream, pp, bs, lbits, o, nbuckets, bpb, ps);
+    else hipLaunchKernelGGL((k_bucket_sort<false, SORT_BS, SORT_BK_CAP, false>), grid, dim3(SORT_BS), 0, c->stream, pp, bs, lbits, o, nbuckets, 1u, ps);
+    return SPH_OK;
+}
+
+// The placed update: k_bin_place -> k_bucket_sort on the bucket table the previous update left (sph_ctx::place).
+// Beyond SORT_PLACE_NB_MAX buckets the sum every sort workgroup takes over the counts in front of it (4 bytes per bucket
+// and workgroup, from L2) outgrows the launches saved: such grids (the sparse tanks, tens of thousands of buckets) keep the
+// four-launch path.  Beyond n / SORT_PLACE_OVF_DIV pairs in the overflow list of the last placed update the host saw --
+// every overflowing bucket filters the whole list, 8 bytes per entry and bucket -- the next update takes the four-launch
+// path, which also brings the table up to date (0.4 % of the particles: at 4 M a list of 128 KB).
+#define SORT_PLACE_NB_MAX 16384
+#define SORT_PLACE_OVF_DIV 256
+static int sort_placed(sph_ctx *c, const BinArrays &ba, uint32_t nblocks, const GridDesc &g, int mm, size_t n, size_t n_fine, long n_cells,
+                       int lbits, uint32_t nbuckets, const SortDest &d)
+{
+    const int pp = 1 - c->place.pp;
+    BinWork w;
+    memset(&w, 0, sizeof w);
+    SPH_TRY(sort_tables(c, nbuckets, &w, pp));
+    if (!c->place.valid) { sph_set_error("nnps: the bucket table of the previous update is gone"); return SPH_ERR_STATE; } // (never: same nbuckets)
+    SPH_TRY(bin_work(c, nblocks, mm, lbits, true, &w));
+    SPH_TRY(c->place_buf.reserve(2 * (n + 64) * sizeof(uint2)));
+    w.pairs = c->tmp_u32b.as<uint2>();
+    w.ovf = c->place_buf.as<uint2>();
+    w.ncat = (uint32_t)n;
+    hipLaunchKernelGGL(k_bin_place, dim3(nblocks), dim3(256), 0, c->stream, ba, g, w);
+    DevArray &T = *d.T;
+    BucketOut o;
+    memset(&o, 0, sizeof o);
+    o.fkeys = T.fkeys_sorted.as<uint32_t>(); o.keys = T.keys_sorted.as<uint32_t>(); o.perm = T.perm.as<uint32_t>();
+    o.slot = d.merged ? T.slot8.as<uint8_t>() : nullptr;
+    o.co = d.co;
+    o.fine_start = T.fine_start.as<uint32_t>(); o.cell_start = T.cell_start.as<uint32_t>();
+    o.n_fine = (uint32_t)n_fine; o.n_cells = (uint32_t)n_cells;
+    o.scratch = c->tmp_u32a.as<uint2>();
+    PlaceSort ps;
+    memset(&ps, 0, sizeof ps);
+    ps.cnt = w.cur; ps.bnew = w.bstart; ps.czero = w.cur2;
+    ps.ovf = w.ovf; ps.ovfn = w.ovfcur; ps.ovfzero = w.ovfc + (1 - pp);
+    ps.gather = c->place_buf.as<uint2>() + (n + 64);
+    ps.ncat = (uint32_t)n;
+    finish_args(ba, w, nblocks, &ps.f);
+    const uint32_t bpb = std::min<uint32_t>(16u, std::max<uint32_t>(1u, nbuckets / 4096u));
+    const dim3 grid(div_up(nbuckets, bpb) + 1); // ... and the service workgroup
+    const uint2 *pairs = (const uint2 *)w.pairs;
+    if (bpb > 1) hipLaunchKernelGGL((k_bucket_sort<true, SORT_BS, SORT_BK_CAP, true>), grid, dim3(SORT_BS), 0, c->stream, pairs, w.bprev, lbits, o, nbuckets, bpb, ps);
+    else hipLaunchKernelGGL((k_bucket_sort<false, SORT_BS, SORT_BK_CAP, true>), grid, dim3(SORT_BS), 0, c->stream, pairs, w.bprev, lbits, o, nbuckets, 1u, ps);
+    c->place.pp = pp;
     return SPH_OK;
 }
 
@@ -1589,9 +1912,20 @@ static int nnps_rho_flag(sph_ctx *c)
 static int lag_wait(sph_ctx *c)
 {
     if (c->lag.pending) {
-        HIP_TRY(hipEventSynchronize(c->lag_ev));
+        // the sequence number is stored behind the payload: normally it arrived a step ago; else the stream is drained
+        // (which completes the kernel that stores it), once
+        const unsigned long long *seq = reinterpret_cast<const unsigned long long *>(c->pin_async + MM_OUT_SEQ);
+        if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) != c->lag_seq) {
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) != c->lag_seq) {
+                sph_set_error("nnps: the bounds of update %llu never reached the host (it holds %llu)", c->lag_seq, __atomic_load_n(seq, __ATOMIC_ACQUIRE));
+                return SPH_ERR_STATE;
+            }
+        }
         c->lag.pending = false;
         c->sort_groups = c->pin_async[MM_OUT_GROUPS];
+        c->place.ovf_seen = (uint32_t)c->pin_async[MM_OUT_OVF];
+        c->timers[T_N_PLACE_OVF].count += (long)c->place.ovf_seen;
         if (c->pin_async[MM_OUT_XFLAG] != 0.0) SPH_TRY(nnps_rho_flag(c));
     }
     return SPH_OK;
@@ -1628,8 +1962,8 @@ extern "C" int sph_nnps_update(sph_ctx *c, int dim, int narrays, const int *ids,
         }
     }
     if (!c->pin_async) {
-        HIP_TRY(hipHostMalloc((void **)&c->pin_async, 64 * sizeof(double), hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&c->lag_ev, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc((void **)&c->pin_async, 64 * sizeof(double), hipHostMallocCoherent)); // (the device stores into it while kernels run)
+        memset(c->pin_async, 0, 64 * sizeof(double));
     }
     BinArrays ba;
     size_t n_cat = 0;
@@ -1689,6 +2023,7 @@ extern "C" int sph_nnps_update(sph_ctx *c, int dim, int narrays, const int *ids,
         if (nblocks && c->pinned[MM_OUT_XFLAG] != 0.0) SPH_TRY(nnps_rho_flag(c));
         c->lag.valid = !bounds;
         c->lag.pending = false;
+        c->place.ovf_seen = 0;
     }
     mm[3] = hr[0]; mm[7] = hr[1];
     // masses: an update that did not look keeps what the last look found while nothing wrote m (m_dirty)
@@ -1729,6 +2064,7 @@ extern "C" int sph_nnps_update(sph_ctx *c, int dim, int narrays, const int *ids,
     c->park_cells = park_cells;
     c->n_cells = n_cells_tab;
     GridDesc g;
+    memset(&g, 0, sizeof g); // (compared bytewise with the previous update's)
     for (int k = 0; k < 3; k++) { g.xmin[k] = c->xmin[k]; g.nc[k] = c->nc[k]; }
     grid_set_cell(g, cell_size);
     g.park_base = (uint32_t)(n_cells_alloc * SPH_NSUB); g.park_bins = (uint32_t)(park_cells * SPH_NSUB); g.park_n = (uint32_t)n_cat;
@@ -1751,6 +2087,7 @@ extern "C" int sph_nnps_update(sph_ctx *c, int dim, int narrays, const int *ids,
     c->merged_valid = false;
     c->tables_valid = true;
     c->ghosts_binned = false;
+    c->sorted_T = nullptr;
     c->merged.dlist_n = 0;
     for (int a = 0; a < narrays; a++) c->arr[ids[a]].dlist_n = 0;
     nnps_face_planes(c); // ghost split: where this step's ghosts will lie (known before they arrive)
@@ -1785,14 +2122,33 @@ extern "C" int sph_nnps_update(sph_ctx *c, int dim, int narrays, const int *ids,
             if (c->via_unordered && T->unordered && T->perm_direct_n == T->n) via = T->perm.as<uint32_t>();
             for (int a = 0; a < narrays; a++) if (&c->arr[ids[a]] == T) ba.via[a] = via;
         }
-        SPH_TRY(launch_bin_keys(c, ba, nblocks, g, mm_async, c->tmp_u32a.as<uint32_t>(), nbuckets, lbits));
-        c->last_keys_via = via != nullptr; c->last_keys_n = merged_first ? 0 : n_cat; c->last_keys_array = merged_first ? nullptr : T;
-        reduced = true;
         SortDest d;
         d.T = T; d.merged = merged_first; d.via = via;
         d.co.narrays = narrays;
         for (int a = 0; a <= SPH_MAX_ARRAYS; a++) d.co.off[a] = a < narrays ? ba.off[a] : (uint32_t)n_cat;
-        SPH_TRY(sort_finish(c, n_cat, n_fine, n_cells_tab, lbits, nbuckets, d));
+        // The placed update (two launches): a lagged update on the grid, the arrays and the bucket table of the update
+        // before it, with few pairs in the overflow list the host last saw.  Anything else: the four launches.
+        static_assert(sizeof(GridDesc) <= sizeof c->place.grid, "sph_ctx::place.grid too small");
+        bool place = lagged && c->sort_place && !via && c->place.valid && c->place.merged == merged_first && c->place.n_cat == n_cat &&
+                     c->place.n_fine == n_fine && c->place.lbits == lbits && c->place.nbuckets == nbuckets && c->place.narrays == narrays &&
+                     memcmp(c->place.grid, &g, sizeof g) == 0 && nbuckets <= SORT_PLACE_NB_MAX &&
+                     (size_t)c->place.ovf_seen * SORT_PLACE_OVF_DIV <= n_cat;
+        for (int a = 0; place && a < narrays; a++) place = c->place.ids[a] == ids[a] && c->place.n[a] == ba.n[a];
+        if (place) {
+            SPH_TRY(sort_placed(c, ba, nblocks, g, mm_async, n_cat, n_fine, n_cells_tab, lbits, nbuckets, d));
+            c->timers[T_N_PLACED].count++;
+        } else {
+            SPH_TRY(launch_bin_keys(c, ba, nblocks, g, mm_async, c->tmp_u32a.as<uint32_t>(), nbuckets, lbits, lagged));
+            SPH_TRY(sort_finish(c, n_cat, n_fine, n_cells_tab, lbits, nbuckets, d));
+            // the table this sort leaves (half 0 of the pairs, the other half's cursors zero) is what a placed update reads
+            c->place.valid = true; c->place.pp = 0; c->place.merged = merged_first; c->place.n_cat = n_cat; c->place.n_fine = n_fine;
+            c->place.lbits = lbits; c->place.nbuckets = nbuckets; c->place.narrays = narrays;
+            memcpy(c->place.grid, &g, sizeof g);
+            for (int a = 0; a < narrays; a++) { c->place.ids[a] = ids[a]; c->place.n[a] = ba.n[a]; }
+        }
+        c->last_keys_via = via != nullptr; c->last_keys_n = merged_first ? 0 : n_cat; c->last_keys_array = merged_first ? nullptr : T;
+        reduced = true;
+        c->sorted_T = T; c->sorted_n = n_cat; c->sorted_n_fine = n_fine;
         SPH_TRY(nnps_tile_order(c, *T, n_cat));
         SPH_TRY(nnps_dest_list(c, *T, merged_first, narrays, ids, n_cat));
         if (!merged_first) T->perm_direct_n = n_cat;
@@ -1829,10 +2185,8 @@ extern "C" int sph_nnps_update(sph_ctx *c, int dim, int narrays, const int *ids,
         }
     }
     if (lagged) {
-        if (!reduced && nblocks) SPH_TRY(launch_bin_keys(c, ba, nblocks, g, mm_async, nullptr, 0, lbits));
-        // this update's bounds: on their way, nobody waits
-        HIP_TRY(hipMemcpyAsync(c->pin_async, c->red_out.ptr, MM_OUT_N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipEventRecord(c->lag_ev, c->stream));
+        if (!reduced && nblocks) SPH_TRY(launch_bin_keys(c, ba, nblocks, g, mm_async, nullptr, 0, lbits, true));
+        // this update's bounds: on their way (stored into pin_async by the kernel that reduced them), nobody waits
         c->lag.pending = true;
     }
     HIP_TRY(hipGetLastError());
@@ -1871,6 +2225,7 @@ extern "C" int sph_nnps_update_ghosts(sph_ctx *c, int axis, double lo, double hi
     if (c->n_cells <= 0 || c->narrays < 1) { sph_set_error("sph_nnps_update_ghosts: call sph_nnps_update first"); return SPH_ERR_STATE; }
     HIP_TRY(hipSetDevice(c->device));
     ScopedTimer tm(c, T_NNPS);
+    c->place.valid = false;
     // the grid must still describe the real particles: nothing but appends since the update
     for (int a = 0; a < c->narrays; a++) {
         DevArray &A = c->arr[c->ids[a]];
@@ -1986,6 +2341,31 @@ extern "C" int sph_nnps_get_order(sph_ctx *c, int id, uint32_t *perm)
     DevArray &A = c->arr[id];
     if (A.n == 0) return SPH_OK;
     HIP_TRY(hipMemcpyAsync(perm, A.perm.ptr, A.n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SPH_OK;
+}
+
+// One table of the ONE sort of the last update (the merged order, or its one non-empty array), as the sort left it.
+extern "C" int sph_nnps_read_table(sph_ctx *c, int which, void *out, size_t cap_bytes, size_t *bytes)
+{
+    if (!c || !bytes) { sph_set_error("sph_nnps_read_table: bad arguments"); return SPH_ERR_ARG; }
+    DevArray *T = c->sorted_T;
+    if (!c->nnps_valid || !T) { sph_set_error("sph_nnps_read_table: the last update did not sort its arrays in one sort"); return SPH_ERR_STATE; }
+    const DevBuf *b = nullptr;
+    size_t nb = 0;
+    switch (which) {
+    case SPH_TABLE_PERM: b = &T->perm; nb = c->sorted_n * 4; break;
+    case SPH_TABLE_FINE_KEYS: b = &T->fkeys_sorted; nb = c->sorted_n * 4; break;
+    case SPH_TABLE_FINE_START: b = &T->fine_start; nb = (c->sorted_n_fine + 1) * 4; break;
+    case SPH_TABLE_CELL_START: b = &T->cell_start; nb = ((size_t)c->n_cells + 1) * 4; break;
+    case SPH_TABLE_SLOT: b = &T->slot8; nb = c->merged_valid ? c->sorted_n : 0; break;
+    default: sph_set_error("sph_nnps_read_table: unknown table %d", which); return SPH_ERR_ARG;
+    }
+    *bytes = nb;
+    if (!out || nb == 0) return SPH_OK;
+    if (cap_bytes < nb || !b->ptr || b->bytes < nb) { sph_set_error("sph_nnps_read_table: %zu bytes needed", nb); return SPH_ERR_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(out, b->ptr, nb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }

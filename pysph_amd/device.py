@@ -75,6 +75,7 @@ SIGNATURES = {
     'sph_nnps_get_csr': (C.c_int, [_P, C.c_int, C.c_int, _PU, C.c_size_t, _PU,
                                    C.c_size_t, C.POINTER(C.c_size_t)]),
     'sph_nnps_get_order': (C.c_int, [_P, C.c_int, _PU]),
+    'sph_nnps_read_table': (C.c_int, [_P, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     'sph_nnps_reorder_array': (C.c_int, [_P, C.c_int]),
     'sph_eval_group': (C.c_int, [_P, C.POINTER(SphKernel),
                                  C.POINTER(SphGroup), C.c_double, C.c_double]),
