@@ -137,9 +137,17 @@ enum sph_eq_kind {
                                                  (writes au av aw ae del2e dt_cfl aalpha1 aalpha2)                         */
     SPH_EQ_SCALE_SMOOTHING_LENGTH = 37,       /* :13-19     par: factor   (no sources; writes h) */
     SPH_EQ_UPDATE_H_FROM_VOLUME = 38,         /* :22-29     par: k dim1 (= 1 / dim)   (no sources; writes h) */
-    SPH_EQ_MPM_UPDATE_GHOST_PROPS = 39        /* :486-497   (no sources, Group(real=False)): p and cs of every row behind the real
+    SPH_EQ_MPM_UPDATE_GHOST_PROPS = 39,       /* :486-497   (no sources, Group(real=False)): p and cs of every row behind the real
                                                  ones from the row the user property orig_idx names (a real row; an image
                                                  is a copy of its row and so carries that row's orig_idx)                 */
+    /* Godunov SPH (pysph/sph/gas_dynamics/gsph.py, riemann_solver.py).  px py pz ux uy uz vx vy vz wx wy wz are user
+     * properties of those names next to the gas-dynamics ones.                                                         */
+    SPH_EQ_GSPH_GRADIENTS = 40,               /* gsph.py:61-101     (writes px..pz ux..uz vx..vz wx..wz: twelve sums with DWI) */
+    SPH_EQ_GSPH_UPDATE_GHOST_PROPS = 41,      /* :104-145   (no sources, Group(real=False)): the twelve gradients, grhox..z, dwdh,
+                                                 rho, div, p, cs of every row behind the real ones from the row orig_idx names */
+    SPH_EQ_GSPH_ACCELERATION = 42             /* :148-541   par: g1 g2 monotonicity rsolver interpolation interface_zero hybrid
+                                                 blend_alpha tf gamma niter tol   (writes au av aw ae; solver failures are
+                                                 counted in a device word: sph_gsph_failures)                           */
 };
 
 /* One Equation(dest, sources) instance: pysph/sph/equation.py:392-420. */
@@ -693,7 +701,8 @@ enum sph_stepper {
     SPH_STEP_RIGID_EULER = 5,/* EulerStepRigidBody  pysph/sph/rigid_body.py:695-715 (stage 1 only)          */
     SPH_STEP_EDAC = 6,       /* EDACStep            pysph/sph/wc/edac.py:95-133  (p0, ap: user properties)  */
     SPH_STEP_EDAC_TVF = 7,   /* EDACTVFStep         pysph/sph/wc/edac.py:493-540                            */
-    SPH_STEP_GASD = 8        /* GasDFluidStep       integrator_step.py:351-428 (h0, ah, converged, omega, alpha*: user properties) */
+    SPH_STEP_GASD = 8,       /* GasDFluidStep       integrator_step.py:351-428 (h0, ah, converged, omega, alpha*: user properties) */
+    SPH_STEP_GSPH = 9        /* GSPHStep            integrator_step.py:431-449 (stage 1 only)                */
 };
 int sph_integrate_stage(sph_ctx *ctx, int array_id, int stepper, int stage, double dt);
 /* The convergence word of the last sph_eval_group call that ran an iterating SPH_EQ_GASD_SUMMATION_DENSITY
@@ -701,6 +710,12 @@ int sph_integrate_stage(sph_ctx *ctx, int array_id, int stepper, int stage, doub
  * equation_has_converged = -1), else 0.  Every lane that fails stores the same constant into one device word, no
  * atomics; the library reads it once per call.                                                                   */
 int sph_gasd_unconverged(sph_ctx *ctx, int *flag);
+/* Riemann-solver failures of the last sph_eval_group call that ran SPH_EQ_GSPH_ACCELERATION: the number of
+ * (destination, source) pairs whose solve returned without a result where the reference's returns 1 -- `exact` on the
+ * vacuum test or with its loop index at niter - 1, `van_leer` on a negative state, `hllc` on wave speeds that match no
+ * case (of the second solve of `hybrid` too).  Such a pair contributes with pstar = ustar = 0.  The sweep counts with
+ * one atomic add per failing pair into a device word; this call is the only host round trip, made when asked.      */
+int sph_gsph_failures(sph_ctx *ctx, unsigned long long *count);
 /* min over the first n_real particles of a property (h_minimum,
  * pysph/sph/integrator.py:150-160).                                        */
 int sph_reduce_min(sph_ctx *ctx, int array_id, int prop, double *out);
@@ -821,6 +836,9 @@ int sph_rigid_motion(sph_ctx *ctx, int array_id, int real_only, long start, long
  *                    skips its neighbour work and only restores the raw arho and div (default 0: DESIGN.md section 7g);
  *                    acts in calls the host marks with "gasd_repeat" 1 -- the second and later iterations of ONE
  *                    iterated group, between which nothing but the group and the neighbour update ran
+ *   "gsph_keep"      1: the next GSPH force sweeps add to the failure word of sph_gsph_failures instead of clearing it -- set by
+ *                    a host that hands ONE group over in several sph_eval_group calls (one per destination), around the
+ *                    second and later ones
  *   "row_mod3"       order in which a wavefront visits its 3x3 rows of cells: 3 (default) = the row whose
  *                    (y mod 3, z mod 3) equals the step, so that all wavefronts in flight walk rows of one
  *                    residue class at a time and find each other's lines in L1 / L2; 1 / 2 = y / z only;
@@ -846,7 +864,7 @@ int sph_timer_reset(sph_ctx *ctx);
  * delta-SPH or laminar-viscosity terms), "pair_delta_sph_pre" (moment matrix and
  * renormalised density gradient), "pair_edac" (the EDAC force group), "pair_avg_pressure"
  * (ComputeAveragePressure, alone or with a density summation), "pair_gasd_density" (the gas-dynamics density sweep with
- * its Newton step for h), "pair_gasd_mpm" (MPMAccelerations); the counter "n_gasd_skipped" (wavefronts of that sweep
+ * its Newton step for h), "pair_gasd_mpm" (MPMAccelerations), "pair_gsph_gradients" (GSPHGradients), "pair_gsph" (GSPHAcceleration); the counter "n_gasd_skipped" (wavefronts of that sweep
  * that left early under option gasd_skip); out: total ms and launches.  Launch counters (ms = 0, counted
  * whether or not timing is enabled): "n_eos_fused" (pair launches on the 64-byte
  * EOS-fused records), "n_eos_absorbed" (of those, the ones whose record packing ran the Tait EOS: sph_group.src_eos 3), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group

@@ -285,8 +285,17 @@ class _BuiltinUnit(object):
                 self.gasd_arrays.update([eq.dest] + list(eq.sources or []))
                 if kind == _GASD_DENSITY_KIND and vals[3]:
                     self.gasd_iterating.append(eq)
-                if kind == _GASD_GHOST_KIND:
+                if kind in _GASD_GHOST_KINDS:
                     owner.orig_idx_arrays.add(eq.dest)
+                if kind == _GSPH_GRAD_KIND:
+                    owner.gsph_grad = True
+                if kind == _GSPH_GHOST_KIND:
+                    owner.gsph_ghost = True
+                if kind == _GSPH_FORCE_KIND:
+                    self.gsph_force = True
+                    # Riemann-solver failures of the last evaluation, read from the device when called (no round trip
+                    # otherwise): the count of the sph_eval_group call this equation ran in
+                    eq.solver_failures = owner.solver_failures
             dprops = _columns(arrays[eq.dest], dprops)
             if kind in _WRITES_H_KINDS and (kind != _GASD_DENSITY_KIND or vals[3]):
                 owner.outputs_exact[eq.dest].add('h')      # (the tables' 'h' is an input everywhere else)
@@ -516,7 +525,10 @@ class _CGroup(object):
         self.outputs_exact = defaultdict(set)  # generated families: exactly the written properties
         self.units = []
         self.rigid_arrays = set()         # arrays whose per-body state the group reads or writes
-        self.orig_idx_arrays = set()      # arrays whose orig_idx column MPMUpdateGhostProps reads
+        self.orig_idx_arrays = set()      # arrays whose orig_idx column MPMUpdateGhostProps / GSPHUpdateGhostProps reads
+        self._failures_ev = None          # the evaluator whose context holds the GSPH failure word (set when the group runs)
+        self.gsph_grad = self.gsph_ghost = False   # the group holds GSPHGradients / GSPHUpdateGhostProps
+        self.ghosts_first = None          # a GSPHGradients group: the GSPHUpdateGhostProps group behind it, run before it too
         self.moments = {}                 # RigidBodyMoments equation -> its unit: run in place of the reduce hook
         self.eos_absorbed_by = None       # annotate_plan: the pair group after this Tait-EOS group that may run the EOS itself
         self.absorbs_eos = False          # ... and that pair group's side of it
@@ -612,20 +624,39 @@ class _CGroup(object):
         return bool(self.absorbs_eos and ev.ctx.options.get('eos_absorb', 1)
                     and (len(self.units) == 1 or self._shared()))
 
+    def solver_failures(self):
+        """Pairs of this group's last evaluation whose Riemann solve failed (``GSPHAcceleration``: the reference's
+        solver returned 1 without a result; such a pair entered with ``pstar = ustar = 0``).  One device word,
+        counted over every destination of the group; read here, when asked (``sph_gsph_failures``)."""
+        ev = self._failures_ev
+        if ev is None:
+            return 0
+        count = C.c_ulonglong(0)
+        dev._check(ev.lib.sph_gsph_failures(ev.ctx._h, C.byref(count)))
+        return int(count.value)
+
     def run(self, ev, t, dt):
         if self.eos_absorbed_by is not None and self.eos_absorbed_by.will_absorb(ev):
             return                       # the pair group after this one runs the equation (src_eos = 3)
         absorb = self.will_absorb(ev)
         shared = self._shared()
+        self._failures_ev = ev
         if not shared:
+            counting = False             # a GSPH force unit of this group has run: the next one adds to its failure word
             for u in self.units:
                 if absorb:               # (one unit: will_absorb) the promise of 1, the EOS still to run
                     u.cg.src_eos = 3
+                gsph = getattr(u, 'gsph_force', False)
+                if gsph and counting:
+                    ev.ctx.set_option('gsph_keep', 1)
                 try:
                     u.run(ev, t, dt)
                 finally:
                     if absorb:
                         u.cg.src_eos = 1
+                    if gsph and counting:
+                        ev.ctx.set_option('gsph_keep', 0)
+                counting = counting or gsph
             return
         for u in self.units:
             if u.delta_sph_arrays or u.edac_arrays or u.gasd_arrays:
@@ -652,8 +683,11 @@ class _CGroup(object):
             u.read_convergence(ev)
 
 
-_GASD_KINDS = (34, 35, 36, 37, 38, 39)    # gas dynamics: density sweep, ideal-gas EOS, MPM accelerations, the two h equations, ghost p / cs
-_GASD_GHOST_KIND = 39
+_GASD_KINDS = (34, 35, 36, 37, 38, 39, 40, 41, 42)    # gas dynamics: density sweep, ideal-gas EOS, MPM accelerations, the two h equations, ghost p / cs; GSPH gradients, ghost columns, accelerations
+_GASD_GHOST_KINDS = (39, 41)          # MPMUpdateGhostProps, GSPHUpdateGhostProps: read orig_idx
+_GSPH_GRAD_KIND = 40
+_GSPH_GHOST_KIND = 41
+_GSPH_FORCE_KIND = 42
 _GASD_DENSITY_KIND = 34
 _WRITES_H_KINDS = (29, 34, 37, 38)    # UpdateSmoothingLengthFerrari; the iterating density sweep; scale h; h from the volume
 _EDAC_KINDS = (30, 31, 32, 33)        # average pressure, the two pressure gradients, the pressure rate
@@ -854,6 +888,14 @@ class HipAccelerationEval(object):
             groups = group_equations(self.a_eval.equations)
         self.plan = [self._plan_group(g, ids) for g in groups]
         annotate_plan(self.plan)
+        # GSPHScheme(has_ghosts=True) puts GSPHUpdateGhostProps BEHIND GSPHGradients, whose sums read p and rho of the
+        # images: in the reference those date from the last domain update (rho of the first density sweep, p of the
+        # evaluation before).  Here the ghost group runs before the gradient group as well, so that a periodic box
+        # computes what its explicit tiling computes; its run behind the gradients stays.
+        leaves = list(self._leaves(self.plan))
+        for prev, cur in zip(leaves, leaves[1:]):
+            if prev.gsph_grad and cur.gsph_ghost:
+                prev.ghosts_first = cur
         self.inputs = defaultdict(set)
         self.outputs = defaultdict(set)
         self.outputs_exact = defaultdict(set)
@@ -1052,6 +1094,9 @@ class HipAccelerationEval(object):
             for eq in g.equations:
                 if hasattr(eq, 'py_initialize'):
                     self._host_hook(eq.py_initialize, self.arrays[eq.dest], t, dt)
+            if item.ghosts_first is not None:
+                item.ghosts_first.refresh_range()
+                item.ghosts_first.run(self, t, dt)
             item.refresh_range()
             item.run(self, t, dt)
             for eq in g.equations:

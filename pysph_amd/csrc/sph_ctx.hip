@@ -150,7 +150,7 @@ int sph_ctx_destroy(sph_ctx *c)
     for (auto &R : c->rigid) { R.state.release(); R.order.release(); R.chunk.release(); R.chunk_start.release(); R.partial.release(); }
     c->io_counts.release();
     for (DevBuf *b : {&c->dbgc, &c->gapq, &c->cub_tmp, &c->red_part, &c->red_out, &c->posh, &c->aux, &c->fposb, &c->dkeys, &c->dperm,
-                      &c->tmp_u32a, &c->tmp_u32b, &c->gen_state, &c->nlbuf, &c->splitcnt, &c->scan_part, &c->bigq, &c->sort_tab, &c->place_buf, &c->xflag, &c->dom_counts})
+                      &c->tmp_u32a, &c->tmp_u32b, &c->gen_state, &c->nlbuf, &c->splitcnt, &c->scan_part, &c->bigq, &c->sort_tab, &c->place_buf, &c->xflag, &c->dom_counts, &c->gsph_word})
         b->release();
     for (auto &b : c->csr_start) b.release();
     for (auto &b : c->csr_nbrs) b.release();
@@ -375,6 +375,7 @@ int sph_set_option(sph_ctx *c, const char *key, long value)
     if (strcmp(key, "row_lds") == 0) { c->row_lds = value; return SPH_OK; }
     if (strcmp(key, "gasd_skip") == 0) { c->gasd_skip = value; return SPH_OK; }
     if (strcmp(key, "gasd_repeat") == 0) { c->gasd_repeat = value; return SPH_OK; }
+    if (strcmp(key, "gsph_keep") == 0) { c->gsph_keep = value; return SPH_OK; }
     if (strcmp(key, "fill_holes") == 0) { c->fill_holes = value ? 1 : 0; return SPH_OK; }
     if (strcmp(key, "dest_list") == 0) { c->dest_list = value < 0 ? 0 : (value > 2 ? 2 : value); c->nnps_valid = false; return SPH_OK; }
     if (strcmp(key, "merge_arrays") == 0) { c->merge_arrays = value ? 1 : 0; c->nnps_valid = false; return SPH_OK; }
@@ -460,7 +461,7 @@ int sph_timer_get(sph_ctx *c, const char *key, double *ms, long *count)
 {
     static const char *names[T_COUNT] = {"nnps", "pack", "eos", "pair", "stage",
                                          "pair_none", "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad", "pair_elastic",
-                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure", "pair_gasd_density", "pair_gasd_mpm",
+                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure", "pair_gasd_density", "pair_gasd_mpm", "pair_gsph_gradients", "pair_gsph",
                                          "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep", "n_eos_absorbed", "n_gasd_skipped", "n_placed", "n_place_overflow"};
     SPH_TRY(timer_drain(c));
     for (int i = 0; i < T_COUNT; i++)

@@ -69,6 +69,7 @@ struct EosArgs {
     size_t start, stop;
     double *q[SPH_PROP_COUNT]; // every device property of the destination (elastic equations)
     uint32_t *tflag;           // MonaghanArtificialStress: set to 1 when any r_ij is non-zero (DevArray::tflag), or null
+    int gcol[20];              // GSPHUpdateGhostProps: the twenty columns an image row takes from its row
 };
 
 // Symmetric 3x3 eigen-decomposition by cyclic Jacobi rotations.  The reference
@@ -238,6 +239,16 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
         a.cs[i] = a.cs[idx];
         break;
     }
+    case SPH_EQ_GSPH_UPDATE_GHOST_PROPS: { // gas_dynamics/gsph.py:113-145; par as above, gcol: px..wz grhox..z dwdh rho div p cs
+        const size_t n_real = (size_t)a.par[0];
+        if (i < n_real) break;
+        const double oi = a.q[(int)a.par[1]][i];
+        if (!(oi >= 0.0 && oi < (double)n_real)) break;
+        const size_t idx = (size_t)oi;
+#pragma unroll
+        for (int k = 0; k < 20; k++) a.q[a.gcol[k]][i] = a.q[a.gcol[k]][idx];
+        break;
+    }
     }
 }
 
@@ -254,7 +265,7 @@ enum { F_CONT = 1, F_MOM = 2, F_XSPH = 4, F_TENSILE = 8,               // WCSPH
        F_SD = 1, F_TVFSD = 2,                                           // density
        F_TP = 1, F_TVISC = 2, F_TAV = 4, F_TAS = 8 };                   // TVF force
 
-#define MAX_AUX 20
+#define MAX_AUX 24
 struct PackArgs {
     const uint32_t *perm;
     size_t n;
@@ -266,6 +277,9 @@ struct PackArgs {
                                   // 3: aux[6..11] = (s_ij - p delta_ij)/rho^2 (p = aux[18], rho = aux[4])
                                   // 4: aux[3] = m/rho (m = aux[3], rho = aux[4]; aux[4] itself is not stored)
                                   // 5: aux[0] = the particle's original index (neighbour lists)
+                                  // 6: aux[15..20] = ux, uy+vx, uz+wx, vy, vz+wy, wz from the nine velocity gradients
+                                  //    aux[15..23] (GSPHAcceleration reads them through eij . G . eij only)
+                                  // 7: aux[4] = m/rho (m = aux[4], rho = aux[5]; aux[5] itself is not stored)
     double4 *posh;
     double *aux;
     double *rec;                  // non-null: interleaved records [x y z h aux... pad], nr doubles each
@@ -338,7 +352,7 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a)
     // (compile-time layouts read the slots their record holds: WCSPH u v w m rho tmpj cs p = 0..7, elastic 0..17 + p)
     constexpr int NV = (LAYOUT == 6 || LAYOUT == 7 || LAYOUT == 12 || LAYOUT == 13) ? 8 : (LAYOUT == 2 ? 1 : (LAYOUT == 3 || LAYOUT == 8 || LAYOUT == 9) ? 11 : MAX_AUX);
 #pragma unroll
-    for (int k = 0; k < MAX_AUX; k++) v[k] = (k < NV && (k < a.na || (a.derived == 3 && k == 18) || (a.derived == 4 && k == 4)) && a.src[k]) ? a.src[k][o] : 0.0;
+    for (int k = 0; k < MAX_AUX; k++) v[k] = (k < NV && (k < a.na || (a.derived == 3 && k == 18) || (a.derived == 4 && k == 4) || (a.derived == 6 && k < 24) || (a.derived == 7 && k == 5)) && a.src[k]) ? a.src[k][o] : 0.0;
     if constexpr (LAYOUT == 6 || LAYOUT == 7 || LAYOUT == 12 || LAYOUT == 13) {
         if (a.eos_abs) { // the Tait EOS of this particle, as k_nosrc would have left it (p is not read: a.src[7] is null)
             double p, cs;
@@ -352,6 +366,12 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs a)
     if (a.derived == 2) { double Vj = 1. / v[8]; v[10] = Vj * Vj; } // Vj2, transport_velocity.py:303-306
     if (a.derived == 4) v[3] = v[3] / v[4]; // m/rho, basic_equations.py:103,139 (VelocityGradient tmp)
     if (a.derived == 5) v[0] = (double)o;
+    if (a.derived == 7) { v[4] = v[4] / v[5]; v[5] = 0.0; } // m/rho, gsph.py:81,86 (GSPHGradients)
+    if (a.derived == 6) { // gsph.py:269-284: the symmetric sums of the velocity gradient
+        const double uy = v[16], uz = v[17], vx = v[18], vy = v[19], vz = v[20], wx = v[21], wy = v[22], wz = v[23];
+        v[16] = uy + vx; v[17] = uz + wx; v[18] = vy; v[19] = vz + wy; v[20] = wz;
+        v[21] = v[22] = v[23] = 0.0;
+    }
     if (a.derived == 3) { // (sigma_ij)/rho^2 with sigma = s - p I: solid_mech/basic.py:281-283,333-339,367-378
         const double r21 = 1. / (v[4] * v[4]), pr = v[18];
         v[6] = (v[6] - pr) * r21; v[7] *= r21; v[8] *= r21;
@@ -1755,6 +1775,486 @@ template <class T> struct FamMPM_T {
     }
 };
 
+// ---- Godunov SPH (pysph/sph/gas_dynamics/gsph.py, riemann_solver.py) --------------------------------------------
+// GSPHGradients (:61-101): the twelve sums px..pz ux..uz vx..vz wx..wz with DWI, one launch; finish() writes all of
+// them, which is the reference's initialize.  Records [x y z h | p u v w m/rho -].
+enum { F_GGRAD = 1 };
+template <class T> struct FamGSPHGrad_T {
+    typedef T Real;
+    static constexpr bool PRED = true; // every sum carries DWI, masked for a pair outside the criterion
+    static constexpr uint32_t CF0 = F_GGRAD;
+    static constexpr int MINB = 3; // (4 spills twelve VGPRs in fp64 under variable h: DESIGN.md section 7h)
+    static constexpr int NA = 5; // p u v w m/rho
+    static constexpr int NR = 10;
+    struct Params { double *g[12]; }; // px py pz ux uy uz vx vy vz wx wy wz
+    struct Dest { T q[4]; T g[12]; };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        for (int k = 0; k < 4; k++) D.q[k] = a[k];
+        for (int k = 0; k < 12; k++) D.g[k] = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        PairGeomT<T> gij, g;
+        pair_geom<KK, UH>(gij, pi, pj, r2, a);
+        pair_geom_at<KK, UH>(g, gij, pi.w, a);
+        T tg = pair_gradfac<KK, UH>(g);
+        tg = pass ? tg : T(0.0);
+        const T dw[3] = {tg * g.xij[0], tg * g.xij[1], tg * g.xij[2]};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const T tmp = s[4] * (s[i] - D.q[i]);
+#pragma unroll
+            for (int j = 0; j < 3; j++) D.g[3 * i + j] += tmp * dw[j];
+        }
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+#pragma unroll
+        for (int k = 0; k < 12; k++) a.p.g[k][o] = (double)D.g[k];
+    }
+};
+
+// The Riemann solvers of riemann_solver.py, in the arithmetic of the sweep.  Each returns 0 with (pstar, ustar) set, or 1
+// where the reference's returns 1 WITHOUT writing its result: the caller's zero-initialised pair stands.  No printing.
+template <class T> __device__ __forceinline__ T gs_pow(T x, T y);
+template <> __device__ __forceinline__ double gs_pow<double>(double x, double y) { return pow(x, y); }
+template <> __device__ __forceinline__ float gs_pow<float>(float x, float y) { return powf(x, y); }
+template <class T> __device__ __forceinline__ T gs_sign(T x, T y) { return y >= T(0) ? fabs(x) : -fabs(x); } // SIGN :12-16
+template <class T> __device__ __forceinline__ T gs_max(T x, T y) { return y > x ? y : x; } // max(x, y) as Python and Cython spell it: x unless y > x
+template <class T> __device__ __forceinline__ T gs_min(T x, T y) { return y < x ? y : x; }
+
+template <class T> __device__ __forceinline__ int gs_van_leer(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, int niter, T tol, T &ps, T &us)
+{ // :54-151
+    if (rhol < T(0) || rhor < T(0) || pl < T(0) || pr < T(0)) { ps = T(0); us = T(0); return 1; }
+    const T gamma2 = T(1) + gamma, gamma1 = T(0.5) * gamma2 / gamma, smallp = T(1e-25);
+    T wl = T(0), wr = T(0), zl, zr, ustar_l, ustar_r;
+    const T Vl = T(1) / rhol, Vr = T(1) / rhor;
+    const T cl = sqrt(gamma * pl * rhol), cr = sqrt(gamma * pr * rhor);
+    T pstar = pr - pl - cr * (ur - ul);
+    pstar = pl + pstar * cl / (cl + cr);
+    pstar = gs_max(pstar, smallp);
+    for (int it = 0; it < niter; it++) {
+        const T pstar_old = pstar;
+        wl = T(1) + gamma1 * (pstar - pl) / pl;
+        wl = cl * sqrt(wl);
+        wr = T(1) + gamma1 * (pstar - pr) / pr;
+        wr = cr * sqrt(wr);
+        zl = T(4) * Vl * wl * wl;
+        zl = -zl * wl / (zl - gamma2 * (pstar - pl));
+        zr = T(4) * Vr * wr * wr;
+        zr = zr * wr / (zr - gamma2 * (pstar - pr));
+        ustar_l = ul - (pstar - pl) / wl;
+        ustar_r = ur + (pstar - pr) / wr;
+        pstar = pstar + (ustar_r - ustar_l) * (zl * zr) / (zr - zl);
+        pstar = gs_max(smallp, pstar);
+        if (fabs(pstar - pstar_old) / pstar < tol) break;
+    }
+    ustar_l = ul - (pstar - pl) / wl;
+    ustar_r = ur + (pstar - pr) / wr;
+    ps = pstar;
+    us = T(0.5) * (ustar_l + ustar_r);
+    return 0; // (not converged: the reference returns 1 but has written its result)
+}
+
+template <class T> __device__ __forceinline__ void gs_prefun(T p, T dk, T pk, T ck, T g1, T g2, T g4, T g5, T g6, T &f, T &fd)
+{ // :154-173
+    if (p <= pk) {
+        const T pratio = p / pk;
+        f = g4 * ck * (gs_pow(pratio, g1) - T(1));
+        fd = (T(1) / (dk * ck)) * gs_pow(pratio, -g2);
+    } else {
+        const T ak = g5 / dk, bk = g6 * pk;
+        const T qrt = sqrt(ak / (bk + p));
+        f = (p - pk) * qrt;
+        fd = (T(1) - T(0.5) * (p - pk) / (bk + p)) * qrt;
+    }
+}
+
+template <class T> __device__ __forceinline__ int gs_exact(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, int niter, T tol, T &ps, T &us)
+{ // :176-286
+    const T tmp1 = T(1) / (T(2) * gamma), tmp2 = T(1) / (gamma - T(1)), tmp3 = T(1) / (gamma + T(1));
+    const T gamma1 = (gamma - T(1)) * tmp1, gamma2 = (gamma + T(1)) * tmp1, gamma3 = T(2) * gamma * tmp2, gamma4 = T(2) * tmp2,
+            gamma5 = T(2) * tmp3, gamma6 = tmp3 / tmp2, gamma7 = T(0.5) * (gamma - T(1));
+    const T cl = sqrt(gamma * pl / rhol), cr = sqrt(gamma * pr / rhor);
+    if (gamma4 * (cl + cr) <= (ur - ul)) return 1; // vacuum
+    const T cup = T(0.25) * (rhol + rhor) * (cl + cr);
+    T ppv = T(0.5) * (pl + pr) + T(0.5) * (ul - ur) * cup;
+    const T pmin = gs_min(pl, pr), pmax = gs_max(pl, pr), qmax = pmax / pmin;
+    ppv = gs_max(T(0), ppv);
+    T pm;
+    if (qmax <= T(2) && pmin <= ppv && ppv <= pmax) {
+        pm = ppv;
+    } else if (ppv < pmin) {
+        const T pq = gs_pow(pl / pr, gamma1);
+        const T um = (pq * ul / cl + ur / cr + gamma4 * (pq - T(1))) / (pq / cl + T(1) / cr);
+        const T ptl = T(1) + gamma7 * (ul - um) / cl, ptr = T(1) + gamma7 * (um - ur) / cr;
+        pm = T(0.5) * (pl * gs_pow(ptl, gamma3) + pr * gs_pow(ptr, gamma3));
+    } else {
+        const T gel = sqrt((gamma5 / rhol) / (gamma6 * pl + ppv)), ger = sqrt((gamma5 / rhor) / (gamma6 * pr + ppv));
+        pm = (gel * pl + ger * pr - (ur - ul)) / (gel + ger);
+    }
+    T pold = pm, p = T(0), fl = T(0), fld = T(0), fr = T(0), frd = T(0);
+    const T udiff = ur - ul;
+    int last = 0; // the reference's loop index after the loop
+    for (int i = 0; i < niter; i++) {
+        last = i;
+        gs_prefun(pold, rhol, pl, cl, gamma1, gamma2, gamma4, gamma5, gamma6, fl, fld);
+        gs_prefun(pold, rhor, pr, cr, gamma1, gamma2, gamma4, gamma5, gamma6, fr, frd);
+        p = pold - (fl + fr + udiff) / (fld + frd);
+        const T change = T(2) * fabs((p - pold) / (p + pold));
+        if (change <= tol) break;
+        pold = p;
+    }
+    if (last == niter - 1) return 1; // (also when it converged in the last iteration allowed: kept)
+    ps = p;
+    us = T(0.5) * (ul + ur + fr - fl);
+    return 0;
+}
+
+template <class T> __device__ __forceinline__ int gs_ducowicz(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, T &ps, T &us)
+{ // :431-525
+    const T al = T(0.5) * (gamma + T(1)), ar = al;
+    const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
+    const T umin = ur - T(0.5) * csr / ar, umax = ul + T(0.5) * csl / al;
+    const T plmin = pl - T(0.25) * rhol * csl * csl / al, prmin = pr - T(0.25) * rhor * csr * csr / ar;
+    const T bl = rhol * al, br = rhor * ar;
+    T a = (br - bl) * (prmin - plmin), b = br * umin * umin - bl * umax * umax, c = br * umin - bl * umax;
+    const T d = br * bl * (umin - umax) * (umin - umax);
+    auto pstar_of = [&](T ustar) {
+        const T v = T(0.5) * (plmin + prmin + br * fabs(ustar - umin) * (ustar - umin) - bl * fabs(ustar - umax) * (ustar - umax));
+        return gs_max(v, T(0));
+    };
+    T dd = sqrt(gs_max(T(0), d - a));
+    T ustar = (b + prmin - plmin) / (c - gs_sign(dd, umax - umin));
+    if ((ustar - umin) >= T(0) && (ustar - umax) <= T(0)) { ps = pstar_of(ustar); us = ustar; return 0; } // case A
+    dd = sqrt(gs_max(T(0), d + a));
+    ustar = (b - prmin + plmin) / (c - gs_sign(dd, umax - umin));
+    if ((ustar - umin) <= T(0) && (ustar - umax) >= T(0)) { ps = pstar_of(ustar); us = ustar; return 0; } // case B
+    a = (bl + br) * (plmin - prmin);
+    b = bl * umax + br * umin;
+    c = T(1) / (bl + br);
+    dd = sqrt(gs_max(T(0), a - d));
+    ustar = (b + dd) * c;
+    if ((ustar - umin) >= T(0) && (ustar - umax) >= T(0)) { ps = pstar_of(ustar); us = ustar; return 0; } // case C
+    dd = sqrt(gs_max(T(0), -a - d));
+    ustar = (b - dd) * c; // case D
+    ps = pstar_of(ustar);
+    us = ustar;
+    return 0;
+}
+
+template <class T> __device__ __forceinline__ int gs_hllc(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, T &ps, T &us)
+{ // :622-717
+    const T gamma1 = T(1) / (gamma - T(1));
+    const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
+    const T ulr = (rrhol * ul + rrhor * ur) / (rrhol + rrhor);
+    const T vl = ul - ulr, vr = ur - ulr;
+    const T csl = sqrt(gamma * pl / rhol), csr = sqrt(gamma * pr / rhor);
+    const T cslr = (rrhol * csl + rrhor * csr) / (rrhol + rrhor);
+    const T sl = gs_min(vl - csl, T(0) - cslr), sr = gs_max(vr + csr, T(0) + cslr);
+    T sm = rhor * vr * (sr - vr) - rhol * vl * (sl - vl) + pl - pr;
+    sm /= (rhor * (sr - vr) - rhol * (sl - vl));
+    const T phat = rhol * (vl - sl) * (vl - sm) + pl;
+    const T el = pl * gamma1 / rhol, El = rhol * (el + T(0.5) * ul * ul);
+    const T er = pr * gamma1 / rhor, Er = rhor * (er + T(0.5) * ur * ur);
+    const T Ml = rhol * ul, Mr = rhor * ur;
+    T pstar, ustar;
+    if (sl > T(0)) {
+        pstar = pl; ustar = ul;
+    } else if (sl <= T(0) && T(0) < sm) {
+        const T mstar = T(1) / (sl - sm) * ((sl - vl) * Ml + (phat - pl));
+        const T estar = T(1) / (sl - sm) * ((sl - vl) * El - pl * vl + phat * sm);
+        pstar = sm * mstar + phat;
+        ustar = sm * estar + (sm + ulr) * phat;
+        ustar /= pstar;
+    } else if (sm <= T(0) && T(0) < sr) {
+        const T mstar = T(1) / (sr - sm) * ((sr - vr) * Mr + (phat - pr));
+        const T estar = T(1) / (sr - sm) * ((sr - vr) * Er - pr * vr + phat * sm);
+        pstar = sm * mstar + phat;
+        ustar = sm * estar + (sm + ulr) * phat;
+        ustar /= pstar;
+    } else if (sr < T(0)) {
+        pstar = pr; ustar = ur;
+    } else {
+        return 1; // "Incorrect wave speeds" (a NaN among them)
+    }
+    ps = pstar; us = ustar;
+    return 0;
+}
+
+// riemann_solve (:19-44): `method` is a launch parameter, uniform over the wavefront
+template <class T> __device__ __forceinline__ int gs_riemann(int method, T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, int niter, T tol, T &ps, T &us)
+{
+    switch (method) {
+    case 0: ps = T(0.5) * (pl + pr); us = T(0.5) * (ul + ur); return 0; // non_diffusive :47-51
+    case 1: return gs_van_leer(rhol, rhor, pl, pr, ul, ur, gamma, niter, tol, ps, us);
+    case 2: return gs_exact(rhol, rhor, pl, pr, ul, ur, gamma, niter, tol, ps, us);
+    case 3: return gs_hllc(rhol, rhor, pl, pr, ul, ur, gamma, ps, us);
+    case 4: return gs_ducowicz(rhol, rhor, pl, pr, ul, ur, gamma, ps, us);
+    case 5: { // hlle :788-851
+        const T gamma1 = T(1) / (gamma - T(1));
+        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
+        const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
+        const T cslr = (rrhol * csl + rrhor * csr) / (rrhol + rrhor);
+        const T sl = gs_min(ul - csl, -cslr), sr = gs_max(ur + csr, +cslr);
+        const T smax = gs_max(sl, sr), smin = gs_min(sl, sr);
+        const T El = pl * gamma1 / rhol + T(0.5) * ul * ul, Er = pr * gamma1 / rhor + T(0.5) * ur * ur;
+        const T pstar = (smax * pl - smin * pr) / (smax - smin) + smax * smin / (smax - smin) * (ur - ul);
+        const T ustar = (smax * pl * ul - smin * pr * ur) / (smax - smin) + smax * smin / (smax - smin) * (Er - El);
+        ps = pstar; us = ustar / pstar;
+        return 0;
+    }
+    case 6: { // roe :528-572
+        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
+        const T denominator = T(1) / (rrhor + rrhol);
+        const T plr = (rrhol * pl + rrhor * pr) * denominator;
+        const T vlr = (rrhol / rhol + rrhor / rhor) * denominator;
+        const T ulr = (rrhol * ul + rrhor * ur) * denominator;
+        const T cslr = sqrt(gamma * plr / vlr), cslr1 = T(1) / cslr;
+        ps = plr - T(0.5) * (ur - ul) * cslr;
+        us = ulr - T(0.5) * (pr - pl) * cslr1;
+        return 0;
+    }
+    case 7: { // llxf :575-619
+        const T gamma1 = T(1) / (gamma - T(1));
+        const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
+        const T cslr = gs_max(csr, csl);
+        const T El = pl * gamma1 / rhol + T(0.5) * ul * ul, Er = pr * gamma1 / rhor + T(0.5) * ur * ur;
+        const T pstar = T(0.5) * (pl + pr - cslr * (ur - ul));
+        ps = pstar;
+        us = T(1) / pstar * (T(0.5) * ((pl * ul + pr * ur) - cslr * (Er - El)));
+        return 0;
+    }
+    case 8: { // hllc_ball :720-785
+        const T gamma1 = T(0.5) * (gamma + T(1)) / gamma;
+        const T csl = sqrt(gamma * pl / rhol), csr = sqrt(gamma * pr / rhor), cslr = T(0.5) * (csl + csr);
+        const T rholr = T(0.5) * (rhol + rhor);
+        T pstar = T(0.5) * (pl + pr - rholr * cslr * (ur - ul));
+        const T ustar = T(0.5) * (ul + ur - T(1) / (rholr * cslr) * (pr - pl));
+        const T Hl = pstar / pl, Hr = pstar / pr;
+        T ql = T(1), qr = T(1);
+        if (Hl > T(1)) ql = sqrt(T(1) + gamma1 * (Hl - T(1)));
+        if (Hr > T(1)) qr = sqrt(T(1) + gamma1 * (Hr - T(1)));
+        const T Sl = ul - csl * ql, Sr = ur + csr * qr;
+        const T pstar_l = pl + rhol * (ul - Sl) * (ul - ustar), pstar_r = pr + rhor * (ur - Sr) * (ur - ustar);
+        ps = T(0.5) * (pstar_l + pstar_r);
+        us = ustar;
+        return 0;
+    }
+    case 9: { // hll_ball :854-913
+        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
+        const T denominator = T(1) / (rrhor + rrhol);
+        const T csl = sqrt(gamma * pl / rhol), csr = sqrt(gamma * pr / rhor);
+        const T eta = T(0.5) * (gamma - T(1)) * (rrhor * rrhol) * denominator * denominator;
+        const T betal = fabs(ul), betar = fabs(ur);
+        const T ulr = (rrhol * ul + rrhor * ur) / (rrhol * rrhor);
+        const T cslr2 = (rrhol * csl * csl + rrhor * csr * csr) / (rrhol * rrhor);
+        const T cslr = sqrt(cslr2 + eta * (betar - betal) * (betar - betal));
+        const T Sl = gs_min(ulr - cslr, ul - csl), Sr = gs_max(ulr + cslr, ur + csr);
+        const T ustar = (Sr * Sl * (rhor - rhol) + rhol * ul * Sr - rhor * ur * Sl) / (rhol * (ul - Sl) + rhor * (Sr - ur));
+        T pstar = pr * (ustar - Sl) - pl * (ustar - Sr) + rhor * ur * (ustar - Sl) * (ur - Sr) - rhol * ul * (ustar - Sr) * (ul - Sl);
+        ps = pstar / (Sr - Sl);
+        us = ustar;
+        return 0;
+    }
+    case 10: { // hllsy :916-972
+        const T gamma1 = T(1) / (gamma - T(1));
+        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
+        const T denominator = T(1) / (rrhor + rrhol);
+        const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
+        const T cslr = denominator * (rrhol * csl + rrhor * csr);
+        const T bl = gs_max(csl, cslr), br = gs_max(csr, cslr);
+        const T wl = br / (bl + br), wr = bl / (bl + br), wlr = bl * br / (bl + br);
+        const T El = pl * gamma1 / rhol + T(0.5) * ul * ul, Er = pr * gamma1 / rhor + T(0.5) * ur * ur;
+        const T pstar = wl * pl + wr * pr - wlr * (ur - ul);
+        const T ustar = wl * (pl * ul) + wr * (pr * ur) - wlr * (Er - El);
+        ps = pstar; us = ustar / pstar;
+        return 0;
+    }
+    default: return 0; // (riemann_solve falls through: the result stays as it was)
+    }
+}
+
+template <class T> __device__ __forceinline__ T gs_sgn(T x) { return T((x > T(0)) - (x < T(0))); }
+template <class T> __device__ __forceinline__ T gs_monotonicity_min(T _x1, T _x2, T _x3)
+{ // gsph.py:34-58
+    const T x1 = T(2) * fabs(_x1), x2 = fabs(_x2), x3 = T(2) * fabs(_x3);
+    const T sx1 = gs_sgn(_x1), sx2 = gs_sgn(_x2), sx3 = gs_sgn(_x3);
+    if (sx1 != sx2 || sx2 != sx3) return T(0);
+    T m;
+    if (x2 < x1) m = x3 < x2 ? x3 : x2;
+    else m = x3 < x1 ? x3 : x1;
+    return sx1 * m;
+}
+
+// GSPHAcceleration (:148-541): the whole loop in one sweep -- local frame, specific-volume interpolation, monotonicity
+// limiter, left and right states with their fallbacks, the Riemann solve (and the second one of `hybrid`), au av aw ae with
+// DWI and DWJ each at its own h, the ADKE conduction with DWIJ.  Solver, limiter, interpolation, hybrid and conduction are
+// launch parameters: branches on them are uniform over the wavefront.  A pair whose solve fails contributes with the zero
+// pair and adds one to a device word.  Not PRED: the body is long and, for two solvers, iterates; lanes without a hit wait.
+// Records [x y z h | u v w rho p cs m e div grhox grhoy grhoz px py pz ux uy+vx uz+wx vy vz+wy wz -]: a velocity gradient is
+// read through eij . G . eij only, so its six symmetric sums are formed once at packing (k_pack, derived 6).
+enum { F_GSPH = 1 };
+template <class T> struct FamGSPH_T {
+    typedef T Real;
+    static constexpr bool PRED = false;
+    static constexpr uint32_t CF0 = F_GSPH;
+    static constexpr int MINB = 2;
+    static constexpr int NA = 21;
+    static constexpr int NR = 26;
+    struct Params {
+        T g1, g2, gamma, tol, blend; // blend = exp(-blend_alpha t / tf), computed by the host once per launch
+        int monotonicity, rsolver, interpolation, interface_zero, hybrid, niter, conduction;
+        double *au, *av, *aw, *ae;
+        unsigned long long *fail;
+    };
+    struct Dest {
+        T u, v, w, rho, p, cs, e, div, gr[3], gp[3], gv[6];
+        T au, av, aw, ae;
+    };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[3]; D.p = a[4]; D.cs = a[5]; D.e = a[7]; D.div = a[8];
+        for (int k = 0; k < 3; k++) { D.gr[k] = a[9 + k]; D.gp[k] = a[12 + k]; }
+        for (int k = 0; k < 6; k++) D.gv[k] = a[15 + k];
+        D.au = D.av = D.aw = D.ae = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        if (!pass) return;
+        PairGeomT<T> g, gi, gj;
+        pair_geom<KK, UH>(g, pi, pj, r2, a);
+        pair_geom_at<KK, UH>(gi, g, pi.w, a);
+        pair_geom_at<KK, UH>(gj, g, pj.w, a);
+        const T ti = pair_gradfac<KK, UH>(gi), tj = pair_gradfac<KK, UH>(gj); // DWI = ti XIJ, DWJ = tj XIJ
+        const T hi = pi.w, hj = pj.w, RIJ = g.rij, dt = (T)a.dt;
+        T e0 = T(0), e1 = T(0), e2 = T(0), sij; // :237-247
+        if (RIJ < T(1e-14)) {
+            sij = T(1) / (RIJ + g.eps);
+        } else {
+            sij = T(1) / RIJ;
+            e0 = g.xij[0] * sij; e1 = g.xij[1] * sij; e2 = g.xij[2] * sij;
+        }
+        const T vl = s[0] * e0 + s[1] * e1 + s[2] * e2;
+        const T vr = D.u * e0 + D.v * e1 + D.w * e2;
+        const T csi = D.cs, csj = s[5], rhoi = D.rho, rhoj = s[3], p_i = D.p, p_j = s[4];
+        // gradients in the local coordinate system (:254-284)
+        T rsi = D.gr[0] * e0 + D.gr[1] * e1 + D.gr[2] * e2;
+        T rsj = s[9] * e0 + s[10] * e1 + s[11] * e2;
+        T psi = D.gp[0] * e0 + D.gp[1] * e1 + D.gp[2] * e2;
+        T psj = s[12] * e0 + s[13] * e1 + s[14] * e2;
+        T vsi = e0 * e0 * D.gv[0] + e0 * e1 * D.gv[1] + e0 * e2 * D.gv[2] + e1 * e1 * D.gv[3] + e1 * e2 * D.gv[4] + e2 * e2 * D.gv[5];
+        T vsj = e0 * e0 * s[15] + e0 * e1 * s[16] + e0 * e2 * s[17] + e1 * e1 * s[18] + e1 * e2 * s[19] + e2 * e2 * s[20];
+        // interpolate (:429-541) with sij = RIJ, gri_eij = rsi, grj_eij = rsj
+        T vij_i, vij_j, sstar = T(0);
+        {
+            const T Vi = T(1) / rhoi, Vj = T(1) / rhoj;
+            const T hij = T(0.5) * (hi + hj);
+            if (a.p.interpolation == 0) {
+                vij_i = T(1) / (rhoi * rhoi);
+                vij_j = T(1) / (rhoj * rhoj);
+            } else if (a.p.interpolation == 1) {
+                const T cij = RIJ < T(1e-8) ? T(0) : (Vi - Vj) / RIJ;
+                const T dij = T(0.5) * (Vi + Vj);
+                vij_i = T(0.25) * hi * hi * cij * cij + dij * dij;
+                vij_j = T(0.25) * hj * hj * cij * cij + dij * dij;
+                if (!a.p.interface_zero) {
+                    const T vij = T(0.5) * (vij_i + vij_j);
+                    sstar = T(0.5) * hij * hij * cij * dij / vij;
+                }
+            } else {
+                const T Vip = T(-1) / (rhoi * rhoi) * rsi, Vjp = T(-1) / (rhoj * rhoj) * rsj;
+                T aij = T(0), bij = T(0), cij = T(0), dij = T(0.5) * (Vi + Vj);
+                if (!(RIJ < T(1e-8))) {
+                    aij = T(-2) * (Vi - Vj) / (RIJ * RIJ * RIJ) + (Vip + Vjp) / (RIJ * RIJ);
+                    bij = T(0.5) * (Vip - Vjp) / RIJ;
+                    cij = T(1.5) * (Vi - Vj) / RIJ - T(0.25) * (Vip + Vjp);
+                    dij = T(0.5) * (Vi + Vj) - T(0.125) * (Vip - Vjp) * RIJ;
+                }
+                const T hi2 = hi * hi, hj2 = hj * hj, hi4 = hi2 * hi2, hj4 = hj2 * hj2, hi6 = hi4 * hi2, hj6 = hj4 * hj2;
+                vij_i = T(15.0 / 64.0) * hi6 * aij * aij + T(3.0 / 16.0) * hi4 * (T(2) * aij * cij + bij * bij) +
+                        T(0.25) * hi2 * (T(2) * bij * dij + cij * cij) + dij * dij;
+                vij_j = T(15.0 / 64.0) * hj6 * aij * aij + T(3.0 / 16.0) * hj4 * (T(2) * aij * cij + bij * bij) +
+                        T(0.25) * hj2 * (T(2) * bij * dij + cij * cij) + dij * dij;
+                if (!a.p.interface_zero) {
+                    const T hij2 = hij * hij, hij4 = hij2 * hij2;
+                    const T vij = T(0.5) * (vij_i + vij_j);
+                    sstar = (T(15.0 / 32.0) * hij4 * hij2 * aij * bij + T(3.0 / 8.0) * hij4 * (aij * dij + bij * cij) +
+                             T(0.5) * hij2 * cij * dij) / vij;
+                }
+            }
+        }
+        // monotonicity (:293-349)
+        if (a.p.monotonicity == 0) {
+            rsi = rsj = psi = psj = vsi = vsj = T(0);
+        } else if (a.p.monotonicity == 1) {
+            if (vsi * vsj < T(0)) { vsi = T(0); vsj = T(0); }
+            if (gs_min(csi, csj) < T(3) * (vl - vr)) rsi = rsj = psi = psj = vsi = vsj = T(0); // first order near a shock
+        } else if (a.p.monotonicity == 2) {
+            if (RIJ > T(1e-14)) {
+                const T qijr = rhoi - rhoj, qijp = p_i - p_j, qiju = vr - vl;
+                T delr = rsi * RIJ, delp = psi * RIJ, delv = vsi * RIJ;
+                rsi = gs_monotonicity_min(qijr, delr, T(2) * delr - qijr) / RIJ;
+                psi = gs_monotonicity_min(qijp, delp, T(2) * delp - qijp) / RIJ;
+                vsi = gs_monotonicity_min(qiju, delv, T(2) * delv - qiju) / RIJ;
+                delr = rsj * RIJ; delp = psj * RIJ; delv = vsj * RIJ;
+                rsj = gs_monotonicity_min(qijr, delr, T(2) * delr - qijr) / RIJ;
+                psj = gs_monotonicity_min(qijp, delp, T(2) * delp - qijp) / RIJ;
+                vsj = gs_monotonicity_min(qiju, delv, T(2) * delv - qiju) / RIJ;
+            } else if (RIJ < T(1e-14)) {
+                rsi = rsj = psi = psj = vsi = vsj = T(0);
+            }
+        }
+        // the states either side of the interface (:351-376)
+        sstar *= T(2);
+        const T fj = T(1) - csj * dt * sij + sstar, fi = T(1) - csi * dt * sij + sstar;
+        T rhol = rhoj + T(0.5) * rsj * RIJ * fj;
+        T rhor = rhoi - T(0.5) * rsi * RIJ * fi;
+        if (rhol < T(0)) rhol = rhoj;
+        if (rhor < T(0)) rhor = rhoi;
+        T pl = p_j + T(0.5) * psj * RIJ * fj;
+        T pr = p_i - T(0.5) * psi * RIJ * fi;
+        if (pl < T(0)) pl = p_j;
+        if (pr < T(0)) pr = p_i;
+        const T ul = vl + T(0.5) * vsj * RIJ * fj;
+        const T ur = vr - T(0.5) * vsi * RIJ * fi;
+        T pstar = T(0), ustar = T(0);
+        int failed = gs_riemann(a.p.rsolver, rhol, rhor, pl, pr, ul, ur, a.p.gamma, a.p.niter, a.p.tol, pstar, ustar);
+        if (a.p.hybrid) { // :388-396: the second solve writes into the result of the first
+            T pstar2 = pstar, ustar2 = ustar;
+            failed += gs_riemann(10, rhoj, rhoi, pl, pr, vl, vr, a.p.gamma, a.p.niter, a.p.tol, pstar2, ustar2);
+            ustar = ustar + a.p.blend * (ustar2 - ustar);
+            pstar = pstar + a.p.blend * (pstar2 - pstar);
+        }
+        if (failed) atomicAdd(a.p.fail, 1ull);
+        // :398-416
+        const T mj = s[6];
+        const T ci = vij_i * ti, cj = vij_j * tj;
+        const T f = -mj * pstar * (ci + cj);
+        D.au += f * g.xij[0]; D.av += f * g.xij[1]; D.aw += f * g.xij[2];
+        const T edotx = e0 * g.xij[0] + e1 * g.xij[1] + e2 * g.xij[2];
+        D.ae += f * (ustar * edotx);
+        if (a.p.conduction) { // :418-427
+            const T divi = D.div, divj = s[8];
+            const T Hi = a.p.g1 * hi * csi + a.p.g2 * hi * hi * (fabs(divi) - divi);
+            const T Hj = a.p.g1 * hj * csj + a.p.g2 * hj * hj * (fabs(divj) - divj);
+            T Hij = (Hi + Hj) * (D.e - s[7]);
+            Hij /= (T(0.5) * (rhoi + rhoj) * (RIJ * RIJ + g.eps));
+            const T tij = pair_gradfac<KK, UH>(g);
+            D.ae += mj * Hij * (tij * (g.xij[0] * g.xij[0] + g.xij[1] * g.xij[1] + g.xij[2] * g.xij[2]));
+        }
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        a.p.au[o] = (double)D.au; a.p.av[o] = (double)D.av; a.p.aw[o] = (double)D.aw; a.p.ae[o] = (double)D.ae;
+    }
+};
+
 // ---- velocity gradient (basic_equations.py:63-148) -------------------------
 template <class T> struct FamVGrad_T {
     typedef T Real; // arithmetic type of the pair loop
@@ -2007,7 +2507,8 @@ static bool is_nosrc_kind(int k)
     return k == SPH_EQ_TAIT_EOS || k == SPH_EQ_TAIT_EOS_HG || k == SPH_EQ_TVF_STATE_EQUATION ||
            k == SPH_EQ_ISOTHERMAL_EOS || k == SPH_EQ_SOLID_ISOTHERMAL_EOS || k == SPH_EQ_MONAGHAN_ART_STRESS ||
            k == SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE || k == SPH_EQ_UPDATE_H_FERRARI || k == SPH_EQ_IDEAL_GAS_EOS ||
-           k == SPH_EQ_SCALE_SMOOTHING_LENGTH || k == SPH_EQ_UPDATE_H_FROM_VOLUME || k == SPH_EQ_MPM_UPDATE_GHOST_PROPS;
+           k == SPH_EQ_SCALE_SMOOTHING_LENGTH || k == SPH_EQ_UPDATE_H_FROM_VOLUME || k == SPH_EQ_MPM_UPDATE_GHOST_PROPS ||
+           k == SPH_EQ_GSPH_UPDATE_GHOST_PROPS;
 }
 
 static int need_prop(sph_ctx *c, int id, int prop, const char *who)
@@ -2026,6 +2527,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     EosArgs a;
     a.kind = e.kind;
     memcpy(a.par, e.par, sizeof a.par);
+    for (int &gc : a.gcol) gc = 0;
     const bool writes_h = e.kind == SPH_EQ_UPDATE_H_FERRARI || e.kind == SPH_EQ_SCALE_SMOOTHING_LENGTH || e.kind == SPH_EQ_UPDATE_H_FROM_VOLUME;
     if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS) {
         const int po = sph_prop_register("orig_idx");
@@ -2033,6 +2535,19 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
         SPH_TRY(need_prop(c, e.dest, po, "MPMUpdateGhostProps (orig_idx)"));
         SPH_TRY(need_prop(c, e.dest, SPH_P, "MPMUpdateGhostProps (p)"));
         SPH_TRY(need_prop(c, e.dest, SPH_CS, "MPMUpdateGhostProps (cs)"));
+        a.par[0] = (double)A.n_real;
+        a.par[1] = (double)po;
+        if (start < A.n_real) start = A.n_real; // nothing to do on the real rows
+        if (stop <= start) return SPH_OK;
+    } else if (e.kind == SPH_EQ_GSPH_UPDATE_GHOST_PROPS) {
+        static const char *names[17] = {"px", "py", "pz", "ux", "uy", "uz", "vx", "vy", "vz", "wx", "wy", "wz",
+                                        "grhox", "grhoy", "grhoz", "dwdh", "div"};
+        const int po = sph_prop_register("orig_idx");
+        if (po < 0) return po;
+        SPH_TRY(need_prop(c, e.dest, po, "GSPHUpdateGhostProps (orig_idx)"));
+        for (int k = 0; k < 17; k++) { a.gcol[k] = sph_prop_register(names[k]); if (a.gcol[k] < 0) return a.gcol[k]; }
+        a.gcol[17] = SPH_RHO; a.gcol[18] = SPH_P; a.gcol[19] = SPH_CS;
+        for (int k = 0; k < 20; k++) SPH_TRY(need_prop(c, e.dest, a.gcol[k], "GSPHUpdateGhostProps"));
         a.par[0] = (double)A.n_real;
         a.par[1] = (double)po;
         if (start < A.n_real) start = A.n_real; // nothing to do on the real rows
@@ -2088,7 +2603,8 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     return SPH_OK;
 }
 
-enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP, FAM_GASSD, FAM_MPM };
+enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP, FAM_GASSD, FAM_MPM,
+              FAM_GSPHGRAD, FAM_GSPH };
 
 static bool is_wcsph_option_kind(int k)
 {
@@ -2110,6 +2626,8 @@ static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false
     case SPH_EQ_EDAC_AVG_PRESSURE: *flag = F_AVGP; return FAM_AVGP;
     case SPH_EQ_GASD_SUMMATION_DENSITY: *flag = F_GSD; return FAM_GASSD;
     case SPH_EQ_MPM_ACCELERATIONS: *flag = F_MPM; return FAM_MPM;
+    case SPH_EQ_GSPH_GRADIENTS: *flag = F_GGRAD; return FAM_GSPHGRAD;
+    case SPH_EQ_GSPH_ACCELERATION: *flag = F_GSPH; return FAM_GSPH;
     default: break;
     }
     if (edac && !elastic) {
@@ -2218,6 +2736,20 @@ static PackPlan pack_plan(int fam)
         int pr[12] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_E, SPH_M, sph_prop_register("omega"),
                       sph_prop_register("alpha1"), sph_prop_register("alpha2"), -1};
         for (int k = 0; k < 12; k++) p.props[k] = pr[k];
+    } else if (fam == FAM_GSPHGRAD) { // [p u v w m/rho]
+        p.nr = 10;
+        p.na = 5;
+        int pr[6] = {SPH_P, SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO};
+        for (int k = 0; k < 6; k++) p.props[k] = pr[k];
+        p.derived = 7;
+    } else if (fam == FAM_GSPH) { // the gradients: user properties by name (run_gsph refuses the launch should the slots have run out)
+        p.nr = 26;
+        p.na = 21;
+        static const char *un[16] = {"div", "grhox", "grhoy", "grhoz", "px", "py", "pz", "ux", "uy", "uz", "vx", "vy", "vz", "wx", "wy", "wz"};
+        int pr[8] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_M, SPH_E};
+        for (int k = 0; k < 8; k++) p.props[k] = pr[k];
+        for (int k = 0; k < 16; k++) p.props[8 + k] = sph_prop_register(un[k]);
+        p.derived = 6;
     } else if (fam == FAM_NBR) {
         p.nr = FamNbr::NR;
         p.na = 1;
@@ -2318,7 +2850,7 @@ static bool slot_required(int fam, uint32_t flags, int prop)
         return true;
     }
     if (fam == FAM_AVGP) return prop == SPH_M ? (flags & (F_SD | F_TVFSD)) != 0 : (flags & F_AVGP) != 0;
-    if (fam == FAM_GASSD || fam == FAM_MPM) return true;
+    if (fam == FAM_GASSD || fam == FAM_MPM || fam == FAM_GSPHGRAD || fam == FAM_GSPH) return true;
     return false;
 }
 
@@ -2371,7 +2903,8 @@ static int pack_array(sph_ctx *c, int id, size_t off, const RecordLayout &rl, in
     pa.x = A.prop[SPH_X]; pa.y = A.prop[SPH_Y]; pa.z = A.prop[SPH_Z]; pa.h = A.prop[SPH_H];
     pa.na = pl.na;
     for (int k = 0; k < MAX_AUX; k++) {
-        if ((k < pl.na || (pl.derived == 3 && k == 18) || (pl.derived == 4 && k == 4)) && pl.props[k] >= 0) {
+        if ((k < pl.na || (pl.derived == 3 && k == 18) || (pl.derived == 4 && k == 4) || (pl.derived == 6 && k < 24) ||
+             (pl.derived == 7 && k == 5)) && pl.props[k] >= 0) {
             pa.src[k] = A.prop[pl.props[k]];
             // a destination that is not among the sources is only read through Fam::load:
             // it does not need a mass unless the equation uses the destination's own
@@ -2421,6 +2954,7 @@ static int pack_array(sph_ctx *c, int id, size_t off, const RecordLayout &rl, in
         pa.src[7] = nullptr; // p is computed, not read
     }
     pa.lds_np = pack_pieces(pa);
+    if ((size_t)pa.lds_np * 256 * 16 > 48 * 1024) pa.lds_np = 0; // the widest records (GSPH, 13 pieces) leave per lane
     if (launch) launch_pack(c, pa, nseg);
     return SPH_OK;
 }
@@ -3499,6 +4033,48 @@ template <class F> static int run_mpm(const PairLaunch &L)
     return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
 }
 
+template <class F> static int run_gsph_grad(const PairLaunch &L)
+{
+    PairArgs<F> a = pair_args<F>(L);
+    static const char *names[12] = {"px", "py", "pz", "ux", "uy", "uz", "vx", "vy", "vz", "wx", "wy", "wz"};
+    for (int k = 0; k < 12; k++) {
+        const int id = sph_prop_register(names[k]);
+        if (id < 0) return id;
+        SPH_TRY(bind_out(L, {{id, &a.p.g[k]}}));
+    }
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+// the GSPH force sweep; the failure word is cleared by the first such launch of a call (sph_gsph_failures reads it)
+template <class F> static int run_gsph(const PairLaunch &L)
+{
+    typedef typename F::Real T;
+    sph_ctx *c = L.c;
+    PairArgs<F> a = pair_args<F>(L);
+    // par g1 g2 monotonicity rsolver interpolation interface_zero hybrid blend_alpha tf gamma niter tol
+    const sph_equation *ge = L.P.eq_of[SPH_EQ_GSPH_ACCELERATION];
+    const double *par = ge->par;
+    a.p.g1 = (T)par[0]; a.p.g2 = (T)par[1];
+    a.p.monotonicity = (int)par[2]; a.p.rsolver = (int)par[3]; a.p.interpolation = (int)par[4];
+    a.p.interface_zero = par[5] != 0.0; a.p.hybrid = par[6] != 0.0;
+    a.p.blend = (T)exp(-par[7] * L.t / par[8]); // gsph.py:232, once per launch
+    a.p.gamma = (T)par[9]; a.p.niter = (int)par[10]; a.p.tol = (T)par[11];
+    a.p.conduction = !(par[0] == 0.0 && par[1] == 0.0);
+    if (a.p.rsolver < 0 || a.p.rsolver > 10 || a.p.monotonicity < 0 || a.p.monotonicity > 2 || a.p.interpolation < 0 || a.p.interpolation > 2) {
+        sph_set_error("GSPHAcceleration: rsolver %d (0..10), monotonicity %d (0..2) or interpolation %d (0..2) out of range",
+                      a.p.rsolver, a.p.monotonicity, a.p.interpolation);
+        return SPH_ERR_ARG;
+    }
+    for (int k = 8; k < 24; k++) if (L.rl.pl.props[k] < 0) { sph_set_error("GSPHAcceleration: no user property slot left for its gradient columns"); return SPH_ERR_ARG; }
+    SPH_TRY(bind_out(L, {{SPH_AU, &a.p.au}, {SPH_AV, &a.p.av}, {SPH_AW, &a.p.aw}, {SPH_AE, &a.p.ae}}));
+    SPH_TRY(c->gsph_word.reserve(64));
+    a.p.fail = c->gsph_word.as<unsigned long long>();
+    if (!c->gsph_cleared && !c->gsph_keep) {
+        HIP_TRY(hipMemsetAsync(a.p.fail, 0, sizeof(unsigned long long), c->stream));
+        c->gsph_cleared = true;
+    }
+    return launch_pair<F>(c, L.K->kind, a, L.rl.record_f32);
+}
+
 // the family instantiation the plan and the records name, in the arithmetic type of the records
 static int launch_family(const PairLaunch &L)
 {
@@ -3524,6 +4100,8 @@ static int launch_family(const PairLaunch &L)
     if (fam == FAM_AVGP) RUN(run_avgp, FamAvgP_T<T>);
     if (fam == FAM_GASSD) RUN(run_gassd, FamGasSD_T<T>);
     if (fam == FAM_MPM) RUN(run_mpm, FamMPM_T<T>);
+    if (fam == FAM_GSPHGRAD) RUN(run_gsph_grad, FamGSPHGrad_T<T>);
+    if (fam == FAM_GSPH) RUN(run_gsph, FamGSPH_T<T>);
     if (fam == FAM_EDAC && (L.P.dflags & F_EINT)) RUN(run_edac, FamEDAC_T<T, true>);
     if (fam == FAM_EDAC) RUN(run_edac, FamEDAC_T<T, false>);
     if (fam == FAM_VGRAD) RUN(run_vgrad, FamVGrad_T<T>);
@@ -3538,6 +4116,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
 {
     if (!c || !K || !g) { sph_set_error("sph_eval_group: NULL argument"); return SPH_ERR_ARG; }
     c->gasd_unconverged = 0;
+    c->gsph_cleared = false;
     if (g->neq > SPH_MAX_EQS) { sph_set_error("sph_eval_group: too many equations"); return SPH_ERR_ARG; }
     SPH_TRY(check_kernel("sph_eval_group", K));
     HIP_TRY(hipSetDevice(c->device));
@@ -3614,6 +4193,17 @@ extern "C" int sph_gasd_unconverged(sph_ctx *c, int *flag)
 {
     if (!c || !flag) { sph_set_error("sph_gasd_unconverged: NULL argument"); return SPH_ERR_ARG; }
     *flag = c->gasd_unconverged ? 1 : 0;
+    return SPH_OK;
+}
+
+extern "C" int sph_gsph_failures(sph_ctx *c, unsigned long long *count)
+{
+    if (!c || !count) { sph_set_error("sph_gsph_failures: NULL argument"); return SPH_ERR_ARG; }
+    *count = 0;
+    if (!c->gsph_word.ptr) return SPH_OK; // no GSPH force sweep has run
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(count, c->gsph_word.ptr, sizeof *count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SPH_OK;
 }
 
@@ -3974,6 +4564,8 @@ UNIT_BOTH(UNIT_PAIR, FamTVF_T);
 UNIT_BOTH(UNIT_PAIR, FamAvgP_T);
 UNIT_BOTH(UNIT_PAIR, FamGasSD_T);
 UNIT_BOTH(UNIT_PAIR, FamMPM_T);
+UNIT_BOTH(UNIT_PAIR, FamGSPHGrad_T);
+UNIT_BOTH(UNIT_PAIR, FamGSPH_T);
 template <class T> using FamEDACInt_T = FamEDAC_T<T, true>;
 template <class T> using FamEDACExt_T = FamEDAC_T<T, false>;
 UNIT_BOTH(UNIT_PAIR, FamEDACInt_T);

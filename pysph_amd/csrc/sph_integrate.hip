@@ -128,6 +128,20 @@ __global__ __launch_bounds__(256) void k_stage(StageArgs a)
             p[g[AL1]][i] = p[g[AL10]][i] + f * p[g[AAL1]][i];
             p[g[AL2]][i] = p[g[AL20]][i] + f * p[g[AAL2]][i];
         }
+    } else if (a.stepper == SPH_STEP_GSPH) {
+        if (a.stage == 1) { // integrator_step.py:433-449: one stage; the energy moves with the half-step velocities
+#pragma clang fp contract(off) // every product rounded on its own, as the reference's expressions are
+            const double au = p[SPH_AU][i], av = p[SPH_AV][i], aw = p[SPH_AW][i];
+            const double u = p[SPH_U][i], v = p[SPH_V][i], w = p[SPH_W][i];
+            const double ustar = u + dtb2 * au, vstar = v + dtb2 * av, wstar = w + dtb2 * aw;
+            p[SPH_U][i] = u + dt * au;
+            p[SPH_V][i] = v + dt * av;
+            p[SPH_W][i] = w + dt * aw;
+            p[SPH_E][i] = p[SPH_E][i] + dt * (p[SPH_AE][i] - ustar * au - vstar * av - wstar * aw);
+            p[SPH_X][i] = p[SPH_X][i] + dt * ustar;
+            p[SPH_Y][i] = p[SPH_Y][i] + dt * vstar;
+            p[SPH_Z][i] = p[SPH_Z][i] + dt * wstar;
+        }
     }
 }
 
@@ -168,8 +182,10 @@ extern "C" int sph_integrate_stage(sph_ctx *c, int id, int stepper, int stage, d
         memcpy(gd0, b0, sizeof b0);
         memcpy(gd1, b1, sizeof b1);
     }
+    static const int gs1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_E, SPH_AU, SPH_AV, SPH_AW, SPH_AE, -1};
     const int *need = nullptr;
     if (stepper == SPH_STEP_GASD) need = stage == 0 ? gd0 : gd1;
+    else if (stepper == SPH_STEP_GSPH) { if (stage != 1) return SPH_OK; need = gs1; }
     else if (stepper == SPH_STEP_EDAC) need = stage == 0 ? ed0 : ed1;
     else if (stepper == SPH_STEP_EDAC_TVF) need = stage == 0 ? ed0 : et1;
     else if (stepper == SPH_STEP_WCSPH) need = stage == 0 ? wc0 : wc1;

@@ -136,7 +136,7 @@ struct RigidState {
 // T_PAIR: every pair launch; T_PAIR_FAM + family (sph_eval.hip enum Family): the same launches per equation family
 // T_N_*: launch counters only (no time): pair launches on EOS-fused records, launches that kept / reused neighbour lists
 // T_N_INTERP_MOM / _SWEEP: moment passes / property sweeps of sph_interpolate
-enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 13, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_N_GASD_SKIP, T_N_PLACED, T_N_PLACE_OVF, T_COUNT };
+enum TimerKey { T_NNPS, T_PACK, T_EOS, T_PAIR, T_STAGE, T_PAIR_FAM, T_N_EOSF = T_PAIR_FAM + 15, T_N_NLKEEP, T_N_NLREUSE, T_N_UMASS, T_N_MERGED, T_N_TFLAG, T_N_PHASE2, T_N_ASYNC, T_N_DLIST, T_N_ROWLDS, T_N_INTERP_MOM, T_N_INTERP_SWEEP, T_N_EOSABS, T_N_GASD_SKIP, T_N_PLACED, T_N_PLACE_OVF, T_COUNT };
 
 struct Timer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -304,6 +304,9 @@ struct sph_ctx {
     long gasd_skip = 0;     // wavefronts of an iterating density sweep whose destinations have all converged skip their neighbour work
     long gasd_repeat = 0;   // ... the host says: this call repeats the previous one inside an iterated group (nothing else ran in between)
     uint32_t gasd_unconverged = 0; // the last sph_eval_group call: an iterating gas-dynamics density sweep left particles unconverged
+    DevBuf gsph_word;              // Riemann-solver failures of the GSPH force sweeps (one 64-bit counter; sph_gsph_failures reads it)
+    bool gsph_cleared = false;     // ... cleared by the first such sweep of the sph_eval_group call in progress
+    long gsph_keep = 0;            // ... unless the host says the call continues a group it gave in several calls (option gsph_keep)
     DevBuf csr_start[SPH_MAX_ARRAYS], csr_nbrs[SPH_MAX_ARRAYS]; // neighbour lists of generated loop_all families
     unsigned long long pack_epoch = 0;
     long pack_group = 0;    // 1 between the per-destination sph_eval_group calls of one host group (records shared)

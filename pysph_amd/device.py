@@ -137,6 +137,7 @@ SIGNATURES = {
     'sph_integrate_stage': (C.c_int, [_P, C.c_int, C.c_int, C.c_int,
                                       C.c_double]),
     'sph_gasd_unconverged': (C.c_int, [_P, C.POINTER(C.c_int)]),
+    'sph_gsph_failures': (C.c_int, [_P, C.POINTER(C.c_ulonglong)]),
     'sph_rigid_chunk': (C.c_int, []),
     'sph_rigid_setup': (C.c_int, [_P, C.c_int, C.c_int, _PU, _PU]),
     'sph_rigid_state_push': (C.c_int, [_P, C.c_int, C.c_int, _PD, C.c_size_t]),

@@ -314,8 +314,13 @@ EQ_MPM_ACCELERATIONS = 36
 EQ_SCALE_SMOOTHING_LENGTH = 37
 EQ_UPDATE_H_FROM_VOLUME = 38
 EQ_MPM_UPDATE_GHOST_PROPS = 39
+EQ_GSPH_GRADIENTS = 40
+EQ_GSPH_UPDATE_GHOST_PROPS = 41
+EQ_GSPH_ACCELERATION = 42
 
 _XV = ('x', 'y', 'z', 'h')
+_GSPH_GRADS = ('px', 'py', 'pz', 'ux', 'uy', 'uz', 'vx', 'vy', 'vz', 'wx', 'wy', 'wz')
+_GSPH_STATE = ('u', 'v', 'w', 'm', 'rho', 'p', 'cs', 'e', 'div', 'grhox', 'grhoy', 'grhoz') + _GSPH_GRADS
 EQUATION_TABLE = OrderedDict([
     # name: (kind, params, dest props, source props)
     ('TaitEOS', (EQ_TAIT_EOS, ('rho0', 'c0', 'gamma', 'p0'),
@@ -425,12 +430,22 @@ EQUATION_TABLE = OrderedDict([
     ('UpdateSmoothingLengthFromVolume', (EQ_UPDATE_H_FROM_VOLUME, ('k', 'dim1'), ('h', 'm', 'rho'), ())),
     # (the two parameters are the library's own: the real rows and the column of orig_idx)
     ('MPMUpdateGhostProps', (EQ_MPM_UPDATE_GHOST_PROPS, (), ('p', 'cs', 'orig_idx'), ())),
+    # Godunov SPH (pysph_amd/gas_dynamics.py, pysph/sph/gas_dynamics/gsph.py)
+    ('GSPHGradients', (
+        EQ_GSPH_GRADIENTS, (), _XV + ('p', 'u', 'v', 'w') + _GSPH_GRADS, _XV + ('p', 'u', 'v', 'w', 'm', 'rho'))),
+    ('GSPHUpdateGhostProps', (
+        EQ_GSPH_UPDATE_GHOST_PROPS, (),
+        _GSPH_GRADS + ('grhox', 'grhoy', 'grhoz', 'dwdh', 'rho', 'div', 'p', 'cs', 'orig_idx'), ())),
+    ('GSPHAcceleration', (
+        EQ_GSPH_ACCELERATION, ('g1', 'g2', 'monotonicity', 'rsolver', 'interpolation', 'interface_zero', 'hybrid',
+                               'blend_alpha', 'tf', 'gamma', 'niter', 'tol'),
+        _XV + _GSPH_STATE + ('au', 'av', 'aw', 'ae'), _XV + _GSPH_STATE)),
 ])
 
 # equations that have no neighbour loop
 NO_SOURCE_KINDS = (EQ_TAIT_EOS, EQ_TAIT_EOS_HG, EQ_TVF_STATE_EQUATION,
                    EQ_ISOTHERMAL_EOS, 17, 19, 21, EQ_UPDATE_H_FERRARI, EQ_IDEAL_GAS_EOS, EQ_SCALE_SMOOTHING_LENGTH,
-                   EQ_UPDATE_H_FROM_VOLUME, EQ_MPM_UPDATE_GHOST_PROPS)
+                   EQ_UPDATE_H_FROM_VOLUME, EQ_MPM_UPDATE_GHOST_PROPS, EQ_GSPH_UPDATE_GHOST_PROPS)
 
 
 def resolve_equation(eq):

@@ -21,11 +21,30 @@ Mirrors the interface of pysph/sph/gas_dynamics/basic.py and ``GasDScheme`` of p
 * ``GasDScheme`` gives the reference's group list for ``adaptive_h_scheme='mpm'`` and ``'gsph'``; ``solids`` are
   refused at construction (running the reference's ``WallBoundary`` through the translator was not attempted);
 * ``GasDFluidStep`` lives in ``pysph_amd.integrator``, ``get_particle_array_gasd`` in ``pysph_amd.particle_array``.
+
+Godunov SPH (pysph/sph/gas_dynamics/gsph.py, riemann_solver.py, ``GSPHScheme`` of scheme.py:1144-1458; DESIGN.md,
+section 7h):
+
+* ``GSPHGradients`` (gsph.py:61-101), ``GSPHUpdateGhostProps`` (:104-145) and ``GSPHAcceleration`` (:148-541) are
+  parameter holders too: ``FamGSPHGrad_T``, a case of ``k_nosrc`` and ``FamGSPH_T``.  The force sweep holds the eleven
+  Riemann solvers; which one runs, the limiter, the interpolation, ``hybrid`` and the conduction switch are launch
+  parameters.  A pair whose solve fails where the reference's returns 1 without a result enters with
+  ``pstar = ustar = 0`` and is counted: ``eq.solver_failures()`` of a ``GSPHAcceleration`` the evaluator has compiled
+  reads the count of the last evaluation from the device (nothing is read unless it is called);
+* the images of a periodic / mirror domain get what ``GSPHAcceleration`` reads from them -- the twelve gradients,
+  ``grhox..z``, ``dwdh``, ``rho``, ``div``, ``p``, ``cs`` -- from ``GSPHUpdateGhostProps``, the ghost kernel, right
+  before the force group (``has_ghosts=True``), not from the domain update.  The reference's list has that group only
+  behind ``GSPHGradients``, which then sums over images whose ``p`` and ``rho`` date from the last domain update; the
+  evaluator runs the ghost group in front of the gradient group as well, so that a periodic box equals its explicit
+  tiling -- a deliberate difference from the reference, for arrays with images only (the group list is the reference's);
+* ``GSPHScheme`` gives the reference's group list (including that it does not hand ``tf`` to ``GSPHAcceleration``);
+  ``configure_solver`` takes ``tf`` from its keywords as the reference's does.  ``GSPHStep`` lives in
+  ``pysph_amd.integrator``.
 """
 import numpy as np
 
 from .equations import Equation, Group
-from .integrator import GasDFluidStep, PECIntegrator
+from .integrator import EulerIntegrator, GasDFluidStep, GSPHStep, PECIntegrator
 from .particle_array import GASD_PROPS, get_npy, get_particle_array_gasd  # noqa: F401
 
 
@@ -206,6 +225,185 @@ class GasDScheme(object):
         for fluid in self.fluids:
             pa = arrays[fluid]
             for p in GASD_PROPS:
+                if p not in pa.properties:
+                    pa.add_property(p)
+            if 'orig_idx' not in pa.properties:
+                pa.add_property('orig_idx', type='int')
+            get_npy(pa, 'orig_idx')[:] = np.arange(pa.get_number_of_particles())
+            pa.set_output_arrays(['x', 'y', 'u', 'v', 'rho', 'm', 'h', 'cs', 'p', 'e', 'au', 'av', 'ae', 'pid', 'gid',
+                                  'tag', 'dwdh', 'alpha1', 'alpha2'])
+
+
+# Riemann solver types, interpolation types (gsph.py:11-27)
+NonDiffusive, VanLeer, Exact, HLLC, Ducowicz, HLLE, Roe, LLXF, HLLCBall, HLLBall, HLLSY = range(11)
+Delta, Linear, Cubic = range(3)
+GSPH_GRADIENT_PROPS = ('px', 'py', 'pz', 'ux', 'uy', 'uz', 'vx', 'vy', 'vz', 'wx', 'wy', 'wz')
+
+
+class GSPHGradients(Equation):
+    """gsph.py:61-101: the gradients of ``p, u, v, w`` with ``DWI``: twelve sums, one sweep."""
+
+
+class GSPHUpdateGhostProps(Equation):
+    """gsph.py:104-145: the twenty columns ``GSPHAcceleration`` reads from an image row, from the row it mirrors
+    (``orig_idx``)."""
+
+    def __init__(self, dest, sources=None):
+        super(GSPHUpdateGhostProps, self).__init__(dest, sources)
+
+
+class GSPHAcceleration(Equation):
+    """gsph.py:148-541: Inutsuka's GSPH accelerations with the monotonicity constraints of I02 / IwIn, the
+    specific-volume interpolations and the Riemann solvers of riemann_solver.py."""
+
+    def __init__(self, dest, sources, g1=0.0, g2=0.0,
+                 monotonicity=0, rsolver=Exact,
+                 interpolation=Linear, interface_zero=True, hybrid=False,
+                 blend_alpha=5.0, tf=1.0,
+                 gamma=1.4, niter=20, tol=1e-6):
+        self.gamma = gamma
+        self.niter = niter
+        self.tol = tol
+        self.g1 = g1
+        self.g2 = g2
+        self.monotonicity = monotonicity
+        self.interpolation = interpolation
+        self.rsolver = rsolver
+        self.sstar = 0.0
+        if (g1 == 0 and g2 == 0):
+            self.thermal_conduction = 0
+        else:
+            self.thermal_conduction = 1
+        self.interface_zero = interface_zero
+        self.hybrid = hybrid
+        self.blend_alpha = blend_alpha
+        self.tf = tf
+        super(GSPHAcceleration, self).__init__(dest, sources)
+
+    def solver_failures(self):
+        """Pairs of the last evaluation whose Riemann solve failed; the evaluator that compiles this equation
+        replaces the method with one that reads the device word."""
+        return 0
+
+
+class GSPHScheme(object):
+    """scheme.py:1144-1458."""
+
+    def __init__(self, fluids, solids, dim, gamma, kernel_factor, g1=0.0,
+                 g2=0.0, rsolver=2, interpolation=1, monotonicity=1,
+                 interface_zero=True, hybrid=False, blend_alpha=5.0, tf=1.0,
+                 niter=20, tol=1e-6, has_ghosts=False):
+        if list(solids):
+            raise NotImplementedError(
+                'GSPHScheme(solids=%r): the WallBoundary equation of gas_dynamics/boundary_equations.py has '
+                'not been run through this backend (not attempted); stale wall values are not computed with' % (list(solids),))
+        self.fluids = list(fluids)
+        self.solids = list(solids)
+        self.dim = dim
+        self.solver = None
+        self.integrator = None
+        self.kernel = None
+        self.gamma = gamma
+        self.kernel_factor = kernel_factor
+        self.g1 = g1
+        self.g2 = g2
+        self.rsolver = rsolver
+        self.interpolation = interpolation
+        self.monotonicity = monotonicity
+        self.interface_zero = interface_zero
+        self.hybrid = hybrid
+        self.blend_alpha = blend_alpha
+        self.tf = tf
+        self.niter = niter
+        self.tol = tol
+        self.has_ghosts = has_ghosts
+        self.rsolver_choices = {'non_diffusive': 0,
+                                'van_leer': 1,
+                                'exact': 2,
+                                'hllc': 3,
+                                'ducowicz': 4,
+                                'hlle': 5,
+                                'roe': 6,
+                                'llxf': 7,
+                                'hllc_ball': 8,
+                                'hll_ball': 9,
+                                'hllsy': 10}
+        self.interpolation_choices = {'delta': 0,
+                                      'linear': 1,
+                                      'cubic': 2}
+        self.monotonicity_choices = {'first_order': 0,
+                                     'i02': 1,
+                                     'iwin': 2}
+
+    def configure(self, **kw):
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise RuntimeError('Parameter %s not defined for %s.' % (k, type(self).__name__))
+            setattr(self, k, v)
+
+    def configure_solver(self, kernel=None, integrator_cls=None,
+                         extra_steppers=None, **kw):
+        """:1294-1335: the kernel (Gaussian by default), one ``GSPHStep`` per fluid, an Euler integrator unless
+        another class is given; ``tf`` of the keywords becomes the scheme's.  The integrator is kept in
+        ``self.integrator`` (this package has no ``Solver``; ``integrator.setup_integrator`` installs it)."""
+        from .kernels import Gaussian
+        if kernel is None:
+            kernel = Gaussian(dim=self.dim)
+        steppers = {}
+        if extra_steppers is not None:
+            steppers.update(extra_steppers)
+        cls = integrator_cls if integrator_cls is not None else EulerIntegrator
+        for name in self.fluids:
+            if name not in steppers:
+                steppers[name] = GSPHStep()
+        self.kernel = kernel
+        self.integrator = cls(**steppers)
+        self.solver_args = dict(kw)
+        if 'tf' in kw:
+            self.tf = kw['tf']
+        return self.integrator
+
+    def get_integrator(self):
+        if self.integrator is None:
+            self.configure_solver()
+        return self.integrator
+
+    def get_equations(self):
+        """:1337-1435 (the wall groups exist with ``solids`` only, which are refused)."""
+        all_pa = self.fluids + self.solids
+        equations = []
+        equations.append(Group(
+            equations=[ScaleSmoothingLength(dest=fluid, sources=None, factor=2.0) for fluid in self.fluids],
+            update_nnps=True))
+        equations.append(Group(
+            equations=[SummationDensity(dest=fluid, sources=all_pa, dim=self.dim) for fluid in self.fluids],
+            update_nnps=False))
+        equations.append(Group(
+            equations=[UpdateSmoothingLengthFromVolume(dest=fluid, sources=None, k=self.kernel_factor,
+                                                       dim=self.dim) for fluid in self.fluids],
+            update_nnps=True))
+        equations.append(Group(
+            equations=[SummationDensity(dest=fluid, sources=all_pa, dim=self.dim) for fluid in self.fluids],
+            update_nnps=False))
+        equations.append(Group(equations=[IdealGasEOS(dest=fluid, sources=None, gamma=self.gamma)
+                                          for fluid in self.fluids]))
+        equations.append(Group(equations=[GSPHGradients(dest=fluid, sources=all_pa) for fluid in self.fluids]))
+        if self.has_ghosts:
+            equations.append(Group(equations=[GSPHUpdateGhostProps(dest=fluid, sources=None) for fluid in self.fluids],
+                                   update_nnps=False, real=False))
+        equations.append(Group(equations=[
+            GSPHAcceleration(dest=fluid, sources=all_pa, g1=self.g1, g2=self.g2, monotonicity=self.monotonicity,
+                             rsolver=self.rsolver, interpolation=self.interpolation,
+                             interface_zero=self.interface_zero, hybrid=self.hybrid, blend_alpha=self.blend_alpha,
+                             gamma=self.gamma, niter=self.niter, tol=self.tol) for fluid in self.fluids]))
+        return equations
+
+    def setup_properties(self, particles, clean=True):
+        """:1437-1458 (properties are added; none is removed)."""
+        arrays = dict((pa.name, pa) for pa in particles)
+        for fluid in self.fluids:
+            pa = arrays[fluid]
+            for p in GASD_PROPS + GSPH_GRADIENT_PROPS:
                 if p not in pa.properties:
                     pa.add_property(p)
             if 'orig_idx' not in pa.properties:

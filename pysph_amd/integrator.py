@@ -72,10 +72,21 @@ class GasDFluidStep(IntegratorStep):
     _kind = STEP_GASD
 
 
+STEP_GSPH = 9
+
+
+class GSPHStep(IntegratorStep):
+    """integrator_step.py:431-449: one stage for ``EulerIntegrator``; velocities and positions advance by ``dt``, the
+    positions with the half-step velocities ``u + dt/2 au``, which the energy update also subtracts:
+    ``e += dt (ae - u* au - v* av - w* aw)``."""
+    _kind = STEP_GSPH
+
+
 # (the two rigid-body steppers are classes of pysph_amd.rigid_body; their stages need the array's body state)
 _STEP_KINDS = {'WCSPHStep': STEP_WCSPH, 'TransportVelocityStep': STEP_TVF,
                'RK2StepRigidBody': STEP_RIGID_RK2, 'EulerStepRigidBody': STEP_RIGID_EULER,
-               'EDACStep': STEP_EDAC, 'EDACTVFStep': STEP_EDAC_TVF, 'GasDFluidStep': STEP_GASD}
+               'EDACStep': STEP_EDAC, 'EDACTVFStep': STEP_EDAC_TVF, 'GasDFluidStep': STEP_GASD,
+               'GSPHStep': STEP_GSPH}
 
 
 def stepper_kind(step):

@@ -17,6 +17,11 @@ synchronise, medians and quartiles of `reps`:
     force           [IdealGasEOS | MPMUpdateGhostProps | MPMAccelerations] at the converged state, and the sweep alone
                     from the timer pair_gasd_mpm
     pec_step        whole PEC steps with GasDFluidStep (dt = 1e-4 of the box)
+    gsph            GSPHScheme on the same box at the same converged state: the gradient group
+                    [GSPHGradients] and its sweep alone (timer pair_gsph_gradients); per Riemann solver exact, hllc and
+                    roe the force group [GSPHUpdateGhostProps | GSPHAcceleration], its sweep alone (timer pair_gsph),
+                    its ratio to the MPM force group above and the solves that failed; after the PEC steps, whole Euler
+                    steps with GSPHStep (exact)
 
 The equation classes of pysph_amd.gas_dynamics are parameter holders without Python bodies, so the same group list
 cannot be forced through run-time-generated families: there is no generated comparison.
@@ -50,7 +55,7 @@ def main():
     from pysph_amd import device as dev
     from pysph_amd.acceleration_eval import AccelerationEval, SPHCompiler
     from pysph_amd.domain import HipDomainManager
-    from pysph_amd.gas_dynamics import GasDScheme
+    from pysph_amd.gas_dynamics import GasDScheme, GSPHScheme
     from pysph_amd.integrator import setup_integrator
     from pysph_amd.kernels import QuinticSpline
     from pysph_amd.nnps import HipNNPS
@@ -79,11 +84,21 @@ def main():
     tvf.setup_properties([pa])
     for a, b in zip(('uhat', 'vhat', 'what'), 'uvw'):
         pa.properties[a][:] = pa.properties[b]
+    solvers = (('exact', 2), ('hllc', 3), ('roe', 6))
+    gsph = dict((name, GSPHScheme(['fluid'], [], dim=3, gamma=1.4, kernel_factor=1.0, has_ghosts=True, rsolver=rs))
+                for name, rs in solvers)
+    gsph['exact'].setup_properties([pa])
     kernel = QuinticSpline(dim=3)
     dev.attach(pa, ctx).push(*[p for p in pa.properties if pa.properties[p].dtype == np.float64])
     groups = gas.get_equations()
     lists = dict(tvf_all=tvf.get_equations(), tvf_force=tvf.get_equations()[-1:], all=groups, density=groups[:1],
                  force=groups[1:])
+    gsph_eqs = dict((name, sch.get_equations()) for name, sch in gsph.items())
+    lists['gsph_all'] = gsph_eqs['exact']
+    lists['gsph_grad'] = gsph_eqs['exact'][5:6]
+    for name, eqs in gsph_eqs.items():
+        assert [e.name for grp in eqs[5:] for e in grp.equations] == ['GSPHGradients', 'GSPHUpdateGhostProps', 'GSPHAcceleration']
+        lists['gsph_force_' + name] = eqs[6:]
     evals = {}
     for name, eqs in lists.items():
         evals[name] = AccelerationEval([pa], eqs, kernel)
@@ -181,6 +196,27 @@ def main():
     result['force']['sweep_alone_ms'] = (ms1 - ms0) / max(c1 - c0, 1)
     result['force_over_tvf_force'] = result['force']['median_ms'] / result['tvf_force']['median_ms']
 
+    # -- GSPH at the same state: the gradient group, then the force group per Riemann solver ---------------------------
+    def timed_group(name, key):
+        fn = lambda: evals[name].compute(0.0, 1e-4)
+        warm(lambda: clocked(fn))
+        r = quartiles([clocked(fn) for _ in range(args.reps)])
+        ctx.lib.sph_timer_enable(ctx._h, 1)
+        ms0, c0 = timer(key)
+        for _ in range(10):
+            fn()
+        ms1, c1 = timer(key)
+        ctx.lib.sph_timer_enable(ctx._h, 0)
+        r['sweep_alone_ms'] = (ms1 - ms0) / max(c1 - c0, 1)
+        return r
+    result['gsph'] = dict(gradients=timed_group('gsph_grad', 'pair_gsph_gradients'))
+    for name, _ in solvers:
+        r = timed_group('gsph_force_' + name, 'pair_gsph')
+        r['solver_failures'] = gsph_eqs[name][-1].equations[0].solver_failures()
+        r['over_mpm_force'] = r['median_ms'] / result['force']['median_ms']
+        r['sweep_over_mpm_sweep'] = r['sweep_alone_ms'] / result['force']['sweep_alone_ms']
+        result['gsph']['force_' + name] = r
+
     # -- whole PEC steps ------------------------------------------------------------------------------------------------
     integ = gas.configure_solver(kernel=kernel)
     setup_integrator(integ, evals['all'], nnps)
@@ -195,6 +231,17 @@ def main():
         ms.append(clocked(step))
         its.append(its_of('all'))
     result['pec_step'] = dict(quartiles(ms), iterations=sorted(set(int(v) for v in its)))
+
+    # -- whole Euler steps of GSPHScheme (exact) ----------------------------------------------------------------------
+    ginteg = gsph['exact'].configure_solver(kernel=kernel)
+    setup_integrator(ginteg, evals['gsph_all'], nnps)
+
+    def gstep():
+        ginteg.step(state['t'], 1e-4 * dx / 0.01)
+        state['t'] += 1e-4 * dx / 0.01
+    warm(lambda: clocked(gstep))
+    result['gsph']['euler_step'] = quartiles([clocked(gstep) for _ in range(args.reps)])
+    result['gsph']['euler_step']['solver_failures'] = gsph_eqs['exact'][-1].equations[0].solver_failures()
     os.makedirs(args.out, exist_ok=True)
     tag = '_f32' if args.f32 else ''
     with open(os.path.join(args.out, 'bench_gasd%s.json' % tag), 'w') as f:
