@@ -227,7 +227,12 @@ int sph_prop_id(const char *name); /* -1 if unknown */
 /* ---------------------------------------------------------------------- */
 /* (Re)size array `array_id` to n particles of which the first n_real are
  * real (particle_array.pyx:423).  Existing device data is preserved up to
- * min(old, new).                                                           */
+ * min(old, new), and NOTHING is cleared: rows behind n keep what a shrink, a
+ * gather or a removal left in them, and a later grow inside the capacity
+ * shows them again (a reallocating grow shows zeros).  Whoever grows an array
+ * writes the new rows: the halo and open-boundary appends do, and
+ * HipDeviceHelper.resize / extend zero them (sph_array_fill), so that the rows
+ * they bring into existence read 0 like the host array's.                  */
 int sph_array_resize(sph_ctx *ctx, int array_id, size_t n, size_t n_real);
 int sph_array_size(sph_ctx *ctx, int array_id, size_t *n, size_t *n_real);
 /* New particle i takes every device property of old particle indices[i]
@@ -450,7 +455,10 @@ typedef struct sph_gen_family {
 int sph_eval_generated(sph_ctx *ctx, const sph_kernel *kernel, sph_gen_family *family,
                        double t, double dt);
 /* max over the first n_real particles of a property (dt_cfl, dt_force:
- * pysph/sph/integrator.py:161-200).                                        */
+ * pysph/sph/integrator.py:161-200); rows behind n_real do not count.
+ * Infinities reduce as values.  A NaN row is ignored (fmax), unlike numpy's
+ * max, which propagates it; an all-NaN range yields the identity, -inf.
+ * n_real == 0: *out = -DBL_MAX.                                            */
 int sph_reduce_max(sph_ctx *ctx, int array_id, int prop, double *out);
 
 /* ---------------------------------------------------------------------- */
@@ -717,7 +725,10 @@ int sph_gasd_unconverged(sph_ctx *ctx, int *flag);
  * one atomic add per failing pair into a device word; this call is the only host round trip, made when asked.      */
 int sph_gsph_failures(sph_ctx *ctx, unsigned long long *count);
 /* min over the first n_real particles of a property (h_minimum,
- * pysph/sph/integrator.py:150-160).                                        */
+ * pysph/sph/integrator.py:150-160); rows behind n_real do not count.
+ * Infinities reduce as values.  A NaN row is ignored (fmax of the negated
+ * values), unlike numpy's min, which propagates it; an all-NaN range yields
+ * the identity, +inf.  n_real == 0: *out = DBL_MAX.                        */
 int sph_reduce_min(sph_ctx *ctx, int array_id, int prop, double *out);
 
 /* ---------------------------------------------------------------------- */

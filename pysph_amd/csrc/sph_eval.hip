@@ -4499,7 +4499,7 @@ static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_ge
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_max(const double *__restrict__ v, size_t n, double *__restrict__ part, double sgn)
 {
-    double m = -DBL_MAX;
+    double m = -INFINITY; // the identity of max: a range of nothing but -inf (min: +inf) reduces to that infinity
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         m = fmax(m, sgn * v[i]);
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));

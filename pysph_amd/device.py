@@ -451,8 +451,19 @@ class HipDeviceHelper(object):
             pa.set_num_real_particles(n if grow and nr0 == self._n else min(nr0, n))
         n = pa.get_number_of_particles() if n is None else n
         nreal = min(pa.get_number_of_particles(True), n)
+        n0 = self.get_number_of_particles()
         _check(self.lib.sph_array_resize(self.ctx._h, self.array_id, n, nreal))
+        self._zero_rows(n0, n)
         self._n = n
+
+    def _zero_rows(self, lo, hi):
+        """rows [lo, hi) of every property with device storage <- 0: the rows a grow of THIS helper brings into
+        existence read 0, as those of the host array do (ParticleArray.resize).  sph_array_resize itself keeps
+        whatever a shrink, a gather or a removal left behind the particles (include/sphhip.h)."""
+        if hi <= lo:
+            return
+        for pid in self.device_props():
+            _check(self.lib.sph_array_fill(self.ctx._h, self.array_id, pid, 0.0, lo, hi - lo))
 
     def _sync_size(self):
         if self.managed:
@@ -656,12 +667,16 @@ class HipDeviceHelper(object):
                     arr[nreal:n] = np.iinfo(arr.dtype).max
 
     def max(self, prop):
+        """max over the REAL rows of the device property (sph_reduce_max).  A NaN row is ignored, and an all-NaN
+        range yields the identity (-inf) -- numpy's max would propagate the NaN; no real rows: -DBL_MAX."""
         out = C.c_double()
         _check(self.lib.sph_reduce_max(self.ctx._h, self.array_id,
                                        prop_id(prop), C.byref(out)))
         return out.value
 
     def min(self, prop):
+        """min over the REAL rows of the device property (sph_reduce_min).  A NaN row is ignored, and an all-NaN
+        range yields the identity (+inf) -- numpy's min would propagate the NaN; no real rows: DBL_MAX."""
         out = C.c_double()
         _check(self.lib.sph_reduce_min(self.ctx._h, self.array_id,
                                        prop_id(prop), C.byref(out)))
@@ -745,6 +760,7 @@ class HipDeviceHelper(object):
         get_npy(pa, 'tag')[n0:] = 0
         _check(self.lib.sph_array_resize(self.ctx._h, self.array_id, n0 + num_particles,
                                          self.get_number_of_particles(True)))
+        self._zero_rows(n0, n0 + num_particles)
         self._n = n0 + num_particles
 
     def add_particles(self, align=True, **particle_props):

@@ -173,18 +173,22 @@ class Integrator(object):
     def update_domain(self):
         self.nnps.update_domain()
 
-    def _reduce(self, pa, name, op):
-        """max/min of one property: on the device when the state is
-        device-resident (sync='manual') and the property is one the device
-        owns (h, or anything an equation writes); from the host array
-        otherwise (sync='auto', or a property only the user sets)."""
+    def _on_device(self, pa, name):
+        """whether ``_reduce`` takes property `name` of `pa` from the device"""
         ev = getattr(self.acceleration_evals[0], 'c_acceleration_eval', None)
         manual = getattr(ev, 'sync', 'auto') == 'manual'
         written = set()
         if ev is not None:
             written = set(ev.outputs.get(pa.name, ())) | set(ev.outputs_exact.get(pa.name, ()))
-        if manual and pa.gpu is not None and dev.prop_id(name) >= 0 and \
-                (name == 'h' or name in written):
+        return manual and pa.gpu is not None and dev.prop_id(name) >= 0 and \
+            (name == 'h' or name in written)
+
+    def _reduce(self, pa, name, op):
+        """max/min of one property: on the device when the state is
+        device-resident (sync='manual') and the property is one the device
+        owns (h, or anything an equation writes); from the host array
+        otherwise (sync='auto', or a property only the user sets)."""
+        if self._on_device(pa, name):
             return pa.gpu.max(name) if op == 'max' else pa.gpu.min(name)
         import numpy as np
         from .particle_array import get_npy
@@ -201,6 +205,10 @@ class Integrator(object):
         dt_min = float('inf')
         for pa in arrays:
             if pa.get_number_of_particles() > 0:
+                if self._on_device(pa, 'dt_adapt') and pa.gpu.get_number_of_particles(True) == 0:
+                    # the device reduces over the real rows: an array that holds nothing but ghosts has no
+                    # constraint to give (its reduction would hand back the empty range's DBL_MAX as a time step)
+                    continue
                 dt_min = min(dt_min, self._reduce(pa, 'dt_adapt', 'min'))
         pm = self.parallel_manager
         if pm is not None and hasattr(pm, 'reduce_min'):

@@ -54,6 +54,52 @@ def test_oracle_steppers_match_reference_bitwise():
         assert np.array_equal(pa.properties[k], g['tvf/stage2/' + k]), k
 
 
+def _golden_inputs(fname):
+    from pysph_amd.particle_array import ParticleArray
+    g = load_golden(fname)
+    props = dict((k[3:], g[k].copy()) for k in g.files if k.startswith('in/'))
+    return g, ParticleArray(name='fluid', **props), sorted(props), float(g['dt'])
+
+
+def _assert_bitwise(pa, g, prefix, names):
+    for k in names:
+        assert np.array_equal(pa.properties[k], g[prefix + k]), (prefix, k)
+
+
+@pytest.mark.parametrize('tag,tvf', [('edac', False), ('edac_tvf', True)])
+def test_oracle_edac_steppers_match_reference_bitwise(tag, tvf):
+    """numpy restatement of EDACStep / EDACTVFStep vs the reference's own methods (edac_steppers.npz): every
+    property after every stage, bit-exact"""
+    from oracle import steppers as S
+    g, pa, names, dt = _golden_inputs('edac_steppers.npz')
+    S.edac_initialize(pa)
+    _assert_bitwise(pa, g, tag + '/initialize/', names)
+    S.edac_stage(pa, dt, 1, tvf)
+    _assert_bitwise(pa, g, tag + '/stage1/', names)
+    S.edac_stage(pa, dt, 2, tvf)
+    _assert_bitwise(pa, g, tag + '/stage2/', names)
+
+
+def test_oracle_gasd_stepper_matches_reference_bitwise():
+    """numpy restatement of GasDFluidStep vs the reference's own methods (gasd_steppers.npz), bit-exact"""
+    from oracle import steppers as S
+    g, pa, names, dt = _golden_inputs('gasd_steppers.npz')
+    S.gasd_initialize(pa)
+    _assert_bitwise(pa, g, 'gasd/initialize/', names)
+    S.gasd_stage(pa, dt, 1)
+    _assert_bitwise(pa, g, 'gasd/stage1/', names)
+    S.gasd_stage(pa, dt, 2)
+    _assert_bitwise(pa, g, 'gasd/stage2/', names)
+
+
+def test_oracle_gsph_stepper_matches_reference_bitwise():
+    """numpy restatement of GSPHStep.stage1 vs the reference's own method (gsph_steppers.npz), bit-exact"""
+    from oracle import steppers as S
+    g, pa, names, dt = _golden_inputs('gsph_steppers.npz')
+    S.gsph_stage1(pa, dt)
+    _assert_bitwise(pa, g, 'gsph/stage1/', names)
+
+
 def test_integrator_api_surface():
     from pysph_amd.integrator import (Integrator, EPECIntegrator, WCSPHStep,
                                       TransportVelocityStep)
