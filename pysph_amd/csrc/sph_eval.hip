@@ -1916,6 +1916,10 @@ template <class T> __device__ __forceinline__ int gs_exact(T rhol, T rhor, T pl,
 
 template <class T> __device__ __forceinline__ int gs_ducowicz(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, T &ps, T &us)
 { // :431-525
+    // a, b, c and d are differences of products of order (rho cs)^2 that cancel down to order rho p: a fused multiply-add
+    // rounds them otherwise than the reference's separately rounded products, and at rho = 1e10, p = 1e20 that moved pstar
+    // by more than four times the reference's own distance from the exact value.  Every product here is rounded on its own.
+#pragma clang fp contract(off)
     const T al = T(0.5) * (gamma + T(1)), ar = al;
     const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
     const T umin = ur - T(0.5) * csr / ar, umax = ul + T(0.5) * csl / al;
@@ -1924,6 +1928,7 @@ template <class T> __device__ __forceinline__ int gs_ducowicz(T rhol, T rhor, T 
     T a = (br - bl) * (prmin - plmin), b = br * umin * umin - bl * umax * umax, c = br * umin - bl * umax;
     const T d = br * bl * (umin - umax) * (umin - umax);
     auto pstar_of = [&](T ustar) {
+#pragma clang fp contract(off)
         const T v = T(0.5) * (plmin + prmin + br * fabs(ustar - umin) * (ustar - umin) - bl * fabs(ustar - umax) * (ustar - umax));
         return gs_max(v, T(0));
     };

@@ -648,3 +648,33 @@ def np_tait(rho, rho0, c0, gamma, p0=0.0, hg=False, mutation=None):
     else:
         rg, rk = np.power(ratio, gamma), np.power(ratio, 0.5 * (gamma - 1.0))
     return {'rho': rho, 'p': p0 + (rho0 * c0 * c0 / gamma) * (rg - 1.0), 'cs': c0 * rk}
+
+
+# rounding cost, in units of u of the decoded value, of gsph_decode below (pstar, ustar), counted from the operations:
+#   pstar: the destination's column is au = fl(fl(-m_j pstar) C) x_ij with C = c_i + c_j the pair factor.  m_j is a power
+#          of two and x_ij = +-2^-3, so au carries one rounding, the calibration column (pstar_0 = fl((pl + pr) / 2), formed
+#          here from the same two doubles in the same way) another, and the quotient and the product of the decoding one
+#          each: 4 u.  C is the same bits in both launches and cancels.
+#   ustar: the device forms ae = fl(f fl(ustar (e . x_ij))) with e . x_ij = 2^-3 and au = f x_ij exactly: two roundings and
+#          the quotient, 3 u.  The reference forms vstar . DWI and vstar . DWJ (one rounding each), weighs them with
+#          vij_i and vij_j (one each), adds (one) and multiplies by fl(-m_j pstar) (one); au goes the same way without
+#          the first pair.  Both sums have terms of one sign, so each factor (1 + d) passes to the sum: 4 + 3 roundings
+#          and the quotient, 8 u.  The larger figure is the stated one.
+GSPH_DECODE_COST = (4.0, 8.0)
+
+
+def gsph_decode(x, au, ae, au_cal, p_cal):
+    """(pstar, ustar) of every destination of a table of isolated 1-D pairs (particles 2 k and 2 k + 1 are partners, 2^-3
+    apart; tests/golden/make_gsph_riemann_golden.py) from the two columns GSPHAcceleration wrote with delta interpolation
+    and no conduction: au_i = -m_j pstar (c_i + c_j) x_ij and ae_i = f ustar e x_ij.  ``au_cal`` is au of the SAME table
+    under the non-diffusive solver, whose pstar is ``p_cal`` = (pl + pr) / 2, one rounding; where that is zero the pair
+    cannot be calibrated (give it a twin).  ustar is not defined where au is zero (pstar = 0): NaN there.  The cost in
+    roundings is GSPH_DECODE_COST."""
+    x, au, ae, au_cal, p_cal = [np.asarray(a, dtype=np.float64) for a in (x, au, ae, au_cal, p_cal)]
+    partner = np.arange(x.size) ^ 1
+    e = np.sign(x - x[partner])
+    assert np.all(np.abs(x - x[partner]) == 0.125)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        pstar = au / au_cal * p_cal
+        ustar = np.where(au != 0.0, e * ae / au, np.nan)
+    return pstar, ustar
