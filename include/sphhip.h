@@ -145,9 +145,20 @@ enum sph_eq_kind {
     SPH_EQ_GSPH_GRADIENTS = 40,               /* gsph.py:61-101     (writes px..pz ux..uz vx..vz wx..wz: twelve sums with DWI) */
     SPH_EQ_GSPH_UPDATE_GHOST_PROPS = 41,      /* :104-145   (no sources, Group(real=False)): the twelve gradients, grhox..z, dwdh,
                                                  rho, div, p, cs of every row behind the real ones from the row orig_idx names */
-    SPH_EQ_GSPH_ACCELERATION = 42             /* :148-541   par: g1 g2 monotonicity rsolver interpolation interface_zero hybrid
+    SPH_EQ_GSPH_ACCELERATION = 42,            /* :148-541   par: g1 g2 monotonicity rsolver interpolation interface_zero hybrid
                                                  blend_alpha tf gamma niter tol   (writes au av aw ae; solver failures are
                                                  counted in a device word: sph_gsph_failures)                           */
+    /* ADKE (gas_dynamics/basic.py, boundary_equations.py).  h0, div, logrho, wij, htmp are user properties of those names. */
+    SPH_EQ_SUMMATION_DENSITY_ADKE = 43,       /* basic.py:32-71   par: k eps   (h = h0 on the destinations, then one sweep: writes
+                                                 rho arho (= 0) div logrho; behind it, in place of the reduce hook, the sum of
+                                                 logrho over EVERY row of the destination in a fixed order, kept in a device
+                                                 word, and h = k (exp(S / n) / rho)^eps h0 on every row: nothing is read back) */
+    SPH_EQ_ADKE_ACCELERATIONS = 44,           /* :274-353   par: alpha beta g1 g2 k eps (g2 arrives equal to g1, as the reference's
+                                                 constructor leaves it)   (writes au av aw ae)                               */
+    SPH_EQ_ADKE_UPDATE_GHOST_PROPS = 45,      /* :500-512   (no sources, Group(real=False)): p, cs and rho of every row behind the
+                                                 real ones from the row orig_idx names                                     */
+    SPH_EQ_GASD_WALL_BOUNDARY = 46            /* boundary_equations.py:5-48   (destination: a wall, sources: the fluids; h = h0,
+                                                 then one sweep of eleven sums with WI: writes wij p u v w m rho e cs div htmp h) */
 };
 
 /* One Equation(dest, sources) instance: pysph/sph/equation.py:392-420. */
@@ -710,7 +721,8 @@ enum sph_stepper {
     SPH_STEP_EDAC = 6,       /* EDACStep            pysph/sph/wc/edac.py:95-133  (p0, ap: user properties)  */
     SPH_STEP_EDAC_TVF = 7,   /* EDACTVFStep         pysph/sph/wc/edac.py:493-540                            */
     SPH_STEP_GASD = 8,       /* GasDFluidStep       integrator_step.py:351-428 (h0, ah, converged, omega, alpha*: user properties) */
-    SPH_STEP_GSPH = 9        /* GSPHStep            integrator_step.py:431-449 (stage 1 only)                */
+    SPH_STEP_GSPH = 9,       /* GSPHStep            integrator_step.py:431-449 (stage 1 only)                */
+    SPH_STEP_ADKE = 10       /* ADKEStep            integrator_step.py:452-499                               */
 };
 int sph_integrate_stage(sph_ctx *ctx, int array_id, int stepper, int stage, double dt);
 /* The convergence word of the last sph_eval_group call that ran an iterating SPH_EQ_GASD_SUMMATION_DENSITY
@@ -875,7 +887,9 @@ int sph_timer_reset(sph_ctx *ctx);
  * delta-SPH or laminar-viscosity terms), "pair_delta_sph_pre" (moment matrix and
  * renormalised density gradient), "pair_edac" (the EDAC force group), "pair_avg_pressure"
  * (ComputeAveragePressure, alone or with a density summation), "pair_gasd_density" (the gas-dynamics density sweep with
- * its Newton step for h), "pair_gasd_mpm" (MPMAccelerations), "pair_gsph_gradients" (GSPHGradients), "pair_gsph" (GSPHAcceleration); the counter "n_gasd_skipped" (wavefronts of that sweep
+ * its Newton step for h), "pair_gasd_mpm" (MPMAccelerations), "pair_gsph_gradients" (GSPHGradients), "pair_gsph" (GSPHAcceleration),
+ * "pair_adke_density" (SummationDensityADKE: the sweep with the reduction and the h launch behind it), "pair_adke" (ADKEAccelerations),
+ * "pair_gasd_wall" (WallBoundary of gas dynamics); the counter "n_gasd_skipped" (wavefronts of the gas-dynamics density sweep
  * that left early under option gasd_skip); out: total ms and launches.  Launch counters (ms = 0, counted
  * whether or not timing is enabled): "n_eos_fused" (pair launches on the 64-byte
  * EOS-fused records), "n_eos_absorbed" (of those, the ones whose record packing ran the Tait EOS: sph_group.src_eos 3), "n_mass_fused" (launches on records that rely on one mass per array), "n_merged" (group

@@ -275,6 +275,7 @@ class _BuiltinUnit(object):
         self.edac_arrays = set()          # arrays an EDAC equation reads or writes
         self.gasd_arrays = set()          # arrays a gas-dynamics equation reads or writes
         self.gasd_iterating = []          # the SummationDensity equations of gas dynamics that iterate on h
+        self.writes_h_behind_grid = False  # SummationDensityADKE / WallBoundary: h changes with no neighbour update behind it
         for i, eq in enumerate(eqs):
             kind, vals, dprops, sprops = resolve_equation(eq)
             if kind in _DELTA_SPH_KINDS:
@@ -299,6 +300,12 @@ class _BuiltinUnit(object):
             dprops = _columns(arrays[eq.dest], dprops)
             if kind in _WRITES_H_KINDS and (kind != _GASD_DENSITY_KIND or vals[3]):
                 owner.outputs_exact[eq.dest].add('h')      # (the tables' 'h' is an input everywhere else)
+            if kind == _WALL_KIND:
+                owner.outputs_exact[eq.dest].update(('m', 'u', 'v', 'w'))   # (inputs everywhere else, too)
+            if kind in (_ADKE_DENSITY_KIND, _WALL_KIND):
+                self.writes_h_behind_grid = True
+            if kind == _ADKE_DENSITY_KIND:
+                owner.device_reduce.add(id(eq))
             ce = self.ceqs[i]
             ce.kind = kind
             ce.dest = array_ids[eq.dest]
@@ -530,6 +537,7 @@ class _CGroup(object):
         self.gsph_grad = self.gsph_ghost = False   # the group holds GSPHGradients / GSPHUpdateGhostProps
         self.ghosts_first = None          # a GSPHGradients group: the GSPHUpdateGhostProps group behind it, run before it too
         self.moments = {}                 # RigidBodyMoments equation -> its unit: run in place of the reduce hook
+        self.device_reduce = set()        # SummationDensityADKE equations: their reduce ran on the device, behind the sweep
         self.eos_absorbed_by = None       # annotate_plan: the pair group after this Tait-EOS group that may run the EOS itself
         self.absorbs_eos = False          # ... and that pair group's side of it
         self._arrays = arrays
@@ -683,13 +691,15 @@ class _CGroup(object):
             u.read_convergence(ev)
 
 
-_GASD_KINDS = (34, 35, 36, 37, 38, 39, 40, 41, 42)    # gas dynamics: density sweep, ideal-gas EOS, MPM accelerations, the two h equations, ghost p / cs; GSPH gradients, ghost columns, accelerations
-_GASD_GHOST_KINDS = (39, 41)          # MPMUpdateGhostProps, GSPHUpdateGhostProps: read orig_idx
+_GASD_KINDS = (34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46)    # gas dynamics: density sweep, ideal-gas EOS, MPM accelerations, the two h equations, ghost p / cs; GSPH gradients, ghost columns, accelerations; ADKE density, accelerations, ghost columns, the wall
+_GASD_GHOST_KINDS = (39, 41, 45)      # MPMUpdateGhostProps, GSPHUpdateGhostProps, ADKEUpdateGhostProps: read orig_idx
+_ADKE_DENSITY_KIND = 43               # SummationDensityADKE: the library runs its reduce on the device, the host hook is not called
+_WALL_KIND = 46                       # WallBoundary of gas dynamics: writes h, m, u, v, w of the wall
 _GSPH_GRAD_KIND = 40
 _GSPH_GHOST_KIND = 41
 _GSPH_FORCE_KIND = 42
 _GASD_DENSITY_KIND = 34
-_WRITES_H_KINDS = (29, 34, 37, 38)    # UpdateSmoothingLengthFerrari; the iterating density sweep; scale h; h from the volume
+_WRITES_H_KINDS = (29, 34, 37, 38, 43, 46)    # UpdateSmoothingLengthFerrari; the iterating density sweep; scale h; h from the volume; ADKE density; the gas-dynamics wall
 _EDAC_KINDS = (30, 31, 32, 33)        # average pressure, the two pressure gradients, the pressure rate
 _DELTA_SPH_KINDS = (22, 23, 24, 25)   # moment matrix, gradient correction, gradrho pre-step, delta-SPH continuity
 _UPDATE_H_KIND = 29             # SPH_EQ_UPDATE_H_FERRARI
@@ -709,6 +719,10 @@ def _plain_leaf(g, cg):
     for eq in g.equations:
         if hasattr(eq, 'py_initialize') or hasattr(eq, 'reduce') or rigid_kind(eq):
             return False
+    # SummationDensityADKE / WallBoundary write h with no neighbour update behind them: nothing kept from such a group
+    # (neighbour lists, promises about the records) holds in the next one
+    if any(getattr(u, 'writes_h_behind_grid', False) for u in cg.units):
+        return False
     return all(isinstance(u, _BuiltinUnit) for u in cg.units)
 
 
@@ -1102,6 +1116,8 @@ class HipAccelerationEval(object):
             for eq in g.equations:
                 if id(eq) in item.moments:
                     item.moments[id(eq)].run(self, t, dt)       # sph_rigid_moments, not the host's reduce
+                elif id(eq) in item.device_reduce:
+                    pass                                            # the library ran it behind the sweep (run_adke_sd)
                 elif hasattr(eq, 'reduce'):
                     self._host_hook(eq.reduce, self.arrays[eq.dest], t, dt)
         if g.update_nnps:

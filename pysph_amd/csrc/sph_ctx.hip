@@ -461,7 +461,7 @@ int sph_timer_get(sph_ctx *c, const char *key, double *ms, long *count)
 {
     static const char *names[T_COUNT] = {"nnps", "pack", "eos", "pair", "stage",
                                          "pair_none", "pair_wcsph", "pair_density", "pair_tvf", "pair_vgrad", "pair_elastic",
-                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure", "pair_gasd_density", "pair_gasd_mpm", "pair_gsph_gradients", "pair_gsph",
+                                         "pair_nbr", "pair_wcsph_options", "pair_delta_sph_pre", "pair_edac", "pair_avg_pressure", "pair_gasd_density", "pair_gasd_mpm", "pair_gsph_gradients", "pair_gsph", "pair_adke_density", "pair_adke", "pair_gasd_wall",
                                          "n_eos_fused", "n_nl_keep", "n_nl_reuse", "n_mass_fused", "n_merged", "n_tension_flag", "n_phase2", "n_async", "n_dest_list", "n_row_lds", "n_interp_moment", "n_interp_sweep", "n_eos_absorbed", "n_gasd_skipped", "n_placed", "n_place_overflow"};
     SPH_TRY(timer_drain(c));
     for (int i = 0; i < T_COUNT; i++)

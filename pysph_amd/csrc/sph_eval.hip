@@ -239,6 +239,17 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
         a.cs[i] = a.cs[idx];
         break;
     }
+    case SPH_EQ_ADKE_UPDATE_GHOST_PROPS: { // gas_dynamics/basic.py:506-512; par as above: p, cs and rho, no more
+        const size_t n_real = (size_t)a.par[0];
+        if (i < n_real) break;
+        const double oi = a.q[(int)a.par[1]][i];
+        if (!(oi >= 0.0 && oi < (double)n_real)) break;
+        const size_t idx = (size_t)oi;
+        a.p[i] = a.p[idx];
+        a.cs[i] = a.cs[idx];
+        a.rho[i] = a.rho[idx];
+        break;
+    }
     case SPH_EQ_GSPH_UPDATE_GHOST_PROPS: { // gas_dynamics/gsph.py:113-145; par as above, gcol: px..wz grhox..z dwdh rho div p cs
         const size_t n_real = (size_t)a.par[0];
         if (i < n_real) break;
@@ -1775,6 +1786,166 @@ template <class T> struct FamMPM_T {
     }
 };
 
+// ---- ADKE (gas_dynamics/basic.py:32-71, :274-353; boundary_equations.py) -----------------------------------------
+// SummationDensityADKE (:32-71): rho with WIJ at HIJ, arho with DWI at the destination's own h (which is its h0: the
+// host driver runs the reference's `h = h0` over the destinations before the records are packed), and in finish() the
+// post_loop: div, arho = 0, logrho.  The reduce hook -- the sum of logrho and the new h of every row -- is two further
+// launches behind this one (run_adke_sd).  Records [x y z h | m u v w]: 64 B in fp64 (four 16-B pieces), 32 B in fp32.
+// MINB 4, as FamGasSD_T, of which this is the shorter body: 105..128 VGPRs in fp64 under variable h (the only h it runs
+// with), 20 B of scratch in kernel id 10 alone.
+enum { F_ASD = 1 };
+template <class T> struct FamADKESD_T {
+    typedef T Real;
+    static constexpr bool PRED = true; // both sums are selected on the criterion
+    static constexpr uint32_t CF0 = F_ASD;
+    static constexpr int MINB = 4;
+    static constexpr int NA = 4; // m u v w
+    static constexpr int NR = 8;
+    struct Params { double *rho, *arho, *div, *logrho; };
+    struct Dest { T u, v, w, rho, arho; };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        D.u = a[1]; D.v = a[2]; D.w = a[3];
+        D.rho = D.arho = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        PairGeomT<T> gij, g;
+        pair_geom<KK, UH>(gij, pi, pj, r2, a);
+        pair_geom_at<KK, UH>(g, gij, pi.w, a);
+        const T wij = pair_w<KK, UH>(gij), tg = pair_gradfac<KK, UH>(g);
+        const T mj = s[0];
+        const T vijdotdwi = tg * ((D.u - s[1]) * g.xij[0] + (D.v - s[2]) * g.xij[1] + (D.w - s[3]) * g.xij[2]);
+        D.rho += pass ? mj * wij : T(0.0);
+        D.arho += pass ? mj * vijdotdwi : T(0.0);
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        const double rho = (double)D.rho;
+        a.p.rho[o] = rho;
+        a.p.div[o] = -(double)D.arho / rho; // :59-62
+        a.p.arho[o] = 0.0;
+        a.p.logrho[o] = log(rho);
+    }
+};
+
+// ADKEAccelerations (:274-353): the pressure term, the Monaghan viscosity under XIJ.VIJ < 0 (HIJ, EPS, RHOIJ1) and the
+// conduction Hij of h, cs, div, e of both particles (RHOIJ), all with DWIJ at HIJ.  A source may be a wall row that no
+// fluid particle reached (rho = 0, cs = NaN: IdealGasEOS on WallBoundary's raw sums): it is never inside the criterion,
+// and the four increments are SELECTED on the criterion, not multiplied by a masked gradient, so that its NaN stays where
+// it is.  Records [x y z h | u v w rho p cs e m div -]: 112 B in fp64 (seven 16-B pieces), 64 B in fp32.
+// MINB 3, as FamMPM_T: 121..139 VGPRs in fp64 under variable h, no scratch; the budget of four blocks is 128.
+enum { F_ADKE = 1 };
+template <class T> struct FamADKE_T {
+    typedef T Real;
+    static constexpr bool PRED = true;
+    static constexpr uint32_t CF0 = F_ADKE;
+    static constexpr int MINB = 3;
+    static constexpr int NA = 9; // u v w rho p cs e m div
+    static constexpr int NR = 14;
+    struct Params {
+        T alpha, beta, g1, g2;
+        double *au, *av, *aw, *ae;
+    };
+    struct Dest {
+        T u, v, w, rho, cs, e, div, pib; // pib = p_i / rho_i^2
+        T au, av, aw, ae;
+    };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
+    {
+        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[3]; D.cs = a[5]; D.e = a[6]; D.div = a[8];
+        D.pib = a[4] / (a[3] * a[3]);
+        D.au = D.av = D.aw = D.ae = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        PairGeomT<T> g;
+        pair_geom<KK, UH>(g, pi, pj, r2, a);
+        const T tg = pair_gradfac<KK, UH>(g);
+        const T rhoj = s[3], mj = s[7];
+        const T pjb = s[4] / (rhoj * rhoj);
+        const T cij = T(0.5) * (D.cs + s[5]);
+        const T hi = pi.w, hj = pj.w;
+        // :319-322: thermal conduction
+        const T Hi = a.p.g1 * hi * D.cs + a.p.g2 * hi * hi * (fabs(D.div) - D.div);
+        const T Hj = a.p.g1 * hj * s[5] + a.p.g2 * hj * hj * (fabs(s[8]) - s[8]);
+        const T rhoij = T(0.5) * (D.rho + rhoj);
+        const T r2e = r2 + g.eps;
+        const T Hij = (Hi + Hj) * (D.e - s[6]) / (rhoij * r2e);
+        const T v0 = D.u - s[0], v1 = D.v - s[1], v2 = D.w - s[2];
+        const T xv = g.xij[0] * v0 + g.xij[1] * v1 + g.xij[2] * v2;
+        const T muij = g.hij * xv / r2e;
+        const T pi_v = muij * (a.p.beta * muij - a.p.alpha * cij) / rhoij; // :324-328
+        const T piij = xv < T(0.0) ? pi_v : T(0.0);
+        const T tmpv = D.pib + pjb + piij;
+        const T f = -mj * tmpv * tg;
+        const T vijdotdwij = tg * xv;
+        const T xijdotdwij = tg * (g.xij[0] * g.xij[0] + g.xij[1] * g.xij[1] + g.xij[2] * g.xij[2]);
+        const T de = T(0.5) * mj * (tmpv * vijdotdwij + T(2.0) * xijdotdwij * Hij);
+        D.au += pass ? f * g.xij[0] : T(0.0);
+        D.av += pass ? f * g.xij[1] : T(0.0);
+        D.aw += pass ? f * g.xij[2] : T(0.0);
+        D.ae += pass ? de : T(0.0);
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        a.p.au[o] = (double)D.au; a.p.av[o] = (double)D.av; a.p.aw[o] = (double)D.aw; a.p.ae[o] = (double)D.ae;
+    }
+};
+
+// WallBoundary (boundary_equations.py:5-48): the destination is a wall, the sources are the fluids.  Eleven sums with WI
+// at the wall row's own h (its h0: the host driver runs `h = h0` first, as for SummationDensityADKE); finish() is the
+// post_loop: every sum over wij where wij > 1e-30 and h = htmp / wij there, else the raw sums and h stays h0.  The
+// records are FamADKE_T's, [x y z h | u v w rho p cs e m div -], read on the fluids' side only.
+// MINB 3: eleven accumulators; up to 136 VGPRs in fp64 under variable h, no scratch; the budget of four blocks is 128.
+enum { F_GWALL = 1 };
+template <class T> struct FamGasWall_T {
+    typedef T Real;
+    static constexpr bool PRED = true; // every sum carries WI, selected on the criterion
+    static constexpr uint32_t CF0 = F_GWALL;
+    static constexpr int MINB = 3;
+    static constexpr int NA = 9; // u v w rho p cs e m div
+    static constexpr int NR = 14;
+    struct Params { double *wij, *p, *u, *v, *w, *m, *rho, *e, *cs, *div, *htmp, *h; };
+    struct Dest { T wij, q[9], htmp; };
+    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *, const A &, uint32_t)
+    {
+        D.wij = D.htmp = T(0.0);
+        for (int k = 0; k < 9; k++) D.q[k] = T(0.0);
+    }
+    template <int KK, bool UH, class A>
+    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
+                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
+    {
+        PairGeomT<T> gij, g;
+        pair_geom<KK, UH>(gij, pi, pj, r2, a);
+        pair_geom_at<KK, UH>(g, gij, pi.w, a);
+        T wi = pair_w<KK, UH>(g);
+        wi = pass ? wi : T(0.0);
+        D.wij += wi;
+#pragma unroll
+        for (int k = 0; k < 9; k++) D.q[k] += pass ? s[k] * wi : T(0.0);
+        D.htmp += pass ? pj.w * wi : T(0.0);
+    }
+    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
+    {
+        const double wij = (double)D.wij, htmp = (double)D.htmp;
+        const bool reached = wij > 1e-30;
+        double q[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) q[k] = reached ? (double)D.q[k] / wij : (double)D.q[k];
+        a.p.wij[o] = wij;
+        a.p.u[o] = -q[0]; a.p.v[o] = -q[1]; a.p.w[o] = -q[2]; // (d_u -= s_u WI)
+        a.p.rho[o] = q[3]; a.p.p[o] = q[4]; a.p.cs[o] = q[5]; a.p.e[o] = q[6]; a.p.m[o] = q[7]; a.p.div[o] = q[8];
+        a.p.htmp[o] = htmp;
+        if (reached) a.p.h[o] = htmp / wij;
+    }
+};
+
 // ---- Godunov SPH (pysph/sph/gas_dynamics/gsph.py, riemann_solver.py) --------------------------------------------
 // GSPHGradients (:61-101): the twelve sums px..pz ux..uz vx..vz wx..wz with DWI, one launch; finish() writes all of
 // them, which is the reference's initialize.  Records [x y z h | p u v w m/rho -].
@@ -2513,7 +2684,7 @@ static bool is_nosrc_kind(int k)
            k == SPH_EQ_ISOTHERMAL_EOS || k == SPH_EQ_SOLID_ISOTHERMAL_EOS || k == SPH_EQ_MONAGHAN_ART_STRESS ||
            k == SPH_EQ_HOOKES_DEVIATORIC_STRESS_RATE || k == SPH_EQ_UPDATE_H_FERRARI || k == SPH_EQ_IDEAL_GAS_EOS ||
            k == SPH_EQ_SCALE_SMOOTHING_LENGTH || k == SPH_EQ_UPDATE_H_FROM_VOLUME || k == SPH_EQ_MPM_UPDATE_GHOST_PROPS ||
-           k == SPH_EQ_GSPH_UPDATE_GHOST_PROPS;
+           k == SPH_EQ_GSPH_UPDATE_GHOST_PROPS || k == SPH_EQ_ADKE_UPDATE_GHOST_PROPS;
 }
 
 static int need_prop(sph_ctx *c, int id, int prop, const char *who)
@@ -2534,12 +2705,13 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     memcpy(a.par, e.par, sizeof a.par);
     for (int &gc : a.gcol) gc = 0;
     const bool writes_h = e.kind == SPH_EQ_UPDATE_H_FERRARI || e.kind == SPH_EQ_SCALE_SMOOTHING_LENGTH || e.kind == SPH_EQ_UPDATE_H_FROM_VOLUME;
-    if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS) {
+    if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS || e.kind == SPH_EQ_ADKE_UPDATE_GHOST_PROPS) {
         const int po = sph_prop_register("orig_idx");
         if (po < 0) return po;
-        SPH_TRY(need_prop(c, e.dest, po, "MPMUpdateGhostProps (orig_idx)"));
-        SPH_TRY(need_prop(c, e.dest, SPH_P, "MPMUpdateGhostProps (p)"));
-        SPH_TRY(need_prop(c, e.dest, SPH_CS, "MPMUpdateGhostProps (cs)"));
+        SPH_TRY(need_prop(c, e.dest, po, "MPMUpdateGhostProps / ADKEUpdateGhostProps (orig_idx)"));
+        SPH_TRY(need_prop(c, e.dest, SPH_P, "MPMUpdateGhostProps / ADKEUpdateGhostProps (p)"));
+        SPH_TRY(need_prop(c, e.dest, SPH_CS, "MPMUpdateGhostProps / ADKEUpdateGhostProps (cs)"));
+        if (e.kind == SPH_EQ_ADKE_UPDATE_GHOST_PROPS) SPH_TRY(need_prop(c, e.dest, SPH_RHO, "ADKEUpdateGhostProps (rho)"));
         a.par[0] = (double)A.n_real;
         a.par[1] = (double)po;
         if (start < A.n_real) start = A.n_real; // nothing to do on the real rows
@@ -2588,7 +2760,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
     for (int k = 0; k < SPH_PROP_COUNT; k++) a.q[k] = A.prop[k];
     a.rho = A.prop[SPH_RHO];
     a.p = A.prop[SPH_P];
-    if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS) a.cs = A.prop[SPH_CS];
+    if (e.kind == SPH_EQ_MPM_UPDATE_GHOST_PROPS || e.kind == SPH_EQ_ADKE_UPDATE_GHOST_PROPS) a.cs = A.prop[SPH_CS];
     a.tflag = nullptr;
     if (e.kind == SPH_EQ_MONAGHAN_ART_STRESS) {
         // "no particle in tension" for the rates kernel: valid when this launch covers every particle of the array
@@ -2609,7 +2781,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
 }
 
 enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP, FAM_GASSD, FAM_MPM,
-              FAM_GSPHGRAD, FAM_GSPH };
+              FAM_GSPHGRAD, FAM_GSPH, FAM_ADKESD, FAM_ADKE, FAM_GASWALL };
 
 static bool is_wcsph_option_kind(int k)
 {
@@ -2633,6 +2805,9 @@ static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false
     case SPH_EQ_MPM_ACCELERATIONS: *flag = F_MPM; return FAM_MPM;
     case SPH_EQ_GSPH_GRADIENTS: *flag = F_GGRAD; return FAM_GSPHGRAD;
     case SPH_EQ_GSPH_ACCELERATION: *flag = F_GSPH; return FAM_GSPH;
+    case SPH_EQ_SUMMATION_DENSITY_ADKE: *flag = F_ASD; return FAM_ADKESD;
+    case SPH_EQ_ADKE_ACCELERATIONS: *flag = F_ADKE; return FAM_ADKE;
+    case SPH_EQ_GASD_WALL_BOUNDARY: *flag = F_GWALL; return FAM_GASWALL;
     default: break;
     }
     if (edac && !elastic) {
@@ -2730,7 +2905,7 @@ static PackPlan pack_plan(int fam)
         p.nr = 6;
         p.na = 2;
         p.props[0] = SPH_M; p.props[1] = SPH_P;
-    } else if (fam == FAM_GASSD) {
+    } else if (fam == FAM_GASSD || fam == FAM_ADKESD) {
         p.nr = 8;
         p.na = 4;
         int pr[4] = {SPH_M, SPH_U, SPH_V, SPH_W};
@@ -2741,6 +2916,11 @@ static PackPlan pack_plan(int fam)
         int pr[12] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_E, SPH_M, sph_prop_register("omega"),
                       sph_prop_register("alpha1"), sph_prop_register("alpha2"), -1};
         for (int k = 0; k < 12; k++) p.props[k] = pr[k];
+    } else if (fam == FAM_ADKE || fam == FAM_GASWALL) { // div: a user property by name (the binders refuse the launch should the slots have run out)
+        p.nr = 14;
+        p.na = 9;
+        int pr[9] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_E, SPH_M, sph_prop_register("div")};
+        for (int k = 0; k < 9; k++) p.props[k] = pr[k];
     } else if (fam == FAM_GSPHGRAD) { // [p u v w m/rho]
         p.nr = 10;
         p.na = 5;
@@ -2856,6 +3036,7 @@ static bool slot_required(int fam, uint32_t flags, int prop)
     }
     if (fam == FAM_AVGP) return prop == SPH_M ? (flags & (F_SD | F_TVFSD)) != 0 : (flags & F_AVGP) != 0;
     if (fam == FAM_GASSD || fam == FAM_MPM || fam == FAM_GSPHGRAD || fam == FAM_GSPH) return true;
+    if (fam == FAM_ADKESD || fam == FAM_ADKE || fam == FAM_GASWALL) return true;
     return false;
 }
 
@@ -4038,6 +4219,126 @@ template <class F> static int run_mpm(const PairLaunch &L)
     return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
 }
 
+// ---- ADKE: what runs around its sweeps ---------------------------------------------------------------------------
+// `h = h0` of SummationDensityADKE.initialize / WallBoundary.initialize over the destinations, BEFORE their records are
+// packed: the sweep then reads the destination's h0 as its h, from the record
+__global__ __launch_bounds__(256) void k_adke_h_reset(double *__restrict__ h, const double *__restrict__ h0, size_t start, size_t stop)
+{
+    const size_t i = start + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < stop) h[i] = h0[i];
+}
+// The sum of a column in a FIXED order: thread t of block b takes rows b * 256 + t, + gridDim * 256, ...; a wavefront
+// folds by xor-shuffles, a block adds its four wavefronts in order, and one further block folds the partial sums the
+// same way.  The grid is a function of n alone, so two runs add in the same order; no floating-point atomics.
+__global__ __launch_bounds__(256) void k_adke_sum(const double *__restrict__ v, size_t n, double *__restrict__ out)
+{
+    double s = 0.0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) s += v[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    __shared__ double sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+// SummationDensityADKE.reduce (:64-71) for every row: h = k (exp(S / n) / rho)^eps h0, S read from the device word
+__global__ __launch_bounds__(256) void k_adke_h(double *__restrict__ h, const double *__restrict__ h0, const double *__restrict__ rho,
+                                                const double *__restrict__ sum, size_t n, double k, double eps)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double g = exp(*sum / (double)n);
+    h[i] = k * pow(g / rho[i], eps) * h0[i];
+}
+
+// h changed behind the neighbour grid (as UpdateSmoothingLengthFerrari in run_nosrc): no pair loop may take "every
+// particle has the h the last update saw" as a launch constant or a record layout, no records packed before and no
+// neighbour lists kept before may be read again
+static void adke_h_written(sph_ctx *c, int id)
+{
+    sph_mark_written(c->arr[id], SPH_H);
+    c->uniform_h = false;
+    c->pack_cache[id].epoch = 0;
+    c->nl.valid = false;
+}
+
+// before the records of a SummationDensityADKE / WallBoundary destination are chosen and packed: h = h0 on the
+// destinations; the wall's output columns exist from here on (its own record is read for x y z h only)
+static int adke_before_records(sph_ctx *c, const DestPlan &P)
+{
+    DevArray &D = c->arr[P.dst];
+    const char *who = P.fam == FAM_GASWALL ? "WallBoundary" : "SummationDensityADKE";
+    if (P.phase != 0) { sph_set_error("%s: not in a split evaluation (sph_group.phase)", who); return SPH_ERR_UNSUPPORTED; }
+    const int ph0 = sph_prop_register("h0");
+    if (ph0 < 0) return ph0;
+    SPH_TRY(need_prop(c, P.dst, ph0, who));
+    SPH_TRY(need_prop(c, P.dst, SPH_H, who));
+    if (P.fam == FAM_GASWALL) {
+        const int pdiv = sph_prop_register("div");
+        if (pdiv < 0) return pdiv;
+        for (int p : {(int)SPH_U, (int)SPH_V, (int)SPH_W, (int)SPH_RHO, (int)SPH_P, (int)SPH_CS, (int)SPH_E, (int)SPH_M, pdiv}) SPH_TRY(sph_array_ensure_prop(c, P.dst, p));
+    }
+    if (P.stop > P.start) {
+        ScopedTimer tm(c, T_EOS);
+        hipLaunchKernelGGL(k_adke_h_reset, dim3(div_up(P.stop - P.start, 256)), dim3(256), 0, c->stream, D.prop[SPH_H], D.prop[ph0], P.start, P.stop);
+    }
+    adke_h_written(c, P.dst);
+    return SPH_OK;
+}
+
+// the ADKE density sweep, then what the reference's reduce hook does, on the device: the sum of logrho over EVERY row of
+// the destination (the rows behind the real ones with whatever logrho they hold, as `serial_reduce_array(dst.logrho)`
+// sums them) into one device word, and the new h of every row from it.  Nothing is read back.
+template <class F> static int run_adke_sd(const PairLaunch &L)
+{
+    sph_ctx *c = L.c;
+    const int dst = L.P.dst;
+    DevArray &D = c->arr[dst];
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *se = L.P.eq_of[SPH_EQ_SUMMATION_DENSITY_ADKE]; // par k eps
+    const int ph0 = sph_prop_register("h0"), pdiv = sph_prop_register("div"), plr = sph_prop_register("logrho");
+    if (ph0 < 0 || pdiv < 0 || plr < 0) return SPH_ERR_ARG;
+    SPH_TRY(bind_out(L, {{SPH_RHO, &a.p.rho}, {SPH_ARHO, &a.p.arho}, {pdiv, &a.p.div}, {plr, &a.p.logrho}}));
+    SPH_TRY(launch_pair<F>(c, L.K->kind, a, L.rl.record_f32));
+    const size_t n = D.n;
+    if (n == 0) return SPH_OK;
+    const int nb = (int)std::min<size_t>(512, div_up(n, 256));
+    SPH_TRY(c->red_part.reserve(1024 * sizeof(double)));
+    double *part = c->red_part.as<double>();
+    {
+        ScopedTimer tm(c, T_EOS);
+        hipLaunchKernelGGL(k_adke_sum, dim3(nb), dim3(256), 0, c->stream, D.prop[plr], n, part);
+        hipLaunchKernelGGL(k_adke_sum, dim3(1), dim3(256), 0, c->stream, part, (size_t)nb, part + 512);
+        hipLaunchKernelGGL(k_adke_h, dim3(div_up(n, 256)), dim3(256), 0, c->stream, D.prop[SPH_H], D.prop[ph0], D.prop[SPH_RHO],
+                           part + 512, n, se->par[0], se->par[1]);
+    }
+    adke_h_written(c, dst);
+    return SPH_OK;
+}
+template <class F> static int run_adke(const PairLaunch &L)
+{
+    typedef typename F::Real T;
+    PairArgs<F> a = pair_args<F>(L);
+    const sph_equation *ae = L.P.eq_of[SPH_EQ_ADKE_ACCELERATIONS]; // par alpha beta g1 g2 k eps
+    a.p.alpha = (T)ae->par[0]; a.p.beta = (T)ae->par[1]; a.p.g1 = (T)ae->par[2]; a.p.g2 = (T)ae->par[3];
+    if (L.rl.pl.props[8] < 0) { sph_set_error("ADKEAccelerations: no user property slot left for div"); return SPH_ERR_ARG; }
+    SPH_TRY(bind_out(L, {{SPH_AU, &a.p.au}, {SPH_AV, &a.p.av}, {SPH_AW, &a.p.aw}, {SPH_AE, &a.p.ae}}));
+    return launch_pair<F>(L.c, L.K->kind, a, L.rl.record_f32);
+}
+// the wall sweep writes h and m of the wall array: both count as written
+template <class F> static int run_gas_wall(const PairLaunch &L)
+{
+    sph_ctx *c = L.c;
+    PairArgs<F> a = pair_args<F>(L);
+    const int pdiv = sph_prop_register("div"), pwij = sph_prop_register("wij"), pht = sph_prop_register("htmp");
+    if (pdiv < 0 || pwij < 0 || pht < 0 || L.rl.pl.props[8] < 0) { sph_set_error("WallBoundary: no user property slot left for div, wij, htmp"); return SPH_ERR_ARG; }
+    SPH_TRY(bind_out(L, {{pwij, &a.p.wij}, {SPH_P, &a.p.p}, {SPH_U, &a.p.u}, {SPH_V, &a.p.v}, {SPH_W, &a.p.w}, {SPH_M, &a.p.m},
+                              {SPH_RHO, &a.p.rho}, {SPH_E, &a.p.e}, {SPH_CS, &a.p.cs}, {pdiv, &a.p.div}, {pht, &a.p.htmp}, {SPH_H, &a.p.h}}));
+    SPH_TRY(launch_pair<F>(c, L.K->kind, a, L.rl.record_f32));
+    adke_h_written(c, L.P.dst);
+    sph_mark_written(c->arr[L.P.dst], SPH_M);
+    return SPH_OK;
+}
+
 template <class F> static int run_gsph_grad(const PairLaunch &L)
 {
     PairArgs<F> a = pair_args<F>(L);
@@ -4107,6 +4408,9 @@ static int launch_family(const PairLaunch &L)
     if (fam == FAM_MPM) RUN(run_mpm, FamMPM_T<T>);
     if (fam == FAM_GSPHGRAD) RUN(run_gsph_grad, FamGSPHGrad_T<T>);
     if (fam == FAM_GSPH) RUN(run_gsph, FamGSPH_T<T>);
+    if (fam == FAM_ADKESD) RUN(run_adke_sd, FamADKESD_T<T>);
+    if (fam == FAM_ADKE) RUN(run_adke, FamADKE_T<T>);
+    if (fam == FAM_GASWALL) RUN(run_gas_wall, FamGasWall_T<T>);
     if (fam == FAM_EDAC && (L.P.dflags & F_EINT)) RUN(run_edac, FamEDAC_T<T, true>);
     if (fam == FAM_EDAC) RUN(run_edac, FamEDAC_T<T, false>);
     if (fam == FAM_VGRAD) RUN(run_vgrad, FamVGrad_T<T>);
@@ -4155,6 +4459,7 @@ extern "C" int sph_eval_group(sph_ctx *c, const sph_kernel *K, const sph_group *
         SPH_TRY(plan_destination(c, g, plan));
         const DestPlan &P = plan;
         if (P.fam == FAM_NONE) continue;
+        if (P.fam == FAM_ADKESD || P.fam == FAM_GASWALL) SPH_TRY(adke_before_records(c, P)); // h = h0: the records and their layout see it
         const RecordLayout rl = choose_records(c, g, P, eos_pending);
         if (eos_pending) { // the Tait EOS the host left to this call: with the records (pack_array), or now, over all of every array
             eos_pending = false;
@@ -4571,6 +4876,9 @@ UNIT_BOTH(UNIT_PAIR, FamGasSD_T);
 UNIT_BOTH(UNIT_PAIR, FamMPM_T);
 UNIT_BOTH(UNIT_PAIR, FamGSPHGrad_T);
 UNIT_BOTH(UNIT_PAIR, FamGSPH_T);
+UNIT_BOTH(UNIT_PAIR, FamADKESD_T);
+UNIT_BOTH(UNIT_PAIR, FamADKE_T);
+UNIT_BOTH(UNIT_PAIR, FamGasWall_T);
 template <class T> using FamEDACInt_T = FamEDAC_T<T, true>;
 template <class T> using FamEDACExt_T = FamEDAC_T<T, false>;
 UNIT_BOTH(UNIT_PAIR, FamEDACInt_T);

@@ -142,6 +142,24 @@ __global__ __launch_bounds__(256) void k_stage(StageArgs a)
             p[SPH_Y][i] = p[SPH_Y][i] + dt * vstar;
             p[SPH_Z][i] = p[SPH_Z][i] + dt * wstar;
         }
+    } else if (a.stepper == SPH_STEP_ADKE) {
+        if (a.stage == 0) { // integrator_step.py:454-467
+            p[SPH_X0][i] = p[SPH_X][i]; p[SPH_Y0][i] = p[SPH_Y][i]; p[SPH_Z0][i] = p[SPH_Z][i];
+            p[SPH_U0][i] = p[SPH_U][i]; p[SPH_V0][i] = p[SPH_V][i]; p[SPH_W0][i] = p[SPH_W][i];
+            p[SPH_E0][i] = p[SPH_E][i];
+            p[SPH_RHO0][i] = p[SPH_RHO][i];
+        } else { // stage1 :470-484 (dt/2), stage2 :486-499 (dt): the positions move with the NEW velocities
+#pragma clang fp contract(off) // every product rounded on its own, as the reference's expressions are
+            const double f = a.stage == 1 ? dtb2 : dt;
+            const double u = p[SPH_U0][i] + f * p[SPH_AU][i];
+            const double v = p[SPH_V0][i] + f * p[SPH_AV][i];
+            const double w = p[SPH_W0][i] + f * p[SPH_AW][i];
+            p[SPH_U][i] = u; p[SPH_V][i] = v; p[SPH_W][i] = w;
+            p[SPH_X][i] = p[SPH_X0][i] + f * u;
+            p[SPH_Y][i] = p[SPH_Y0][i] + f * v;
+            p[SPH_Z][i] = p[SPH_Z0][i] + f * w;
+            p[SPH_E][i] = p[SPH_E0][i] + f * p[SPH_AE][i];
+        }
     }
 }
 
@@ -183,9 +201,14 @@ extern "C" int sph_integrate_stage(sph_ctx *c, int id, int stepper, int stage, d
         memcpy(gd1, b1, sizeof b1);
     }
     static const int gs1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_E, SPH_AU, SPH_AV, SPH_AW, SPH_AE, -1};
+    static const int ad0[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_E, SPH_RHO, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0,
+                              SPH_E0, SPH_RHO0, -1};
+    static const int ad1[] = {SPH_X, SPH_Y, SPH_Z, SPH_U, SPH_V, SPH_W, SPH_E, SPH_X0, SPH_Y0, SPH_Z0, SPH_U0, SPH_V0, SPH_W0, SPH_E0,
+                              SPH_AU, SPH_AV, SPH_AW, SPH_AE, -1};
     const int *need = nullptr;
     if (stepper == SPH_STEP_GASD) need = stage == 0 ? gd0 : gd1;
     else if (stepper == SPH_STEP_GSPH) { if (stage != 1) return SPH_OK; need = gs1; }
+    else if (stepper == SPH_STEP_ADKE) need = stage == 0 ? ad0 : ad1;
     else if (stepper == SPH_STEP_EDAC) need = stage == 0 ? ed0 : ed1;
     else if (stepper == SPH_STEP_EDAC_TVF) need = stage == 0 ? ed0 : et1;
     else if (stepper == SPH_STEP_WCSPH) need = stage == 0 ? wc0 : wc1;

@@ -186,7 +186,9 @@ class HipDomainManager(_DomainBase):
 
     def set_image_props(self, mapping):
         """restrict the images to the properties somebody reads: {array name: property names}, e.g. the `inputs` of the
-        compiled acceleration evaluator; x, y, z, h, m always travel"""
+        compiled acceleration evaluator; x, y, z, h, m always travel.  (Under ``ADKEScheme`` an image needs ``h0``: the
+        reduction behind ``SummationDensityADKE`` writes ``h`` of every row, images included, from its ``h0`` and ``rho``.
+        The evaluator's inputs name it, and without a restriction every device column travels.)"""
         self.image_props = {k: sorted(set(v) | set(('x', 'y', 'z', 'h', 'm'))) for k, v in dict(mapping).items()}
 
     def _props_of(self, helper):

@@ -317,10 +317,15 @@ EQ_MPM_UPDATE_GHOST_PROPS = 39
 EQ_GSPH_GRADIENTS = 40
 EQ_GSPH_UPDATE_GHOST_PROPS = 41
 EQ_GSPH_ACCELERATION = 42
+EQ_SUMMATION_DENSITY_ADKE = 43
+EQ_ADKE_ACCELERATIONS = 44
+EQ_ADKE_UPDATE_GHOST_PROPS = 45
+EQ_GASD_WALL_BOUNDARY = 46
 
 _XV = ('x', 'y', 'z', 'h')
 _GSPH_GRADS = ('px', 'py', 'pz', 'ux', 'uy', 'uz', 'vx', 'vy', 'vz', 'wx', 'wy', 'wz')
 _GSPH_STATE = ('u', 'v', 'w', 'm', 'rho', 'p', 'cs', 'e', 'div', 'grhox', 'grhoy', 'grhoz') + _GSPH_GRADS
+_ADKE_STATE = ('u', 'v', 'w', 'rho', 'p', 'cs', 'e', 'm', 'div')
 EQUATION_TABLE = OrderedDict([
     # name: (kind, params, dest props, source props)
     ('TaitEOS', (EQ_TAIT_EOS, ('rho0', 'c0', 'gamma', 'p0'),
@@ -440,12 +445,25 @@ EQUATION_TABLE = OrderedDict([
         EQ_GSPH_ACCELERATION, ('g1', 'g2', 'monotonicity', 'rsolver', 'interpolation', 'interface_zero', 'hybrid',
                                'blend_alpha', 'tf', 'gamma', 'niter', 'tol'),
         _XV + _GSPH_STATE + ('au', 'av', 'aw', 'ae'), _XV + _GSPH_STATE)),
+    # ADKE (pysph_amd/gas_dynamics.py, pysph/sph/gas_dynamics/basic.py, boundary_equations.py).  SummationDensityADKE and
+    # WallBoundary also write h, WallBoundary m, u, v, w too (acceleration_eval._WRITES_H_KINDS, _WALL_KIND).  WallBoundary
+    # is one of four classes of that name: `resolve_equation` takes the one of boundary_equations / this package.
+    ('SummationDensityADKE', (
+        EQ_SUMMATION_DENSITY_ADKE, ('k', 'eps'),
+        _XV + ('u', 'v', 'w', 'h0', 'rho', 'arho', 'div', 'logrho'), _XV + ('u', 'v', 'w', 'm'))),
+    ('ADKEAccelerations', (
+        EQ_ADKE_ACCELERATIONS, ('alpha', 'beta', 'g1', 'g2', 'k', 'eps'),
+        _XV + _ADKE_STATE + ('au', 'av', 'aw', 'ae'), _XV + _ADKE_STATE)),
+    ('ADKEUpdateGhostProps', (EQ_ADKE_UPDATE_GHOST_PROPS, (), ('p', 'cs', 'rho', 'orig_idx'), ())),
+    ('WallBoundary', (
+        EQ_GASD_WALL_BOUNDARY, (), _XV + ('h0', 'wij', 'htmp') + _ADKE_STATE, _XV + _ADKE_STATE)),
 ])
 
 # equations that have no neighbour loop
 NO_SOURCE_KINDS = (EQ_TAIT_EOS, EQ_TAIT_EOS_HG, EQ_TVF_STATE_EQUATION,
                    EQ_ISOTHERMAL_EOS, 17, 19, 21, EQ_UPDATE_H_FERRARI, EQ_IDEAL_GAS_EOS, EQ_SCALE_SMOOTHING_LENGTH,
-                   EQ_UPDATE_H_FROM_VOLUME, EQ_MPM_UPDATE_GHOST_PROPS, EQ_GSPH_UPDATE_GHOST_PROPS)
+                   EQ_UPDATE_H_FROM_VOLUME, EQ_MPM_UPDATE_GHOST_PROPS, EQ_GSPH_UPDATE_GHOST_PROPS,
+                   EQ_ADKE_UPDATE_GHOST_PROPS)
 
 
 def resolve_equation(eq):
@@ -464,6 +482,12 @@ def resolve_equation(eq):
     if name == 'SummationDensity' and 'gas_dynamics' in type(eq).__module__:
         # the third class of this name (gas_dynamics/basic.py:74), this package's or the reference's
         name = 'GasDSummationDensity'
+    if name == 'WallBoundary':
+        # four classes of the reference carry this name (boundary_equations.py, psph.py, tsph.py, magma2.py): the
+        # hand-written one is boundary_equations' (this package's holder lives in gas_dynamics)
+        mod = type(eq).__module__
+        if not (mod.endswith('boundary_equations') or mod.endswith('pysph_amd.gas_dynamics')):
+            name = mod.rsplit('.', 1)[-1] + '.WallBoundary'
     if name not in EQUATION_TABLE:
         try:   # the elastic family registers itself on import
             from . import solid_mech  # noqa: F401

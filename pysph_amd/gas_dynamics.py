@@ -40,11 +40,21 @@ section 7h):
 * ``GSPHScheme`` gives the reference's group list (including that it does not hand ``tf`` to ``GSPHAcceleration``);
   ``configure_solver`` takes ``tf`` from its keywords as the reference's does.  ``GSPHStep`` lives in
   ``pysph_amd.integrator``.
+
+ADKE (gas_dynamics/basic.py:32-71, :274-353, :500-512, boundary_equations.py, ``ADKEScheme`` of scheme.py:1461-1644;
+DESIGN.md, section 7i):
+
+* ``SummationDensityADKE``, ``ADKEAccelerations``, ``ADKEUpdateGhostProps`` and ``WallBoundary`` are parameter holders:
+  ``FamADKESD_T``, ``FamADKE_T``, a case of ``k_nosrc`` and ``FamGasWall_T``.  The ``reduce`` hook of
+  ``SummationDensityADKE`` is replaced by a device reduction in a fixed order and one element-wise launch behind the
+  sweep: no value crosses to the host.  ``ADKEAccelerations`` drops the ``g2`` it is given, as the reference does;
+* ``ADKEScheme`` gives the reference's group list, ``solids`` included (``GasDScheme`` and ``GSPHScheme`` still refuse
+  them).  ``ADKEStep`` lives in ``pysph_amd.integrator``.
 """
 import numpy as np
 
 from .equations import Equation, Group
-from .integrator import EulerIntegrator, GasDFluidStep, GSPHStep, PECIntegrator
+from .integrator import ADKEStep, EulerIntegrator, GasDFluidStep, GSPHStep, PECIntegrator
 from .particle_array import GASD_PROPS, get_npy, get_particle_array_gasd  # noqa: F401
 
 
@@ -411,3 +421,144 @@ class GSPHScheme(object):
             get_npy(pa, 'orig_idx')[:] = np.arange(pa.get_number_of_particles())
             pa.set_output_arrays(['x', 'y', 'u', 'v', 'rho', 'm', 'h', 'cs', 'p', 'e', 'au', 'av', 'ae', 'pid', 'gid',
                                   'tag', 'dwdh', 'alpha1', 'alpha2'])
+
+
+# -- ADKE (pysph/sph/gas_dynamics/basic.py:32-71, :274-353, :500-512; boundary_equations.py; scheme.py:1461-1644) -------
+ADKE_PROPS = ('x', 'y', 'z', 'u', 'v', 'w', 'rho', 'h', 'm', 'cs', 'p', 'e', 'au', 'av', 'aw', 'arho', 'ae', 'am', 'ah',
+              'x0', 'y0', 'z0', 'u0', 'v0', 'w0', 'rho0', 'e0', 'h0', 'div', 'wij', 'htmp', 'logrho')
+
+
+class SummationDensityADKE(Equation):
+    """gas_dynamics/basic.py:32-71: the pilot density with ``h = h0``, ``div`` and ``logrho``; the ``reduce`` of the
+    reference -- ``h = k (exp(mean logrho) / rho)^eps h0`` over every row -- runs on the device behind the sweep, so
+    this holder has no ``reduce`` method (a reference object's is not called either)."""
+
+    def __init__(self, dest, sources, k=1.0, eps=0.0):
+        self.k = k
+        self.eps = eps
+        super(SummationDensityADKE, self).__init__(dest, sources)
+
+
+class ADKEAccelerations(Equation):
+    """gas_dynamics/basic.py:274-353.  As the reference's constructor does (:287-288), ``g2`` becomes ``g1``: the value
+    given for ``g2`` is dropped."""
+
+    def __init__(self, dest, sources, alpha, beta, g1, g2, k, eps):
+        self.alpha = alpha
+        self.g1 = g1
+        self.g2 = g1
+        self.alpha = alpha
+        self.beta = beta
+        self.k = k
+        self.eps = eps
+        super(ADKEAccelerations, self).__init__(dest, sources)
+
+
+class ADKEUpdateGhostProps(Equation):
+    """gas_dynamics/basic.py:500-512: ``p``, ``cs`` and ``rho`` of an image row from the row it mirrors."""
+
+    def __init__(self, dest, sources=None, dim=2):
+        super(ADKEUpdateGhostProps, self).__init__(dest, sources)
+        self.dim = dim
+
+
+class WallBoundary(Equation):
+    """gas_dynamics/boundary_equations.py:5-48: a wall row takes the kernel average of the fluid's
+    ``p, -u, -v, -w, m, rho, e, cs, div, h`` at its own ``h0``; a row no fluid particle reaches keeps the raw (zero)
+    sums and ``h = h0``."""
+
+
+class ADKEScheme(object):
+    """scheme.py:1461-1644."""
+
+    def __init__(self, fluids, solids, dim, gamma=1.4, alpha=1.0, beta=2.0,
+                 k=1.0, eps=0.0, g1=0, g2=0, has_ghosts=False):
+        self.fluids = list(fluids)
+        self.solids = list(solids)
+        self.dim = dim
+        self.solver = None
+        self.integrator = None
+        self.kernel = None
+        self.gamma = gamma
+        self.alpha = alpha
+        self.beta = beta
+        self.k = k
+        self.eps = eps
+        self.g1 = g1
+        self.g2 = g2
+        self.has_ghosts = has_ghosts
+
+    def configure(self, **kw):
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise RuntimeError('Parameter %s not defined for %s.' % (k, type(self).__name__))
+            setattr(self, k, v)
+
+    def get_equations(self):
+        """:1504-1572, group for group."""
+        from .equations import SummationDensity as BasicSummationDensity
+        all_pa = self.fluids + self.solids
+        equations = []
+
+        def wall_group():
+            return Group(equations=[WallBoundary(solid, sources=self.fluids) for solid in self.solids])
+        if self.solids:
+            equations.append(wall_group())
+        equations.append(Group(
+            equations=[SummationDensityADKE(fluid, sources=all_pa, k=self.k, eps=self.eps) for fluid in self.fluids],
+            update_nnps=False, iterate=False))
+        if self.solids:
+            equations.append(wall_group())
+        equations.append(Group(equations=[BasicSummationDensity(fluid, all_pa) for fluid in self.fluids],
+                               update_nnps=True))
+        if self.solids:
+            equations.append(wall_group())
+        equations.append(Group(equations=[IdealGasEOS(elem, sources=None, gamma=self.gamma) for elem in all_pa]))
+        if self.has_ghosts:
+            equations.append(Group(equations=[ADKEUpdateGhostProps(dest=fluid, sources=None) for fluid in self.fluids],
+                                   real=False))
+        equations.append(Group(equations=[
+            ADKEAccelerations(dest=fluid, sources=all_pa, alpha=self.alpha, beta=self.beta, g1=self.g1, g2=self.g2,
+                              k=self.k, eps=self.eps) for fluid in self.fluids]))
+        return equations
+
+    def configure_solver(self, kernel=None, integrator_cls=None,
+                         extra_steppers=None, **kw):
+        """:1574-1612: the kernel (Gaussian by default), one ``ADKEStep`` per fluid, a PEC integrator unless another
+        class is given.  The integrator is kept in ``self.integrator`` (this package has no ``Solver``;
+        ``integrator.setup_integrator`` installs it)."""
+        from .kernels import Gaussian
+        if kernel is None:
+            kernel = Gaussian(dim=self.dim)
+        steppers = {}
+        if extra_steppers is not None:
+            steppers.update(extra_steppers)
+        cls = integrator_cls if integrator_cls is not None else PECIntegrator
+        for name in self.fluids:
+            if name not in steppers:
+                steppers[name] = ADKEStep()
+        self.kernel = kernel
+        self.integrator = cls(**steppers)
+        self.solver_args = dict(kw)
+        return self.integrator
+
+    def get_integrator(self):
+        if self.integrator is None:
+            self.configure_solver()
+        return self.integrator
+
+    def setup_properties(self, particles, clean=True):
+        """:1614-1644 (properties are added; none is removed)."""
+        arrays = dict((pa.name, pa) for pa in particles)
+        out = ['x', 'y', 'u', 'v', 'rho', 'm', 'h', 'cs', 'p', 'e', 'au', 'av', 'ae', 'pid', 'gid', 'tag']
+        for name in self.solids + self.fluids:
+            pa = arrays[name]
+            for p in ADKE_PROPS:
+                if p not in pa.properties:
+                    pa.add_property(p)
+            pa.set_output_arrays(out)
+        for fluid in self.fluids:
+            pa = arrays[fluid]
+            if 'orig_idx' not in pa.properties:
+                pa.add_property('orig_idx', type='int')
+            get_npy(pa, 'orig_idx')[:] = np.arange(pa.get_number_of_particles())

@@ -82,11 +82,20 @@ class GSPHStep(IntegratorStep):
     _kind = STEP_GSPH
 
 
+STEP_ADKE = 10
+
+
+class ADKEStep(IntegratorStep):
+    """integrator_step.py:452-499: predictor-corrector for ADKE gas dynamics on ``x, u, e``; the positions move with
+    the velocities just updated; ``initialize`` also keeps ``rho`` in ``rho0``, which no stage reads."""
+    _kind = STEP_ADKE
+
+
 # (the two rigid-body steppers are classes of pysph_amd.rigid_body; their stages need the array's body state)
 _STEP_KINDS = {'WCSPHStep': STEP_WCSPH, 'TransportVelocityStep': STEP_TVF,
                'RK2StepRigidBody': STEP_RIGID_RK2, 'EulerStepRigidBody': STEP_RIGID_EULER,
                'EDACStep': STEP_EDAC, 'EDACTVFStep': STEP_EDAC_TVF, 'GasDFluidStep': STEP_GASD,
-               'GSPHStep': STEP_GSPH}
+               'GSPHStep': STEP_GSPH, 'ADKEStep': STEP_ADKE}
 
 
 def stepper_kind(step):
