@@ -104,6 +104,10 @@ template <> struct SphKernel<3> { // QuinticSpline
     }
     template <bool INSUP = false, class R> static __device__ __forceinline__ R dw(R q, int = 0)
     {
+        // No fma contraction here: towards q = 0 the three terms cancel (-405 + 480 - 75) and the result is the
+        // rounding of the products; with the reference's own roundings (kernels.py:1137-1151) it is the reference's
+        // value bit for bit, like w above (tests/test_edac_pair_edges.py, a partner at 2^-39)
+#pragma clang fp contract(off)
         R t3 = R(3) - q, t2 = raw_max(R(2) - q, R(0)), t1 = raw_max(R(1) - q, R(0));
         R v = R(-5) * t3 * t3 * t3 * t3;
         v += R(30) * t2 * t2 * t2 * t2;
