@@ -266,2364 +266,13 @@ __global__ __launch_bounds__(256) void k_nosrc(EosArgs a)
 #endif // SPH_PRIMARY_UNIT
 
 // ---------------------------------------------------------------------------
-// equation families
+// equation families, then the packer of their records (it names the record sizes the families' loaders export)
 // ---------------------------------------------------------------------------
-enum { F_VG2 = 1, F_VG3 = 2,                                            // velocity gradient
-       F_ECONT = 1, F_ESTRESS = 2, F_EAV = 4, F_EXSPH = 8 };            // elastic rates
-enum { F_DCONT = 16, F_DMOM = 32, F_LAM = 64, F_LAMD = 128,             // WCSPH options (next to the WCSPH flags below)
-       F_MOMENT = 1, F_GRADRHO = 2, F_GCORR = 4 };                      // delta-SPH pre-passes
-enum { F_CONT = 1, F_MOM = 2, F_XSPH = 4, F_TENSILE = 8,               // WCSPH
-       F_SD = 1, F_TVFSD = 2,                                           // density
-       F_TP = 1, F_TVISC = 2, F_TAV = 4, F_TAS = 8 };                   // TVF force
-
-#define MAX_AUX 24
-struct PackArgs {
-    const uint32_t *perm;
-    size_t n;
-    size_t off;
-    const double *x, *y, *z, *h;
-    int na;                       // doubles in the aux record
-    const double *src[MAX_AUX];   // nullptr -> 0.0
-    int derived;                  // 1: aux[5] = p/(rho*rho) (p = aux[7], rho = aux[4]); 2: aux[10] = 1/V^2 (V = aux[8]);
-                                  // 3: aux[6..11] = (s_ij - p delta_ij)/rho^2 (p = aux[18], rho = aux[4])
-                                  // 4: aux[3] = m/rho (m = aux[3], rho = aux[4]; aux[4] itself is not stored)
-                                  // 5: aux[0] = the particle's original index (neighbour lists)
-                                  // 6: aux[15..20] = ux, uy+vx, uz+wx, vy, vz+wy, wz from the nine velocity gradients
-                                  //    aux[15..23] (GSPHAcceleration reads them through eij . G . eij only)
-                                  // 7: aux[4] = m/rho (m = aux[4], rho = aux[5]; aux[5] itself is not stored)
-    double4 *posh;
-    double *aux;
-    double *rec;                  // non-null: interleaved records [x y z h aux... pad], nr doubles each
-    int nr;
-    int layout;                   // 0: [x y z h | aux...]; 1: WCSPH [x y z cs | u v w m | rho tmpj | h p]; 2: density [x y z m];
-                                  // 3: TVF [x y z rho | u v w p | Vj2 m uhat vhat | what -];
-                                  // 4: generated, uniform h [x y z | aux...]; 5: fp32 records (floats, any family)
-                                  // 6: WCSPH, p and cs recomputed by the pair kernel [x y | z u | v w | rho m] (64 B);
-                                  // 7: the same in fp32 [x-x0 y-y0 z-z0 u | v w rho m] (32 B)
-                                  // 8 / 9: TVF, p and V recomputed from rho (fp64 80 B / fp32 48 B)
-                                  // 10 / 11: elastic rates without h and m (fp64 160 B / fp32 80 B)
-                                  // 12 / 13: WCSPH with variable h, one mass per array, EOS recomputed (64 B / 32 B)
-                                  // (1, 2: aggregated kernel only)
-    int umass;                    // layouts 6 / 7: the last slot carries p / rho^2 (derived 1) instead of m
-    float4 *fpos;                 // non-null: fp32 {x-xmin, y-ymin, z-zmin, radius_scale*h} for the prefilter tiles
-    int lds_np;                   // 16-B pieces per record when the launch carries 256 * lds_np * 16 B of LDS, else 0
-    double gmin[3];
-    double radius_scale;
-    double hu;                    // h == nullptr: the one h of every particle (uniform h, layouts 6 / 7: the record holds none)
-    int eos_abs;                  // layouts 6 / 7 / 12 / 13: the Tait EOS of the group before has NOT run (sph_group.src_eos = 3):
-                                  // p and cs are computed here from the rho just loaded, stored, and p / rho^2 formed from that p
-    double eos_par[4];            // rho0 c0 gamma p0
-    double *p_out, *cs_out;
-};
-
-#define PACK_MAXP ((4 + MAX_AUX) / 2) // 16-B pieces of the widest record
-
-// Store one record of `np` 16-B pieces per lane.  The 64 records of a wavefront are contiguous in
-// the packed buffer: a whole block transposes them through (dynamic) LDS so that each store
-// instruction writes 1 KiB of whole lines instead of 64 pieces a record apart (k_pack 0.29 -> 0.22 ms
-// on the 4 M cube); the ragged last block, and launches without LDS, store per lane.
-template <class PA>
-__device__ __forceinline__ void emit_pieces(const PA &a, size_t i, const double2 (&pc)[PACK_MAXP], int np)
-{
-    extern __shared__ __attribute__((aligned(16))) double2 pack_lds[];
-    double2 *const base = reinterpret_cast<double2 *>(a.rec);
-    if (a.lds_np == np && ((size_t)blockIdx.x + 1) * 256 <= a.n) {
-        const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-        double2 *const sw = pack_lds + (size_t)w * 64 * np;
-#pragma unroll
-        for (int q = 0; q < PACK_MAXP; q++)
-            if (q < np) sw[l * np + q] = pc[q];
-        // private to the wavefront: program order is execution order, the fence is for the compiler
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        double2 *const ow = base + (a.off + (size_t)blockIdx.x * 256 + (size_t)w * 64) * np;
-#pragma unroll
-        for (int q = 0; q < PACK_MAXP; q++)
-            if (q < np) ow[q * 64 + l] = sw[q * 64 + l];
-    } else {
-        double2 *const r2 = base + (a.off + i) * np;
-#pragma unroll
-        for (int q = 0; q < PACK_MAXP; q++)
-            if (q < np) r2[q] = pc[q];
-    }
-}
-
-// LAYOUT >= 0: the record layout as a compile-time constant (the hot layouts of the hand-written families: the layout
-// switch folds away, the piece count is a constant, and the record never passes through a dynamically indexed local array
-// -- the one-kernel-for-all form kept 32 B per lane in scratch); -1: PackArgs::layout at run time (every other layout).
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_pack(PackArgs a)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    uint32_t o = a.perm[i];
-    const int layout = LAYOUT >= 0 ? LAYOUT : a.layout;
-    double4 ph;
-    ph.x = a.x[o]; ph.y = a.y[o]; ph.z = a.z[o]; ph.w = a.h ? a.h[o] : a.hu;
-    double v[MAX_AUX];
-    // (compile-time layouts read the slots their record holds: WCSPH u v w m rho tmpj cs p = 0..7, elastic 0..17 + p)
-    constexpr int NV = (LAYOUT == 6 || LAYOUT == 7 || LAYOUT == 12 || LAYOUT == 13) ? 8 : (LAYOUT == 2 ? 1 : (LAYOUT == 3 || LAYOUT == 8 || LAYOUT == 9) ? 11 : MAX_AUX);
-#pragma unroll
-    for (int k = 0; k < MAX_AUX; k++) v[k] = (k < NV && (k < a.na || (a.derived == 3 && k == 18) || (a.derived == 4 && k == 4) || (a.derived == 6 && k < 24) || (a.derived == 7 && k == 5)) && a.src[k]) ? a.src[k][o] : 0.0;
-    if constexpr (LAYOUT == 6 || LAYOUT == 7 || LAYOUT == 12 || LAYOUT == 13) {
-        if (a.eos_abs) { // the Tait EOS of this particle, as k_nosrc would have left it (p is not read: a.src[7] is null)
-            double p, cs;
-            tait_eos(v[4], a.eos_par[0], a.eos_par[1], a.eos_par[2], a.eos_par[3], p, cs);
-            a.p_out[o] = p;
-            a.cs_out[o] = cs;
-            v[7] = p;
-        }
-    }
-    if (a.derived == 1) v[5] = v[4] != 0.0 ? v[7] * (1.0 / (v[4] * v[4])) : 0.0; // tmpj = p*rhoj21, wc/basic.py:211,234
-    if (a.derived == 2) { double Vj = 1. / v[8]; v[10] = Vj * Vj; } // Vj2, transport_velocity.py:303-306
-    if (a.derived == 4) v[3] = v[3] / v[4]; // m/rho, basic_equations.py:103,139 (VelocityGradient tmp)
-    if (a.derived == 5) v[0] = (double)o;
-    if (a.derived == 7) { v[4] = v[4] / v[5]; v[5] = 0.0; } // m/rho, gsph.py:81,86 (GSPHGradients)
-    if (a.derived == 6) { // gsph.py:269-284: the symmetric sums of the velocity gradient
-        const double uy = v[16], uz = v[17], vx = v[18], vy = v[19], vz = v[20], wx = v[21], wy = v[22], wz = v[23];
-        v[16] = uy + vx; v[17] = uz + wx; v[18] = vy; v[19] = vz + wy; v[20] = wz;
-        v[21] = v[22] = v[23] = 0.0;
-    }
-    if (a.derived == 3) { // (sigma_ij)/rho^2 with sigma = s - p I: solid_mech/basic.py:281-283,333-339,367-378
-        const double r21 = 1. / (v[4] * v[4]), pr = v[18];
-        v[6] = (v[6] - pr) * r21; v[7] *= r21; v[8] *= r21;
-        v[9] = (v[9] - pr) * r21; v[10] *= r21; v[11] = (v[11] - pr) * r21;
-        v[18] = 0.0;
-    }
-    if (a.fpos)
-        a.fpos[a.off + i] = make_float4((float)(ph.x - a.gmin[0]), (float)(ph.y - a.gmin[1]), (float)(ph.z - a.gmin[2]),
-                                        (float)(a.radius_scale * ph.w));
-    if (a.rec) {
-        // the record as 16-B pieces, then ONE way out (emit_pieces): the records of a wavefront
-        // are contiguous, so they leave transposed through LDS as whole lines
-        double2 pc[PACK_MAXP];
-#pragma unroll
-        for (int q = 0; q < PACK_MAXP; q++) pc[q] = make_double2(0.0, 0.0);
-        int np;
-        if (layout == 6) { // WCSPH with the EOS fused into the pair kernel: one 64-B half line per record
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, v[0]);
-            pc[2] = make_double2(v[1], v[2]); pc[3] = make_double2(v[4], a.umass ? v[5] : v[3]); // [rho m], uniform mass: [rho p/rho^2]
-            np = 4;
-        } else if (layout == 7) {
-            pc[0] = __builtin_bit_cast(double2, make_float4((float)(ph.x - a.gmin[0]), (float)(ph.y - a.gmin[1]),
-                                                            (float)(ph.z - a.gmin[2]), (float)v[0]));
-            pc[1] = __builtin_bit_cast(double2, make_float4((float)v[1], (float)v[2], (float)v[4], (float)(a.umass ? v[5] : v[3])));
-            np = 2;
-        } else if (layout == 8) { // TVF with the state equation fused: [x y | z rho | u v | w uhat | vhat what] (no artificial stress: 4 pieces)
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, v[6]);
-            pc[2] = make_double2(v[0], v[1]); pc[3] = make_double2(v[2], v[3]);
-            pc[4] = make_double2(v[4], v[5]);
-            np = a.nr / 2;
-        } else if (layout == 9) { // the same in fp32: [x-x0 y-y0 z-z0 rho | u v w uhat | vhat what - -]
-            pc[0] = __builtin_bit_cast(double2, make_float4((float)(ph.x - a.gmin[0]), (float)(ph.y - a.gmin[1]),
-                                                            (float)(ph.z - a.gmin[2]), (float)v[6]));
-            pc[1] = __builtin_bit_cast(double2, make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]));
-            pc[2] = __builtin_bit_cast(double2, make_float4((float)v[4], (float)v[5], 0.f, 0.f));
-            np = a.nr / 4;
-        } else if (layout == 12) { // WCSPH, variable h, one mass, EOS recomputed: [x y | z h | u v | w rho]
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, ph.w);
-            pc[2] = make_double2(v[0], v[1]); pc[3] = make_double2(v[2], v[4]);
-            np = 4;
-        } else if (layout == 13) { // the same in fp32: [x y z h | u v w rho]
-            pc[0] = __builtin_bit_cast(double2, make_float4((float)(ph.x - a.gmin[0]), (float)(ph.y - a.gmin[1]),
-                                                            (float)(ph.z - a.gmin[2]), (float)ph.w));
-            pc[1] = __builtin_bit_cast(double2, make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[4]));
-            np = 2;
-        } else if (layout == 10) { // elastic, uniform h and mass: [x y | z u | v w | rho cs | t x6 | r x6]
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, v[0]);
-            pc[2] = make_double2(v[1], v[2]); pc[3] = make_double2(v[4], v[5]);
-#pragma unroll
-            for (int q = 0; q < 6; q++) pc[4 + q] = make_double2(v[6 + 2 * q], v[7 + 2 * q]);
-            np = 10;
-        } else if (layout == 11) { // the same in fp32: [x y z u | v w rho cs | t t t t | t t r r | r r r r]
-            pc[0] = __builtin_bit_cast(double2, make_float4((float)(ph.x - a.gmin[0]), (float)(ph.y - a.gmin[1]),
-                                                            (float)(ph.z - a.gmin[2]), (float)v[0]));
-            pc[1] = __builtin_bit_cast(double2, make_float4((float)v[1], (float)v[2], (float)v[4], (float)v[5]));
-#pragma unroll
-            for (int q = 0; q < 3; q++)
-                pc[2 + q] = __builtin_bit_cast(double2, make_float4((float)v[6 + 4 * q], (float)v[7 + 4 * q], (float)v[8 + 4 * q], (float)v[9 + 4 * q]));
-            np = 5;
-        } else if (layout == 1) { // WCSPH [x y | z cs | u v | w m | rho tmpj] (+ [h p]: variable h / tensile correction)
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, v[6]);
-            pc[2] = make_double2(v[0], v[1]); pc[3] = make_double2(v[2], v[3]);
-            pc[4] = make_double2(v[4], v[5]); pc[5] = make_double2(ph.w, v[7]);
-            np = a.nr / 2;
-        } else if (layout == 5) { // fp32 records [x-x0 y-y0 z-z0 h | aux...] (option record_f32), a.nr floats
-            float w[4 + MAX_AUX];
-            w[0] = (float)(ph.x - a.gmin[0]); w[1] = (float)(ph.y - a.gmin[1]); w[2] = (float)(ph.z - a.gmin[2]);
-            w[3] = (float)ph.w;
-#pragma unroll
-            for (int k = 0; k < MAX_AUX; k++) w[4 + k] = k < a.na ? (float)v[k] : 0.f;
-#pragma unroll
-            for (int q = 0; q < (4 + MAX_AUX) / 4; q++)
-                pc[q] = __builtin_bit_cast(double2, make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]));
-            np = a.nr / 4;
-        } else if (layout == 4) { // generated families under uniform h: [x y z | aux...] (h is a launch constant)
-            double w[3 + MAX_AUX + 1];
-            w[0] = ph.x; w[1] = ph.y; w[2] = ph.z;
-#pragma unroll
-            for (int k = 0; k < MAX_AUX + 1; k++) w[3 + k] = k < a.na ? v[k < MAX_AUX ? k : 0] : 0.0;
-#pragma unroll
-            for (int q = 0; q < (3 + MAX_AUX + 1) / 2; q++) pc[q] = make_double2(w[2 * q], w[2 * q + 1]);
-            np = (a.nr + 1) / 2;
-        } else if (layout == 3) { // TVF under uniform h: [x y | z rho | u v | w p | Vj2 what | uhat vhat] (+ [m -] with artificial viscosity)
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, v[6]);
-            pc[2] = make_double2(v[0], v[1]); pc[3] = make_double2(v[2], v[7]);
-            pc[4] = make_double2(v[10], v[5]); pc[5] = make_double2(v[3], v[4]);
-            pc[6] = make_double2(v[9], 0.0);
-            np = a.nr > 12 ? 7 : 6;
-        } else if (layout == 2) { // compact density records [x y z m] (uniform h)
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, v[0]);
-            np = 2;
-        } else { // [x y z h | aux...]
-            pc[0] = make_double2(ph.x, ph.y); pc[1] = make_double2(ph.z, ph.w);
-#pragma unroll
-            for (int q = 0; q < MAX_AUX / 2; q++) pc[2 + q] = make_double2(v[2 * q], v[2 * q + 1]);
-            np = a.nr / 2;
-        }
-        emit_pieces(a, i, pc, np);
-    } else {
-        a.posh[a.off + i] = ph;
-        double *dst = a.aux + (a.off + i) * (size_t)a.na;
-#pragma unroll
-        for (int k = 0; k < MAX_AUX; k++) if (k < a.na) dst[k] = v[k];
-    }
-}
-
-// Records of the MERGED order (FamWCSPHM_T): thread p packs the particle at merged position p -- array slot[p], original
-// index perm[p] -- from ITS array's properties (pointer tables read per lane from the kernarg segment) into
-// [x y | z u | v w | +-rho p/rho^2] (fp32: [x-x0 y-y0 z-z0 u | v w +-rho p/rho^2]); the sign of rho is the array's class.
-// One launch for all arrays; consecutive merged positions are consecutive records, so whole blocks leave through LDS
-// as full lines like k_pack's.
-struct PackMArgs {
-    const uint32_t *perm;
-    const uint8_t *slot;
-    size_t n, off;                 // off = 0 (emit_pieces)
-    const double *prop[9][SPH_MAX_ARRAYS]; // x y z u v w rho p h, per slot (h: variable-h records only)
-    int vh;                        // 1: variable h -- records [x y | z h | u v | w +-rho], p / rho^2 recomputed by the pair kernel
-    uint32_t cls;                  // bit s: slot s is a class-1 array
-    double *rec;
-    float4 *fpos;
-    int f32, lds_np;
-    double gmin[3];
-    double hr;                     // radius_scale * h (uniform h)
-    uint32_t *rho_flag;            // device word: set to 1 when a density is not positive (the class bit is the SIGN of rho)
-};
-
-// (F32, VH: PackMArgs::f32 / vh as compile-time constants -- the piece count of the record is then one too)
-template <bool F32, bool VH>
-__global__ __launch_bounds__(256) void k_pack_merged(PackMArgs a)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n) return;
-    const uint32_t o = a.perm[i], sl = a.slot[i];
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const double *p = kernarg_read<const double *>(__builtin_offsetof(PackMArgs, prop) + ((size_t)k * SPH_MAX_ARRAYS + sl) * sizeof(double *));
-        v[k] = p[o];
-    }
-    const double rho = v[6];
-    const double q = rho != 0.0 ? v[7] * (1.0 / (rho * rho)) : 0.0; // tmpj = p*rhoj21, wc/basic.py:211,234 (as k_pack, derived 1)
-    const double srho = ((a.cls >> sl) & 1u) ? -rho : rho;
-    // rho <= 0 (or NaN): this record's class bit is not to be trusted (padding rows of sph_halo_append_padded, parked far
-    // outside the domain with rho = 0, are nobody's neighbour)
-    if (!(rho > 0.0) && fabs(v[0]) < SPH_PARKED_MIN) atomicOr(a.rho_flag, 1u);
-    double hp = 0.0;
-    if (VH) hp = kernarg_read<const double *>(__builtin_offsetof(PackMArgs, prop) + ((size_t)8 * SPH_MAX_ARRAYS + sl) * sizeof(double *))[o];
-    a.fpos[i] = make_float4((float)(v[0] - a.gmin[0]), (float)(v[1] - a.gmin[1]), (float)(v[2] - a.gmin[2]),
-                            VH ? (float)(a.hr * hp) : (float)a.hr); // hr: radius_scale * h, or radius_scale alone with variable h
-    double2 pc[PACK_MAXP];
-#pragma unroll
-    for (int k = 0; k < PACK_MAXP; k++) pc[k] = make_double2(0.0, 0.0);
-    int np;
-    if (VH && F32) {
-        pc[0] = __builtin_bit_cast(double2, make_float4((float)(v[0] - a.gmin[0]), (float)(v[1] - a.gmin[1]), (float)(v[2] - a.gmin[2]), (float)hp));
-        pc[1] = __builtin_bit_cast(double2, make_float4((float)v[3], (float)v[4], (float)v[5], (float)srho));
-        np = 2;
-    } else if (VH) {
-        pc[0] = make_double2(v[0], v[1]); pc[1] = make_double2(v[2], hp);
-        pc[2] = make_double2(v[3], v[4]); pc[3] = make_double2(v[5], srho);
-        np = 4;
-    } else if (F32) {
-        pc[0] = __builtin_bit_cast(double2, make_float4((float)(v[0] - a.gmin[0]), (float)(v[1] - a.gmin[1]), (float)(v[2] - a.gmin[2]), (float)v[3]));
-        pc[1] = __builtin_bit_cast(double2, make_float4((float)v[4], (float)v[5], (float)srho, (float)q));
-        np = 2;
-    } else {
-        pc[0] = make_double2(v[0], v[1]); pc[1] = make_double2(v[2], v[3]);
-        pc[2] = make_double2(v[4], v[5]); pc[3] = make_double2(srho, q);
-        np = 4;
-    }
-    emit_pieces(a, i, pc, np);
-}
-
-template <class T> struct FamWCSPH_T {
-    typedef T Real; // arithmetic type of the pair loop
-    static constexpr uint32_t CF0 = F_CONT | F_MOM | F_XSPH; // flag set compiled as a constant (variant 6)
-#ifndef SPH_WCSPH_MINB
-#define SPH_WCSPH_MINB 4
-#endif
-    static constexpr int MINB = SPH_WCSPH_MINB; // wavefronts per SIMD the pair kernel is compiled for (VGPR budget)
-    static constexpr int NA = 8; // u v w m rho tmpj(=p/rho^2) cs p
-    static constexpr int NR = 12; // x y z h + NA (128-B padded records measured slower: larger L2 footprint)
-    struct Params {
-        T c0, alpha, beta, gx, gy, gz, eps;
-        double *arho, *au, *av, *aw, *ax, *ay, *az, *dt_cfl, *dt_force;
-    };
-    struct Dest {
-        T u, v, w, rho, p, cs, tmpi;
-        T arho, au, av, aw, ax, ay, az, dt_cfl;
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[4]; D.tmpi = a[5]; D.cs = a[6]; D.p = a[7];
-        D.arho = D.au = D.av = D.aw = D.ax = D.ay = D.az = T(0.0);
-        D.dt_cfl = T(-1.0); // running max of |h v.x / r2| over the pairs; -1: none yet (finish)
-    }
-    // The algebra below is the reference's (cited per term) regrouped so that a
-    // pair costs one rsqrt and one reciprocal:  DWIJ = tg*XIJ  =>
-    //   DWIJ.VIJ = tg*(XIJ.VIJ),   f*DWIJ = (f*tg)*XIJ,
-    //   1/(R2IJ+EPS) and 1/RHOIJ from one reciprocal of their product,
-    //   1/R2IJ = rinv^2.
-    // PRED: the lean kernel calls pair() for every lane of every iteration and
-    // passes the neighbour criterion as `pass`; a pair that fails contributes
-    // exactly zero because every term carries the factor m_j (set to 0) -- no
-    // branch around the accumulators, which then stay in their registers.
-    static constexpr bool PRED = true;
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        // (one transcendental per pair where the momentum equation acts: pair_geom_mom)
-        constexpr bool MRG = SPH_MERGED_RSQ && sizeof(T) == 8 && !SphKernel<KK>::CUTOFF;
-        T tt_m = T(0.0);
-        if constexpr (MRG) {
-            if (fl & F_MOM) tt_m = pair_geom_mom<KK, UH>(g, pi, pj, r2, T(0.5) * (D.rho + s[4]), a);
-            else pair_geom<KK, UH>(g, pi, pj, r2, a);
-        } else {
-            pair_geom<KK, UH>(g, pi, pj, r2, a);
-        }
-        const T tg = pair_gradfac<KK, UH>(g);
-        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2]; // VIJ equation.py:214-223
-        const T vdotx = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
-        const T mj = pass ? s[3] : T(0.0);
-        if (fl & F_CONT) D.arho = fma(mj * tg, vdotx, D.arho); // basic_equations.py:187-192
-        if (fl & (F_MOM | F_XSPH)) {
-            const T rhoij = T(0.5) * (D.rho + s[4]); // RHOIJ equation.py:196
-            T rhoij1;                              // RHOIJ1 :199
-            T wij = T(0.0);
-            if (fl & (F_XSPH | F_TENSILE)) wij = pair_w<KK, UH>(g);
-            if (fl & F_MOM) { // wc/basic.py:204-259
-                const T re = r2 + g.eps;
-                const T tt = MRG ? tt_m : fast_rcp(re * rhoij);
-                const T inv_re = rhoij * tt;
-                rhoij1 = re * tt;
-                const T hv = g.hij * vdotx;
-                // the viscosity acts for approaching pairs only (vdotx < 0; h > 0): muij from min(hv, 0) is exactly
-                // zero otherwise and takes piij with it
-                const T muij = raw_min(hv, T(0.0)) * inv_re;
-                const T cij = T(0.5) * (D.cs + s[6]);
-                const T piij = (a.p.beta * muij - a.p.alpha * cij) * muij * rhoij1;
-                // dt_cfl = max_j (|h v.x / r2| + c0) = max_j |h v.x / r2| + c0 (rounding is monotonic): the running
-                // maximum starts at -1 (no pair yet), finish() adds c0 once
-                const T dtv = fabs(hv * (g.rinv * g.rinv));
-                D.dt_cfl = raw_max(D.dt_cfl, (r2 > T(1e-12) && pass) ? dtv : T(-1.0));
-                const T tmpj = s[5];
-                T tmp = D.tmpi + tmpj;
-                if (fl & F_TENSILE) {
-                    // WDP = KERNEL(XIJ, DELTAP*HIJ, HIJ)  equation.py:243-246
-                    const T qd = (a.k.deltap * g.hij) * g.h1;
-                    const T wdp = SphKernel<KK>::w(qd, g.dim) * g.fac;
-                    T fij = wij * fast_rcp(wdp);
-                    fij = fij * fij;
-                    fij = fij * fij;
-                    const T Ri = D.p > 0 ? T(0.01) * D.tmpi : T(0.2) * fabs(D.tmpi);
-                    const T Rj = s[7] > 0 ? T(0.01) * tmpj : T(0.2) * fabs(tmpj);
-                    tmp = (D.tmpi + tmpj) + (Ri + Rj) * fij;
-                }
-                const T ft = -mj * (tmp + piij) * tg;
-                D.au = fma(ft, g.xij[0], D.au);
-                D.av = fma(ft, g.xij[1], D.av);
-                D.aw = fma(ft, g.xij[2], D.aw);
-            } else {
-                rhoij1 = fast_rcp(rhoij);
-            }
-            if (fl & F_XSPH) { // basic_equations.py:290-295
-                const T tmp = -a.p.eps * mj * wij * rhoij1;
-                D.ax = fma(tmp, vij0, D.ax);
-                D.ay = fma(tmp, vij1, D.ay);
-                D.az = fma(tmp, vij2, D.az);
-            }
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        if (a.dflags & F_CONT) a.p.arho[o] = D.arho;
-        if (a.dflags & F_MOM) { // post_loop wc/basic.py:261-271
-            T au = D.au + a.p.gx, av = D.av + a.p.gy, aw = D.aw + a.p.gz;
-            a.p.au[o] = au; a.p.av[o] = av; a.p.aw[o] = aw;
-            a.p.dt_cfl[o] = D.dt_cfl < T(0.0) ? T(0.0) : D.dt_cfl + a.p.c0;
-            a.p.dt_force[o] = au * au + av * av + aw * aw;
-        }
-        if (a.dflags & F_XSPH) { // post_loop basic_equations.py:297-300
-            a.p.ax[o] = D.ax + D.u; a.p.ay[o] = D.ay + D.v; a.p.az[o] = D.az + D.w;
-        }
-    }
-};
-typedef FamWCSPH_T<double> FamWCSPH;
-
-// The same equations on 64-byte records [x y | z u | v w | rho m] (fp32: 32 bytes): when the group before
-// this one was the Tait EOS over every array read here (sph_group.src_eos), p and cs are functions of rho
-// and are recomputed per gathered record -- four 16-B pieces in ONE 64-B half line instead of five pieces
-// that straddle a 128-B line half of the time.  ~14 more VALU operations per pair, hidden under the gathers.
-// Arithmetic as k_nosrc's (TaitEOS, gamma = 7) and k_pack's p / rho^2.
-// UM (uniform-mass records): every particle of a source array has the same mass (seen by the last sph_nnps_update),
-// so the record's eighth slot carries p / rho^2 as k_pack computes it for the 80-byte records and m is a constant of
-// the source: of the EOS only cs = c0 (rho/rho0)^3 is left in the loop (13 of its 17 instructions go).
-template <class T, bool UM = false> struct FamWCSPHE_T : FamWCSPH_T<T> {
-    static constexpr bool EOSF = true;
-    static constexpr bool UMASS = UM;
-    static constexpr int NR = 8;
-    // one gathered record as it arrives (four / two 16-B pieces), and its decoding
-    struct Raw {
-        typename std::conditional<sizeof(T) == 8, double2, float4>::type q[sizeof(T) == 8 ? 4 : 2];
-    };
-    template <class A> static __device__ __forceinline__ void load_raw(const A &a, uint32_t jg, Raw &r)
-    {
-        if constexpr (sizeof(T) == 8) {
-            const double2 *p = reinterpret_cast<const double2 *>(a.rec) + (unsigned long long)jg * 4;
-            r.q[0] = p[0]; r.q[1] = p[1]; r.q[2] = p[2]; r.q[3] = p[3];
-        } else {
-            const float4 *p = reinterpret_cast<const float4 *>(a.rec) + (unsigned long long)jg * 2;
-            r.q[0] = p[0]; r.q[1] = p[1];
-        }
-    }
-    // gk: the exponent gamma = 2 gk + 1 -- the constant 3 here (water: the compiler folds the powers), the launch
-    // argument in FamWCSPHEG_T below
-    template <class A> static __device__ __forceinline__ void decode(const A &a, const Raw &r, uint32_t fl, T mu, real4<T> &pj, T (&s)[8],
-                                                                     int gk = 3)
-    {
-        T rho;
-        if constexpr (sizeof(T) == 8) {
-            pj.x = r.q[0].x; pj.y = r.q[0].y; pj.z = r.q[1].x; pj.w = 0.0;
-            s[0] = r.q[1].y; s[1] = r.q[2].x; s[2] = r.q[2].y; s[3] = r.q[3].y; rho = r.q[3].x;
-        } else {
-            pj.x = r.q[0].x; pj.y = r.q[0].y; pj.z = r.q[0].z; pj.w = 0.f;
-            s[0] = r.q[0].w; s[1] = r.q[1].x; s[2] = r.q[1].y; s[3] = r.q[1].w; rho = r.q[1].z;
-        }
-        s[4] = rho;
-        s[5] = s[6] = s[7] = T(0.0);
-        if constexpr (UM) {
-            const T q = s[3]; // p / rho^2
-            s[3] = mu;
-            if (fl & F_MOM) {
-                const T ratio = rho * (T)a.e_rho01;
-                s[5] = q;
-                s[6] = (T)a.e_c0 * tait_cs_power(ratio, gk);
-            }
-        } else
-        if (fl & F_MOM) { // the flags of this (destination, source): a compile-time constant in the common case; a
-                          // continuity-only destination -- a dam break's walls -- reads neither
-            const T ratio = rho * (T)a.e_rho01;
-            T r7, r3; // (ratio^gamma, ratio^((gamma - 1) / 2): named for the usual exponent)
-            tait_powers(ratio, gk, r7, r3);
-            const T p = (T)a.e_p0 + (T)a.e_B * (r7 - T(1.0));
-            s[5] = rho != T(0.0) ? p * fast_rcp(rho * rho) : T(0.0);
-            s[6] = (T)a.e_c0 * r3;
-            s[7] = p;
-        }
-    }
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t fl, T mu, real4<T> &pj, T (&s)[8])
-    {
-        Raw r;
-        load_raw(a, jg, r);
-        decode(a, r, fl, mu, pj, s);
-    }
-};
-
-// ... with the exponent as a launch argument (gamma = 1, 3, 5: PairArgs::e_gk).  A family of its own because the select
-// costs the water kernels 1.3-2 % of their time when they carry it (profiles/r06_ab_tables.txt).
-template <class T, bool UM = false> struct FamWCSPHEG_T : FamWCSPHE_T<T, UM> {
-    typedef FamWCSPHE_T<T, UM> Base;
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t fl, T mu, real4<T> &pj, T (&s)[8])
-    {
-        typename Base::Raw r;
-        Base::load_raw(a, jg, r);
-        Base::decode(a, r, fl, mu, pj, s, a.e_gk);
-    }
-};
-
-// Variable h with ONE mass per source array: [x y | z h | u v | w rho] (fp32: [x y z h | u v w rho]) -- 64 bytes instead of
-// the 96-byte records with cs, m, p / rho^2 and p: the mass is a constant of the source, p, cs and p / rho^2 are the
-// Tait EOS of the gathered rho (as FamWCSPHE_T without the uniform-mass slot).  Run with UH = false.
-template <class T> struct FamWCSPHV_T : FamWCSPH_T<T> {
-    static constexpr bool EOSF = true;
-    static constexpr int NR = 8;
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t fl, T mu, real4<T> &pj, T (&s)[8])
-    {
-        T rho;
-        if constexpr (sizeof(T) == 8) {
-            const double2 *p = reinterpret_cast<const double2 *>(a.rec) + (unsigned long long)jg * 4;
-            const double2 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-            pj.x = q0.x; pj.y = q0.y; pj.z = q1.x; pj.w = q1.y;
-            s[0] = q2.x; s[1] = q2.y; s[2] = q3.x; rho = q3.y;
-        } else {
-            const float4 *p = reinterpret_cast<const float4 *>(a.rec) + (unsigned long long)jg * 2;
-            const float4 q0 = p[0], q1 = p[1];
-            pj.x = q0.x; pj.y = q0.y; pj.z = q0.z; pj.w = q0.w;
-            s[0] = q1.x; s[1] = q1.y; s[2] = q1.z; rho = q1.w;
-        }
-        s[3] = mu;
-        s[4] = rho;
-        s[5] = s[6] = s[7] = T(0.0);
-        if (fl & F_MOM) {
-            const T ratio = rho * (T)a.e_rho01;
-            T r7, r3; // (ratio^gamma, ratio^((gamma - 1) / 2): named for the usual exponent)
-            tait_powers(ratio, 3, r7, r3); // (gamma = 7 only: sph_eval_group checks)
-            const T p = (T)a.e_p0 + (T)a.e_B * (r7 - T(1.0));
-            s[5] = rho != T(0.0) ? p * fast_rcp(rho * rho) : T(0.0);
-            s[6] = (T)a.e_c0 * r3;
-            s[7] = p;
-        }
-    }
-};
-
-// ---- the same equations over the MERGED order of all arrays of the grid (sph_ctx::merged): ONE record stream, one
-// phase 1 and one phase 2 per wavefront whatever the number of arrays, destinations of every array in one launch.
-// A dam break -- fluid <- {fluid, boundary, obstacle}, walls <- fluid -- is two CLASSES of arrays: which equations act for
-// a (destination, source) pair depends on the classes of the two particles only.  Records are the uniform-mass ones,
-// [x y | z u | v w | +-rho p/rho^2]: the SIGN of rho is the particle's class (rho > 0 always), the mass a constant of
-// the class.  The class table is the kernel's compile-time flag constant CF = f00 | f01 << 4 | f10 << 8 | f11 << 12
-// (f<destination class><source class>: F_CONT | F_MOM | F_XSPH bits), so every "does equation e act for this pair" is
-// a boolean expression of two sign bits, and the criterion stays a factor: a pair without equations adds exactly zero.
-// Reference semantics: per-source equation lists of pysph/sph/acceleration_eval.py:126-151 (here per class pair),
-// equations wc/basic.py:198-269, basic_equations.py:187-192,285-300.  Sums run over all arrays in cell order instead of
-// source by source (another association of the same terms).
-#define WCSPHM_CT(f00, f01, f10, f11) ((uint32_t)(f00) | ((uint32_t)(f01) << 4) | ((uint32_t)(f10) << 8) | ((uint32_t)(f11) << 12))
-template <class T> struct FamWCSPHM_T : FamWCSPHE_T<T, true> {
-    typedef FamWCSPHE_T<T, true> Base;
-    typedef typename Base::Raw Raw;
-    static constexpr bool MERGED = true;
-    // WCSPHScheme(fluids, solids): fluid <- fluid all three, fluid <- solid no XSPH, solid <- fluid continuity only
-    static constexpr uint32_t CF0 = WCSPHM_CT(F_CONT | F_MOM | F_XSPH, F_CONT | F_MOM, F_CONT, 0);
-    struct Params {
-        T c0, alpha, beta, gx, gy, gz, eps;
-        double mu1;                                // mass of the class-1 arrays (class 0: SrcDesc::mu)
-        uint32_t rng[SPH_MAX_ARRAYS][2];           // per slot: destination index range [start, stop) (empty: no destination)
-        double *out[SPH_MAX_ARRAYS][9];            // per slot: arho au av aw ax ay az dt_cfl dt_force
-    };
-    static __device__ __forceinline__ size_t rng_offset(uint32_t slot) { return __builtin_offsetof(Params, rng) + (size_t)slot * 8; }
-    struct Dest : Base::Dest { bool dc; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &A_, uint32_t o, uint32_t)
-    {
-        Base::load(D, a, A_, o);
-        D.dc = a[3] < T(0.0); // decode() left the class in the sign of the mass
-    }
-    template <class A> static __device__ __forceinline__ void decode(const A &a, const Raw &r, uint32_t, T mu, real4<T> &pj, T (&s)[8])
-    {
-        T rho, q;
-        if constexpr (sizeof(T) == 8) {
-            pj.x = r.q[0].x; pj.y = r.q[0].y; pj.z = r.q[1].x; pj.w = 0.0;
-            s[0] = r.q[1].y; s[1] = r.q[2].x; s[2] = r.q[2].y; q = r.q[3].y; rho = r.q[3].x;
-        } else {
-            pj.x = r.q[0].x; pj.y = r.q[0].y; pj.z = r.q[0].z; pj.w = 0.f;
-            s[0] = r.q[0].w; s[1] = r.q[1].x; s[2] = r.q[1].y; q = r.q[1].w; rho = r.q[1].z;
-        }
-        const bool c1 = rho < T(0.0);
-        s[3] = c1 ? -(T)a.p.mu1 : mu;          // +-m: the sign is the class
-        rho = fabs(rho);
-        s[4] = rho;
-        const T ratio = rho * (T)a.e_rho01;
-        s[5] = q;                               // p / rho^2 as k_pack_merged computed it from the stored p
-        s[6] = (T)a.e_c0 * tait_cs_power(ratio, 3); // (gamma = 7 only: sph_eval_group checks)
-        s[7] = T(0.0);
-    }
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t fl, T mu, real4<T> &pj, T (&s)[8])
-    {
-        Raw r;
-        Base::load_raw(a, jg, r);
-        decode(a, r, fl, mu, pj, s);
-    }
-    // does equation `bit` act for (destination class dc, source class sc)?  ct is a compile-time constant
-    static __device__ __forceinline__ bool acts(uint32_t ct, uint32_t bit, bool dc, bool sc)
-    {
-        const bool c00 = ct & bit, c01 = (ct >> 4) & bit, c10 = (ct >> 8) & bit, c11 = (ct >> 12) & bit;
-        return dc ? (sc ? c11 : c10) : (sc ? c01 : c00);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[8], uint32_t ct, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        constexpr bool MRG = SPH_MERGED_RSQ && sizeof(T) == 8 && !SphKernel<KK>::CUTOFF;
-        T tt_m = T(0.0);
-        if constexpr (MRG) tt_m = pair_geom_mom<KK, UH>(g, pi, pj, r2, T(0.5) * (D.rho + s[4]), a);
-        else pair_geom<KK, UH>(g, pi, pj, r2, a);
-        const T tg = pair_gradfac<KK, UH>(g);
-        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
-        const T vdotx = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
-        const bool sc = s[3] < T(0.0);
-        const T m = fabs(s[3]);
-        const bool on_c = pass && acts(ct, F_CONT, D.dc, sc), on_m = pass && acts(ct, F_MOM, D.dc, sc),
-                   on_x = pass && acts(ct, F_XSPH, D.dc, sc);
-        D.arho = fma((on_c ? m : T(0.0)) * tg, vdotx, D.arho); // basic_equations.py:187-192
-        const T rhoij = T(0.5) * (D.rho + s[4]);
-        const T wij = pair_w<KK, UH>(g);
-        // wc/basic.py:204-259
-        const T re = r2 + g.eps;
-        const T tt = MRG ? tt_m : fast_rcp(re * rhoij);
-        const T inv_re = rhoij * tt;
-        const T rhoij1 = re * tt;
-        const T hv = g.hij * vdotx;
-        const T muij = raw_min(hv, T(0.0)) * inv_re; // approaching pairs only, as FamWCSPH_T::pair
-        const T cij = T(0.5) * (D.cs + s[6]);
-        const T piij = (a.p.beta * muij - a.p.alpha * cij) * muij * rhoij1;
-        const T dtv = fabs(hv * (g.rinv * g.rinv));
-        D.dt_cfl = raw_max(D.dt_cfl, (r2 > T(1e-12) && on_m) ? dtv : T(-1.0));
-        const T ft = -(on_m ? m : T(0.0)) * ((D.tmpi + s[5]) + piij) * tg;
-        D.au = fma(ft, g.xij[0], D.au);
-        D.av = fma(ft, g.xij[1], D.av);
-        D.aw = fma(ft, g.xij[2], D.aw);
-        // basic_equations.py:290-295
-        const T tmp = -a.p.eps * (on_x ? m : T(0.0)) * wij * rhoij1;
-        D.ax = fma(tmp, vij0, D.ax);
-        D.ay = fma(tmp, vij1, D.ay);
-        D.az = fma(tmp, vij2, D.az);
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o, uint32_t slot)
-    {
-        // the equations with this lane's class as destination (class table row); its array's output pointers
-        const uint32_t ct = a.dflags;
-        const uint32_t row = D.dc ? ((ct >> 8) | (ct >> 12)) & 15u : (ct | (ct >> 4)) & 15u;
-        const size_t base = __builtin_offsetof(A, p) + __builtin_offsetof(Params, out) + (size_t)slot * (9 * sizeof(double *));
-        auto out = [&](int k) { return kernarg_read<double *>(base + (size_t)k * sizeof(double *)); };
-        if (row & F_CONT) out(0)[o] = D.arho;
-        if (row & F_MOM) { // post_loop wc/basic.py:261-271
-            const T au = D.au + a.p.gx, av = D.av + a.p.gy, aw = D.aw + a.p.gz;
-            out(1)[o] = au; out(2)[o] = av; out(3)[o] = aw;
-            out(7)[o] = D.dt_cfl < T(0.0) ? T(0.0) : D.dt_cfl + a.p.c0;
-            out(8)[o] = au * au + av * av + aw * aw;
-        }
-        if (row & F_XSPH) { // post_loop basic_equations.py:297-300
-            out(4)[o] = D.ax + D.u; out(5)[o] = D.ay + D.v; out(6)[o] = D.az + D.w;
-        }
-    }
-};
-
-// ... and with VARIABLE h (round 5): records [x y | z h | u v | w +-rho] (fp32 [x y z h | u v w +-rho]) as FamWCSPHV_T's
-// with the class in the sign of rho; p / rho^2 and cs are the Tait EOS of the gathered rho.  Run with UH = false.
-template <class T> struct FamWCSPHMV_T : FamWCSPHM_T<T> {
-    typedef FamWCSPHM_T<T> Base;
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t, T mu, real4<T> &pj, T (&s)[8])
-    {
-        T rho;
-        if constexpr (sizeof(T) == 8) {
-            const double2 *p = reinterpret_cast<const double2 *>(a.rec) + (unsigned long long)jg * 4;
-            const double2 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-            pj.x = q0.x; pj.y = q0.y; pj.z = q1.x; pj.w = q1.y;
-            s[0] = q2.x; s[1] = q2.y; s[2] = q3.x; rho = q3.y;
-        } else {
-            const float4 *p = reinterpret_cast<const float4 *>(a.rec) + (unsigned long long)jg * 2;
-            const float4 q0 = p[0], q1 = p[1];
-            pj.x = q0.x; pj.y = q0.y; pj.z = q0.z; pj.w = q0.w;
-            s[0] = q1.x; s[1] = q1.y; s[2] = q1.z; rho = q1.w;
-        }
-        const bool c1 = rho < T(0.0);
-        s[3] = c1 ? -(T)a.p.mu1 : mu; // +-m: the sign is the class
-        rho = fabs(rho);
-        s[4] = rho;
-        const T ratio = rho * (T)a.e_rho01;
-        T r7, r3;
-        tait_powers(ratio, 3, r7, r3); // (gamma = 7 only: sph_eval_group checks)
-        const T p = (T)a.e_p0 + (T)a.e_B * (r7 - T(1.0));
-        s[5] = rho != T(0.0) ? p * fast_rcp(rho * rho) : T(0.0);
-        s[6] = (T)a.e_c0 * r3;
-        s[7] = T(0.0);
-    }
-};
-
-// WCSPH records of the aggregated kernel use the layout
-//   [x y z cs | u v w m | rho tmpj | h p]
-// so that the common case (uniform h, no tensile correction) gathers 80 B =
-// five 16-B pieces per pair and never touches the last piece.
-template <bool UH>
-__device__ __forceinline__ void load_record_wcsph(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[8])
-{
-    const double2 *r2 = reinterpret_cast<const double2 *>(rj);
-    const double2 a0 = r2[0], a1 = r2[1], b0 = r2[2], b1 = r2[3], c = r2[4];
-    pj.x = a0.x; pj.y = a0.y; pj.z = a1.x; pj.w = 0.0;
-    s[0] = b0.x; s[1] = b0.y; s[2] = b1.x; s[3] = b1.y; s[4] = c.x; s[5] = c.y; s[6] = a1.y; s[7] = 0.0;
-    if (!UH || (fl & F_TENSILE)) {
-        const double2 d = *reinterpret_cast<const double2 *>(rj + 10);
-        pj.w = d.x; s[7] = d.y;
-    }
-}
-template <> __device__ __forceinline__ void load_record<FamWCSPH, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[8]) { load_record_wcsph<true>(rj, fl, pj, s); }
-template <> __device__ __forceinline__ void load_record<FamWCSPH, false>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[8]) { load_record_wcsph<false>(rj, fl, pj, s); }
-
-// ---- WCSPHScheme options: delta-SPH, laminar viscosity ---------------------------------
-// The rates group of WCSPHScheme(delta_sph=True and / or nu != 0) in ONE sweep: Continuity / Momentum / XSPH exactly as
-// FamWCSPH_T evaluates them, plus
-//   F_DCONT  ContinuityEquationDeltaSPH   wc/basic.py:400-414   (reads gradrho of destination and source)
-//   F_DMOM   MomentumEquationDeltaSPH     wc/basic.py:326-343
-//   F_LAM    LaminarViscosity             wc/viscosity.py:12-27
-//   F_LAMD   LaminarViscosityDeltaSPH     wc/viscosity.py:134-144
-// per (destination, source) like every other flag.  All terms add into arho / au av aw before finish(), so dt_force sees
-// the summed acceleration as the reference's post_loop does.  Records [x y z h | u v w m rho p/rho^2 cs p] and, with
-// DS (a delta-SPH continuity term acts on this destination), three more values: the source's gradrho.
-// The new terms are the reference's, regrouped as FamWCSPH_T::pair regroups (DWIJ = tg XIJ, reciprocals shared); the
-// one place where terms cancel -- psi = fac XIJ - gradrho_i - gradrho_j -- keeps the reference's order.
-template <class T, bool DS> struct FamWCSPHX_T : FamWCSPH_T<T> {
-    typedef FamWCSPH_T<T> Base;
-    static constexpr uint32_t CF0 = DS ? (F_CONT | F_MOM | F_XSPH | F_DCONT | F_DMOM | F_LAMD) : (F_CONT | F_MOM | F_XSPH | F_LAM);
-    static constexpr int MINB = DS ? 2 : 3; // (the base family's sums and inputs + the extra terms' registers)
-    static constexpr int NA = DS ? 11 : 8;  // Base's eight + gradrho x y z
-    static constexpr int NR = DS ? 16 : 12;
-    struct Params : Base::Params {
-        T nu4, eta;   // LaminarViscosity: 4 nu, eta
-        T lfac;       // LaminarViscosityDeltaSPH: 2 (dim + 2) nu rho0
-        T mfac;       // MomentumEquationDeltaSPH: alpha c0 rho0
-        T dfac;       // ContinuityEquationDeltaSPH: delta c0
-    };
-    struct Dest : Base::Dest { T g0, g1, g2, rho1; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *s, const A &a, uint32_t o)
-    {
-        Base::load(D, s, a, o);
-        D.g0 = D.g1 = D.g2 = T(0.0);
-        if constexpr (DS) { D.g0 = s[8]; D.g1 = s[9]; D.g2 = s[10]; }
-        D.rho1 = fast_rcp(D.rho);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        Base::template pair<KK, UH>(D, pi, pj, r2, reinterpret_cast<const T (&)[8]>(s), fl, a, pass);
-        if (!(fl & (F_DCONT | F_DMOM | F_LAM | F_LAMD))) return;
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        const T tg = pair_gradfac<KK, UH>(g); // DWIJ = tg XIJ (0 for r <= 1e-12)
-        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
-        const T vdotx = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
-        const T rhoj = s[4];
-        if (fl & F_LAM) { // tmp = mb 4 nu Fij / ((rhoa + rhob) (R2IJ + eta HIJ^2)),  Fij = DWIJ.XIJ
-            const T fij = tg * (g.xij[0] * g.xij[0] + g.xij[1] * g.xij[1] + g.xij[2] * g.xij[2]);
-            const T den = (D.rho + rhoj) * (r2 + a.p.eta * g.hij * g.hij);
-            const T tmp = pass ? s[3] * a.p.nu4 * fij * fast_rcp(den) : T(0.0);
-            D.au = fma(tmp, vij0, D.au);
-            D.av = fma(tmp, vij1, D.av);
-            D.aw = fma(tmp, vij2, D.aw);
-        }
-        if (fl & (F_DCONT | F_DMOM | F_LAMD)) {
-            const T re1 = fast_rcp(r2 + g.eps);
-            // Vj = mj / rhoj; a candidate outside the criterion adds exactly zero (a select, not a product: a parked
-            // padding row has rho = 0)
-            const T Vj = pass ? s[3] * fast_rcp(rhoj) : T(0.0);
-            if (fl & (F_DMOM | F_LAMD)) { // both are  f piij Vj / rhoi DWIJ  with piij = VIJ.XIJ / (R2IJ + EPS)
-                T f = T(0.0);
-                if (fl & F_DMOM) f = a.p.mfac * g.hij; // alpha HIJ c0 rho0
-                if (fl & F_LAMD) f += a.p.lfac;        // 2 (dim + 2) nu rho0
-                const T ft = f * (vdotx * re1) * Vj * D.rho1 * tg;
-                D.au = fma(ft, g.xij[0], D.au);
-                D.av = fma(ft, g.xij[1], D.av);
-                D.aw = fma(ft, g.xij[2], D.aw);
-            }
-            if constexpr (DS) {
-                if (fl & F_DCONT) {
-                    const T fac = T(-2.0) * (rhoj - D.rho) * re1;
-                    const T px = (fac * g.xij[0] - D.g0) - s[8];
-                    const T py = (fac * g.xij[1] - D.g1) - s[9];
-                    const T pz = (fac * g.xij[2] - D.g2) - s[10];
-                    const T psidot = tg * (px * g.xij[0] + py * g.xij[1] + pz * g.xij[2]);
-                    D.arho = fma(a.p.dfac * g.hij * psidot, Vj, D.arho);
-                }
-            }
-        }
-    }
-};
-
-// ---- delta-SPH pre-passes on [x y z h | m rho] records --------------------------------------------------------
-//   F_MOMENT   GradientCorrectionPreStep          wc/kernel_correction.py:46-74: m_mat[3i+j] = -sum V_b DWIJ[i] XIJ[j]
-//   F_GRADRHO  ContinuityEquationDeltaSPHPreStep  wc/basic.py:355-369: gradrho = sum (rho_b - rho_a) DWIJ V_b
-//   F_GCORR    GradientCorrection                 wc/kernel_correction.py:98-123, in front of it in the group: DWIJ
-//              becomes res = M^-1 DWIJ on the leading n x n block when |sum|res| - sum|DWIJ|| / (sum|DWIJ| + 1e-4 HIJ) < tol
-// The reference solves M res = DWIJ per pair with gj_solve (wc/linalg.py:94-166).  Its row search exchanges nothing
-// (after `bigrow = row` the exchange is of an element with itself), so it is elimination in the given row order, and
-// that does not depend on the right-hand side: load() factorises M once per destination (multipliers, the upper
-// triangle, reciprocal pivots), pair() applies the factors to DWIJ in gj_solve's own order.  gj_solve's ways out:
-//   * a pivot but the last below 1e-12 in magnitude: it returns with the result untouched (zero).  All factors are set
-//     to zero, which gives res = 0;
-//   * the last pivot exactly zero: with |rhs| > 1e-12 in that row the result stays zero; otherwise the row is left as
-//     it is (res_last = rhs_last, nothing eliminated above it): reciprocal 1, its column of the triangle 0, and the
-//     per-pair test of that rhs (`chk`).
-// res = 0 makes the change ~1 and DWIJ stays uncorrected (for tol <= 1), as in the reference.
-template <class T> struct FamDSPre_T {
-    typedef T Real;
-    static constexpr bool PRED = true;
-    static constexpr uint32_t CF0 = F_GRADRHO | F_GCORR;
-    static constexpr int MINB = 3;
-    static constexpr int NA = 2; // m rho
-    static constexpr int NR = 6;
-    struct Params {
-        int mdim;       // GradientCorrectionPreStep.dim
-        int n;          // GradientCorrection.dim
-        T tol;
-        double *mm[9];  // m_mat__0..8 of the destination: written by F_MOMENT, read by F_GCORR
-        double *gr[3];  // gradrho__0..2
-    };
-    struct Dest {
-        T rho;
-        T acc[9];                       // F_MOMENT: the nine sums; F_GRADRHO: acc[0..2]
-        T c10, c20, c21, u01, u02, u12; // elimination multipliers, upper triangle
-        T i0, i1, i2;                   // reciprocal pivots
-        bool chk;                       // last pivot exactly zero: the pair tests its right-hand side
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *s, const A &a, uint32_t o)
-    {
-        D.rho = s[1];
-#pragma unroll
-        for (int k = 0; k < 9; k++) D.acc[k] = T(0.0);
-        D.c10 = D.c20 = D.c21 = D.u01 = D.u02 = D.u12 = D.i0 = D.i1 = D.i2 = T(0.0);
-        D.chk = false;
-        if (!(a.dflags & F_GCORR)) return;
-        const int n = a.p.n;
-        T M[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) M[i][j] = (i < n && j < n) ? (T)a.p.mm[3 * i + j][o] : T(i == j ? 1.0 : 0.0);
-        bool ok = true;
-        if (n > 1) { // column 0
-            const T d = M[0][0];
-            if (fabs(d) < T(1e-12)) ok = false;
-            else {
-                D.c10 = -M[1][0] / d;
-                M[1][1] += D.c10 * M[0][1]; M[1][2] += D.c10 * M[0][2];
-                if (n > 2) { D.c20 = -M[2][0] / d; M[2][1] += D.c20 * M[0][1]; M[2][2] += D.c20 * M[0][2]; }
-            }
-        }
-        if (ok && n > 2) { // column 1
-            const T d = M[1][1];
-            if (fabs(d) < T(1e-12)) ok = false;
-            else { D.c21 = -M[2][1] / d; M[2][2] += D.c21 * M[1][2]; }
-        }
-        if (!ok) { D.c10 = D.c20 = D.c21 = T(0.0); return; } // every factor zero: res = 0
-        D.u01 = M[0][1]; D.u02 = M[0][2]; D.u12 = M[1][2];
-        D.i0 = T(1.0) / M[0][0]; D.i1 = T(1.0) / M[1][1]; D.i2 = T(1.0) / M[2][2]; // (rows >= n: identity)
-        const T last = n == 3 ? M[2][2] : (n == 2 ? M[1][1] : M[0][0]);
-        if (last == T(0.0)) {
-            D.chk = true;
-            if (n == 3) { D.i2 = T(1.0); D.u02 = D.u12 = T(0.0); }
-            else if (n == 2) { D.i1 = T(1.0); D.u01 = T(0.0); }
-            else D.i0 = T(1.0);
-        }
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        const T tg = pair_gradfac<KK, UH>(g);
-        T dw[3] = {tg * g.xij[0], tg * g.xij[1], tg * g.xij[2]};
-        const T Vj = pass ? s[0] * fast_rcp(s[1]) : T(0.0); // (a select: a parked padding row has rho = 0)
-        if (fl & F_MOMENT) {
-            const int md = a.p.mdim;
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-#pragma unroll
-                for (int j = 0; j < 3; j++)
-                    if (i < md && j < md) D.acc[3 * i + j] = fma(-Vj * dw[i], g.xij[j], D.acc[3 * i + j]);
-        }
-        if (fl & F_GRADRHO) {
-            if (fl & F_GCORR) {
-                const int n = a.p.n;
-                // forward: rows 1, 2 += multiplier * row above, in gj_solve's order
-                T y0 = dw[0], y1 = dw[1], y2 = dw[2];
-                if (n > 1) y1 = fma(D.c10, y0, y1);
-                if (n > 2) { y2 = fma(D.c20, y0, y2); y2 = fma(D.c21, y1, y2); }
-                const T ylast = n == 3 ? y2 : (n == 2 ? y1 : y0);
-                // back substitution from the last row up
-                T x0, x1 = T(0.0), x2 = T(0.0);
-                if (n > 2) { x2 = y2 * D.i2; y1 = fma(-D.u12, x2, y1); y0 = fma(-D.u02, x2, y0); }
-                if (n > 1) { x1 = y1 * D.i1; y0 = fma(-D.u01, x1, y0); }
-                x0 = y0 * D.i0;
-                if (D.chk && fabs(ylast) > T(1e-12)) { x0 = x1 = x2 = T(0.0); }
-                T rmag = fabs(x0), dmag = fabs(dw[0]);
-                if (n > 1) { rmag += fabs(x1); dmag += fabs(dw[1]); }
-                if (n > 2) { rmag += fabs(x2); dmag += fabs(dw[2]); }
-                const T change = fabs(rmag - dmag) / (dmag + T(1.0e-4) * g.hij);
-                if (change < a.p.tol) {
-                    dw[0] = x0;
-                    if (n > 1) dw[1] = x1;
-                    if (n > 2) dw[2] = x2;
-                }
-            }
-            const T cf = (s[1] - D.rho) * Vj;
-            D.acc[0] = fma(cf, dw[0], D.acc[0]);
-            D.acc[1] = fma(cf, dw[1], D.acc[1]);
-            D.acc[2] = fma(cf, dw[2], D.acc[2]);
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        if (a.dflags & F_MOMENT) {
-#pragma unroll
-            for (int k = 0; k < 9; k++) a.p.mm[k][o] = D.acc[k];
-        }
-        if (a.dflags & F_GRADRHO) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) a.p.gr[k][o] = D.acc[k];
-        }
-    }
-};
-
-// ---- density summations (basic_equations.py:19-29, transport_velocity.py:24-58)
-template <class T> struct FamDensity_T {
-    typedef T Real; // arithmetic type of the pair loop
-    static constexpr bool PRED = true; // see FamWCSPH
-    static constexpr uint32_t CF0 = F_TVFSD; // flag set compiled as a constant (variant 6)
-    static constexpr int MINB = 4; // wavefronts per SIMD the pair kernel is compiled for (VGPR budget)
-    static constexpr int NA = 1; // m
-    static constexpr int NR = 6;  // x y z h m pad
-    struct Params { double *rho, *V; };
-    struct Dest { T m, rho, V; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t) { D.m = a[0]; D.rho = T(0.0); D.V = T(0.0); }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        T wij = pair_w<KK, UH>(g);
-        wij = pass ? wij : T(0.0); // PRED: a pair outside the criterion adds exactly zero
-        if (fl & F_SD) D.rho += s[0] * wij;
-        if (fl & F_TVFSD) { D.V += wij; D.rho += D.m * wij; }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        a.p.rho[o] = D.rho;
-        if (a.dflags & F_TVFSD) a.p.V[o] = D.V;
-    }
-};
-typedef FamDensity_T<double> FamDensity;
-
-// Density records of the aggregated kernel under uniform h: [x y z m] (32 B, two
-// 16-B pieces per pair); otherwise the generic [x y z h | m pad].
-template <> __device__ __forceinline__ void load_record<FamDensity, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[1])
-{
-    const double2 *r2 = reinterpret_cast<const double2 *>(rj);
-    const double2 a0 = r2[0], a1 = r2[1];
-    pj.x = a0.x; pj.y = a0.y; pj.z = a1.x; pj.w = 0.0;
-    s[0] = a1.y;
-}
-
-// ---- neighbour lists (LinkedListNNPS.find_nearest_neighbors, linked_list_nnps.pyx:92-196; the reference's
-//      NeighborCache, nnps_base.pyx:1144-1257) on the pair-kernel skeleton: the "equation" counts the pairs
-//      that pass the exact criterion and, in the fill pass, writes the neighbour's ORIGINAL index (it travels
-//      in the record as a double) behind the destination's list start.  Same candidate tiles, fp32 prefilter
-//      and exact test as every other family, so the lists are the pair loops' own neighbour sets.
-struct FamNbr {
-    typedef double Real;
-    static constexpr bool PRED = true;
-    static constexpr uint32_t CF0 = 1;
-    static constexpr int MINB = 4;
-    static constexpr int NA = 1; // original index of the particle
-    static constexpr int NR = 6; // x y z h idx pad  (uniform h: [x y z idx])
-    struct Params { uint32_t *count; const uint32_t *start; uint32_t *nbrs; };
-    struct Dest { uint32_t n, base; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const double *, const A &a, uint32_t o)
-    {
-        D.n = 0;
-        D.base = a.p.start ? a.p.start[o] : 0u;
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const double4 &, const double4 &, double, const double (&s)[NA], uint32_t,
-                                                const A &a, bool pass = true)
-    {
-        if (pass) {
-            if (a.p.nbrs) a.p.nbrs[D.base + D.n] = (uint32_t)s[0];
-            D.n++;
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        if (a.p.count) a.p.count[o] = D.n;
-    }
-};
-template <> __device__ __forceinline__ void load_record<FamNbr, true>(const double *__restrict__ rj, uint32_t, double4 &pj, double (&s)[1])
-{
-    const double2 *r2 = reinterpret_cast<const double2 *>(rj);
-    const double2 a0 = r2[0], a1 = r2[1];
-    pj.x = a0.x; pj.y = a0.y; pj.z = a1.x; pj.w = 0.0;
-    s[0] = a1.y;
-}
-
-// ---- TVF momentum terms (transport_velocity.py:219-545) -------------------
-template <class T> struct FamTVF_T {
-    typedef T Real; // arithmetic type of the pair loop
-    static constexpr bool PRED = true; // see FamWCSPH
-    static constexpr uint32_t CF0 = F_TP | F_TVISC | F_TAS; // flag set compiled as a constant (variant 6)
-    static constexpr int MINB = 4; // wavefronts per SIMD the pair kernel is compiled for (VGPR budget; fp64: 125-129 registers)
-    static constexpr int NA = 12; // u v w uhat vhat what rho p V m Vj2 pad
-    static constexpr int NR = 16; // x y z h + NA
-    struct Params {
-        T pb, gx, gy, gz, tdamp, nu, c0, alpha;
-        const double *m; // the destination's own mass (a neighbour's travels in the records only with F_TAV)
-        double *au, *av, *aw, *auhat, *avhat, *awhat;
-    };
-    struct Dest {
-        T u, v, w, uh, vh, wh, rho, p, Vi2, mi1;
-        T au, av, aw, auh, avh, awh;
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &A_, uint32_t o)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.uh = a[3]; D.vh = a[4]; D.wh = a[5];
-        D.rho = a[6]; D.p = a[7]; D.Vi2 = a[10]; D.mi1 = T(1.0) / T(A_.p.m[o]);
-        D.au = D.av = D.aw = D.auh = D.avh = D.awh = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        T tg = pair_gradfac<KK, UH>(g);
-        tg = pass ? tg : T(0.0); // PRED: every term carries DWIJ
-        T dw0 = tg * g.xij[0], dw1 = tg * g.xij[1], dw2 = tg * g.xij[2];
-        T rhoj = s[6], Vj2 = s[10];
-        T vsum = D.Vi2 + Vj2;
-        T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
-        if (fl & F_TP) { // :290-320
-            T pij = rhoj * D.p + D.rho * s[7];
-            pij *= fast_rcp(rhoj + D.rho);
-            T tmp = -pij * D.mi1 * vsum;
-            D.au += tmp * dw0; D.av += tmp * dw1; D.aw += tmp * dw2;
-            tmp = -a.p.pb * D.mi1 * vsum;
-            D.auh += tmp * dw0; D.avh += tmp * dw1; D.awh += tmp * dw2;
-        }
-        if (fl & F_TAV) { // :420-436
-            T vijdotrij = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
-            T piij = T(0.0);
-            if (vijdotrij < 0) {
-                T muij = (g.hij * vijdotrij) * fast_rcp(r2 + g.eps);
-                piij = -a.p.alpha * a.p.c0 * muij;
-                piij = s[9] * piij * fast_rcp(T(0.5) * (D.rho + rhoj));
-            }
-            D.au += -piij * dw0; D.av += -piij * dw1; D.aw += -piij * dw2;
-        }
-        if (fl & F_TVISC) { // :363-384
-            T etai = a.p.nu * D.rho, etaj = a.p.nu * rhoj;
-            T etaij = 2 * (etai * etaj) * fast_rcp(etai + etaj);
-            T Fij = dw0 * g.xij[0] + dw1 * g.xij[1] + dw2 * g.xij[2];
-            T tmp = D.mi1 * vsum * etaij * Fij * fast_rcp(r2 + g.eps);
-            D.au += tmp * vij0; D.av += tmp * vij1; D.aw += tmp * vij2;
-        }
-        if (fl & F_TAS) { // :473-545
-            // A = rho v (x) (vhat - v);  0.5 (A_i + A_j) . DWIJ, with the dot
-            // products (vhat - v) . DWIJ taken first (same terms as the
-            // reference's 18 products, associated per particle)
-            const T ddi = (D.uh - D.u) * dw0 + (D.vh - D.v) * dw1 + (D.wh - D.w) * dw2;
-            const T ddj = (s[3] - s[0]) * dw0 + (s[4] - s[1]) * dw1 + (s[5] - s[2]) * dw2;
-            const T ci = D.rho * ddi, cj = rhoj * ddj;
-            const T tmp = T(0.5) * D.mi1 * vsum;
-            D.au += tmp * (ci * D.u + cj * s[0]);
-            D.av += tmp * (ci * D.v + cj * s[1]);
-            D.aw += tmp * (ci * D.w + cj * s[2]);
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        T damp = T(1.0); // post_loop :322-325
-        if (a.t < a.p.tdamp) damp = T(0.5) * (sin((-T(0.5) + a.t / a.p.tdamp) * M_PI) + T(1.0));
-        T gx = (a.dflags & F_TP) ? a.p.gx * damp : T(0.0);
-        T gy = (a.dflags & F_TP) ? a.p.gy * damp : T(0.0);
-        T gz = (a.dflags & F_TP) ? a.p.gz * damp : T(0.0);
-        a.p.au[o] = D.au + gx; a.p.av[o] = D.av + gy; a.p.aw[o] = D.aw + gz;
-        if (a.dflags & F_TP) { a.p.auhat[o] = D.auh; a.p.avhat[o] = D.avh; a.p.awhat[o] = D.awh; }
-    }
-};
-typedef FamTVF_T<double> FamTVF;
-
-// TVF records of the aggregated kernel under uniform h (see k_pack layout 3):
-// five 16-B pieces per pair, a sixth when the artificial-stress term acts, a
-// seventh (the neighbour's mass) only for the artificial viscosity.
-template <> __device__ __forceinline__ void load_record<FamTVF, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12])
-{
-    const double2 *r2 = reinterpret_cast<const double2 *>(rj);
-    const double2 a0 = r2[0], a1 = r2[1], b0 = r2[2], b1 = r2[3], c0 = r2[4];
-    pj.x = a0.x; pj.y = a0.y; pj.z = a1.x; pj.w = 0.0;
-    s[0] = b0.x; s[1] = b0.y; s[2] = b1.x; s[6] = a1.y; s[7] = b1.y; s[8] = 0.0; s[9] = 0.0; s[10] = c0.x; s[11] = 0.0;
-    s[3] = s[4] = 0.0; s[5] = c0.y;
-    if (fl & F_TAS) {
-        const double2 d0 = r2[5];
-        s[3] = d0.x; s[4] = d0.y;
-    }
-    if (fl & F_TAV) s[9] = r2[6].x;
-}
-
-// The same terms on records WITHOUT p and V (sph_group.src_eos = 2): the group before this one was TVF's StateEquation
-// over every particle of every array read here and its density summation ran earlier in the evaluation, so
-// p = p0 (rho / rho0 - b) and V = rho / m are functions of the gathered rho and the source array's ONE mass:
-// [x y | z rho | u v | w uhat | vhat what] -- 80 bytes, five 16-B pieces instead of six (four without the artificial
-// stress); fp32: [x y z rho | u v w uhat | vhat what - -], three pieces instead of four.  One reciprocal more per pair.
-template <class T> struct FamTVFE_T : FamTVF_T<T> {
-    static constexpr bool EOSF = true;
-    static constexpr int NA = 12;
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t fl, T mu, real4<T> &pj, T (&s)[12])
-    {
-        T rho;
-        if constexpr (sizeof(T) == 8) {
-            const double2 *p = reinterpret_cast<const double2 *>(a.rec) + (unsigned long long)jg * (unsigned)(a.nrec >> 1);
-            const double2 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-            pj.x = q0.x; pj.y = q0.y; pj.z = q1.x; pj.w = 0.0; rho = q1.y;
-            s[0] = q2.x; s[1] = q2.y; s[2] = q3.x; s[3] = q3.y; s[4] = s[5] = 0.0;
-            if (fl & F_TAS) { const double2 q4 = p[4]; s[4] = q4.x; s[5] = q4.y; }
-        } else {
-            const float4 *p = reinterpret_cast<const float4 *>(a.rec) + (unsigned long long)jg * (unsigned)(a.nrec >> 2);
-            const float4 q0 = p[0], q1 = p[1];
-            pj.x = q0.x; pj.y = q0.y; pj.z = q0.z; pj.w = 0.f; rho = q0.w;
-            s[0] = q1.x; s[1] = q1.y; s[2] = q1.z; s[3] = q1.w; s[4] = s[5] = 0.f;
-            if (fl & F_TAS) { const float4 q2 = p[2]; s[4] = q2.x; s[5] = q2.y; }
-        }
-        s[6] = rho;
-        s[7] = (T)a.e_p0 * (rho * (T)a.e_rho01 - (T)a.e_B); // StateEquation, as k_nosrc computes it
-        s[8] = T(0.0);
-        s[9] = mu;
-        const T vj = mu * fast_rcp(rho);                     // 1 / V_j with V = sum W = rho / m (transport_velocity.py:52-58): Vj2 = (m / rho)^2, :303-306
-        s[10] = vj * vj;
-        s[11] = T(0.0);
-    }
-};
-
-// ---- EDAC force group (pysph/sph/wc/edac.py:301-488 with transport_velocity.py:328-545 and basic_equations.py:260-300)
-//      Everything EDACScheme puts on a fluid destination in its force group, in ONE sweep: the pressure gradient
-//      (external form :320-343, or the internal one :443-478 with pb, the transport accelerations and the
-//      destination's pavg taken off both pressures), the artificial and the physical viscosity, the artificial stress
-//      (internal branch), the pressure rate ap (:365-386: a continuity-like term with cs^2 and a damping term with
-//      its OWN viscosity edac_nu) and the XSPH correction (external branch; it reads the fluid only, which the
-//      per-source flags express).  INT = the internal branch: the two branches are two instantiations, each with its
-//      scheme's default flag set as a compile-time constant and without the other branch's terms and accumulators.
-//      Records: the generic [x y z h | u v w uhat vhat what rho p V m Vj2 -] of FamTVF_T; under uniform h k_pack's
-//      compact layout 3 in its seven-piece form, which carries m (load_record_edac below).  p is integrated state
-//      here, not a function of rho, so the records that leave p and V out (FamTVFE_T) do not apply.
-enum { F_EP = 1, /* F_TVISC = 2, F_TAV = 4, F_TAS = 8 as in FamTVF_T */ F_EINT = 16, F_EDAC = 32, F_EXS = 64 };
-template <class T, bool INT> struct FamEDAC_T {
-    typedef T Real;
-    static constexpr bool PRED = true; // every term carries DWIJ or WIJ, both zero for a pair outside the criterion
-    static constexpr uint32_t CF0 = INT ? (F_EP | F_EINT | F_TVISC | F_TAS | F_EDAC) : (F_EP | F_TVISC | F_EDAC | F_EXS);
-    static constexpr uint32_t MASK = INT ? ~(uint32_t)F_EXS : ~(uint32_t)(F_TAS | F_EINT);
-    static constexpr int MINB = 4;
-    static constexpr int NA = 12; // u v w uhat vhat what rho p V m Vj2 pad
-    static constexpr int NR = 16;
-    struct Params {
-        T pb, gx, gy, gz, tdamp, nu, c0, alpha, cs2, enu, eps;
-        const double *m, *pavg; // the destination's own mass and average pressure
-        double *au, *av, *aw, *auhat, *avhat, *awhat, *ap, *ax, *ay, *az;
-    };
-    struct Dest {
-        T u, v, w, uh, vh, wh, rho, p, pavg, Vi2, mi1;
-        T au, av, aw, auh, avh, awh, ap, ax, ay, az;
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &A_, uint32_t o)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.uh = a[3]; D.vh = a[4]; D.wh = a[5];
-        D.rho = a[6]; D.p = a[7]; D.Vi2 = a[10]; D.mi1 = T(1.0) / T(A_.p.m[o]);
-        D.pavg = T(0.0); // the destination's, taken off both pressures (edac.py:450-454)
-        if (INT && (A_.dflags & F_EP)) D.pavg = T(A_.p.pavg[o]);
-        D.uh = INT ? D.uh : T(0.0); D.vh = INT ? D.vh : T(0.0); D.wh = INT ? D.wh : T(0.0);
-        D.au = D.av = D.aw = D.auh = D.avh = D.awh = D.ap = D.ax = D.ay = D.az = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl_, const A &a, bool pass = true)
-    {
-        const uint32_t fl = fl_ & MASK;
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        T tg = pair_gradfac<KK, UH>(g);
-        tg = pass ? tg : T(0.0);
-        const T dw0 = tg * g.xij[0], dw1 = tg * g.xij[1], dw2 = tg * g.xij[2];
-        const T rhoj = s[6], Vj2 = s[10];
-        const T vsum = D.Vi2 + Vj2;
-        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
-        const T xdw = dw0 * g.xij[0] + dw1 * g.xij[1] + dw2 * g.xij[2]; // XIJ . DWIJ
-        const T rsum1 = fast_rcp(rhoj + D.rho);
-        if (fl & F_EP) { // edac.py:323-343 / :448-478
-            T pij = rhoj * (D.p - D.pavg) + D.rho * (s[7] - D.pavg);
-            pij *= rsum1;
-            T tmp = -pij * D.mi1 * vsum;
-            D.au += tmp * dw0; D.av += tmp * dw1; D.aw += tmp * dw2;
-            if (INT) {
-                tmp = -a.p.pb * D.mi1 * vsum;
-                D.auh += tmp * dw0; D.avh += tmp * dw1; D.awh += tmp * dw2;
-            }
-        }
-        if (fl & F_TAV) { // transport_velocity.py:420-436
-            const T vijdotrij = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
-            T piij = T(0.0);
-            if (vijdotrij < 0) {
-                const T muij = (g.hij * vijdotrij) * fast_rcp(r2 + g.eps);
-                piij = -a.p.alpha * a.p.c0 * muij;
-                piij = s[9] * piij * fast_rcp(T(0.5) * (D.rho + rhoj));
-            }
-            D.au += -piij * dw0; D.av += -piij * dw1; D.aw += -piij * dw2;
-        }
-        if (fl & (F_TVISC | F_EDAC)) {
-            // 2 rho_i rho_j / (rho_i + rho_j) / (r^2 + eps) (Vi2 + Vj2) / m_i (XIJ . DWIJ): shared by the physical
-            // viscosity (transport_velocity.py:363-384, times nu) and the pressure damping (edac.py:375,384-386, times edac_nu)
-            const T common = T(2.0) * (D.rho * rhoj) * rsum1 * D.mi1 * vsum * xdw * fast_rcp(r2 + g.eps);
-            if (fl & F_TVISC) {
-                const T tmp = a.p.nu * common;
-                D.au += tmp * vij0; D.av += tmp * vij1; D.aw += tmp * vij2;
-            }
-            if (fl & F_EDAC) {
-                const T vijdotdwij = dw0 * vij0 + dw1 * vij1 + dw2 * vij2;
-                D.ap += D.rho * fast_rcp(rhoj) * a.p.cs2 * s[9] * vijdotdwij; // :380-381
-                D.ap += a.p.enu * common * (D.p - s[7]);
-            }
-        }
-        if (INT && (fl & F_TAS)) { // transport_velocity.py:473-545, as FamTVF_T
-            const T ddi = (D.uh - D.u) * dw0 + (D.vh - D.v) * dw1 + (D.wh - D.w) * dw2;
-            const T ddj = (s[3] - s[0]) * dw0 + (s[4] - s[1]) * dw1 + (s[5] - s[2]) * dw2;
-            const T ci = D.rho * ddi, cj = rhoj * ddj;
-            const T tmp = T(0.5) * D.mi1 * vsum;
-            D.au += tmp * (ci * D.u + cj * s[0]);
-            D.av += tmp * (ci * D.v + cj * s[1]);
-            D.aw += tmp * (ci * D.w + cj * s[2]);
-        }
-        if (!INT && (fl & F_EXS)) { // basic_equations.py:290-295
-            T wij = pair_w<KK, UH>(g);
-            wij = pass ? wij : T(0.0);
-            const T tmp = -a.p.eps * s[9] * wij * fast_rcp(T(0.5) * (D.rho + rhoj));
-            D.ax += tmp * vij0; D.ay += tmp * vij1; D.az += tmp * vij2;
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        if (a.dflags & (F_EP | F_TVISC | F_TAV | F_TAS)) {
-            T gx = T(0.0), gy = T(0.0), gz = T(0.0);
-            if (a.dflags & F_EP) { // post_loop edac.py:345-351 / :480-488
-                T damp = T(1.0);
-                if (a.t < a.p.tdamp) damp = T(0.5) * (sin((-T(0.5) + a.t / a.p.tdamp) * M_PI) + T(1.0));
-                gx = a.p.gx * damp; gy = a.p.gy * damp; gz = a.p.gz * damp;
-            }
-            a.p.au[o] = D.au + gx; a.p.av[o] = D.av + gy; a.p.aw[o] = D.aw + gz;
-        }
-        if (INT && (a.dflags & F_EP)) { a.p.auhat[o] = D.auh; a.p.avhat[o] = D.avh; a.p.awhat[o] = D.awh; }
-        if (a.dflags & F_EDAC) a.p.ap[o] = D.ap;
-        if (!INT && (a.dflags & F_EXS)) { // post_loop basic_equations.py:297-300: with eps = 0 still ax = u (EDACStep moves x with it)
-            a.p.ax[o] = D.ax + D.u; a.p.ay[o] = D.ay + D.v; a.p.az[o] = D.az + D.w;
-        }
-    }
-};
-
-// EDAC records of the aggregated kernel under uniform h: k_pack layout 3 in its seven-piece form
-// [x y | z rho | u v | w p | Vj2 what | uhat vhat | m -] (112 B instead of the generic 128 B); the sixth piece is
-// read only where the artificial stress acts, the seventh (m: the pressure rate reads it) always.
-template <bool INT>
-__device__ __forceinline__ void load_record_edac(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12])
-{
-    const double2 *r2 = reinterpret_cast<const double2 *>(rj);
-    const double2 a0 = r2[0], a1 = r2[1], b0 = r2[2], b1 = r2[3], c0 = r2[4], e0 = r2[6];
-    pj.x = a0.x; pj.y = a0.y; pj.z = a1.x; pj.w = 0.0;
-    s[0] = b0.x; s[1] = b0.y; s[2] = b1.x; s[6] = a1.y; s[7] = b1.y; s[8] = 0.0; s[9] = e0.x; s[10] = c0.x; s[11] = 0.0;
-    s[3] = s[4] = 0.0; s[5] = c0.y;
-    if (INT && (fl & F_TAS)) {
-        const double2 d0 = r2[5];
-        s[3] = d0.x; s[4] = d0.y;
-    }
-}
-template <> __device__ __forceinline__ void load_record<FamEDAC_T<double, true>, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12]) { load_record_edac<true>(rj, fl, pj, s); }
-template <> __device__ __forceinline__ void load_record<FamEDAC_T<double, false>, true>(const double *__restrict__ rj, uint32_t fl, double4 &pj, double (&s)[12]) { load_record_edac<false>(rj, fl, pj, s); }
-
-// ---- ComputeAveragePressure (edac.py:62-79), with the density summations when they share its destination and
-//      group (EDACScheme without solids).  pavg = sum of the neighbours' p, nnbr = their number -- the pairs that
-//      pass the exact criterion, as FamNbr counts them -- and the division.  Records [x y z h | m p].
-enum { F_AVGP = 4 }; // next to F_SD = 1, F_TVFSD = 2
-template <class T> struct FamAvgP_T {
-    typedef T Real;
-    static constexpr bool PRED = true;
-    static constexpr uint32_t CF0 = F_TVFSD | F_AVGP;
-    static constexpr int MINB = 4;
-    static constexpr int NA = 2; // m p
-    static constexpr int NR = 6; // x y z h m p
-    struct Params { double *rho, *V, *pavg, *nnbr; };
-    struct Dest { T m, rho, V, ps, nn; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.m = a[0]; D.rho = T(0.0); D.V = T(0.0); D.ps = T(0.0); D.nn = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        if (fl & (F_SD | F_TVFSD)) {
-            PairGeomT<T> g;
-            pair_geom<KK, UH>(g, pi, pj, r2, a);
-            T wij = pair_w<KK, UH>(g);
-            wij = pass ? wij : T(0.0);
-            if (fl & F_SD) D.rho += s[0] * wij;
-            if (fl & F_TVFSD) { D.V += wij; D.rho += D.m * wij; }
-        }
-        if (fl & F_AVGP) { D.ps += pass ? s[1] : T(0.0); D.nn += pass ? T(1.0) : T(0.0); }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        if (a.dflags & (F_SD | F_TVFSD)) a.p.rho[o] = D.rho;
-        if (a.dflags & F_TVFSD) a.p.V[o] = D.V;
-        if (a.dflags & F_AVGP) {
-            a.p.pavg[o] = D.nn > T(0.0) ? D.ps / D.nn : D.ps; // post_loop :77-79
-            a.p.nnbr[o] = D.nn;
-        }
-    }
-};
-
-// ---- gas dynamics (pysph/sph/gas_dynamics/basic.py) -------------------------------------------------------------
-// The geometry of a pair at ONE smoothing length: WI / DWI / GHI of the reference are the kernel at the
-// destination's own h, DWJ at the source's (equation.py:214-224), where `gij` holds the pair at HIJ.  Under uniform h
-// the three lengths are one and `gij` is returned as it is.
-template <int KK, bool UH, class T, class A>
-__device__ __forceinline__ void pair_geom_at(PairGeomT<T> &g, const PairGeomT<T> &gij, T h, const A &a)
-{
-    g = gij;
-    if (!UH) {
-        g.hij = h;
-        g.h1 = SphKernel<KK>::CUTOFF ? T(1) / h : fast_rcp(h);
-        g.fac = kernel_norm((T)a.k.sigma, g.h1, a.k.dim);
-        g.q = g.rij * g.h1;
-    }
-}
-
-// SummationDensity (:74-219): the sums rho, arho, grhox..z, dwdh with WI / DWI / GHI and, in finish(), the whole
-// post_loop -- one Newton-Raphson step for h of every particle that has not converged, the 0.8 / 1.2 clamp, the
-// fallback, the convergence test and the group's convergence word -- in ONE launch.  The post_loop runs in fp64 whatever
-// the arithmetic of the sums.  A particle that converged in an EARLIER iteration is summed again every iteration and
-// leaves with the raw arho (its post_loop block is skipped); one that converges in this launch leaves with arho * omega:
-// the reference's behaviour, kept.  The new h goes to the property column only: the records every wavefront reads were
-// packed before the launch.  Records [x y z h | m u v w].
-enum { F_GSD = 1 };
-template <class T> struct FamGasSD_T {
-    typedef T Real;
-    static constexpr bool PRED = true; // every sum carries WI, DWI or GHI, masked for a pair outside the criterion
-    static constexpr uint32_t CF0 = F_GSD;
-    static constexpr int MINB = 4;
-    static constexpr int NA = 4; // m u v w
-    static constexpr int NR = 8;
-    static constexpr bool WAVE_SKIP = true;
-    struct Params {
-        double dim, k, htol;
-        int iterate, once;     // density_iterations, iterate_only_once
-        int skip;              // option gasd_skip in a repeated call: wavefronts without an unconverged destination leave early
-        double *araw;          // ... the raw arho of every row, as the last full sweep summed it (null: not kept)
-        const double *m, *h0;
-        double *h, *rho, *arho, *grhox, *grhoy, *grhoz, *dwdh, *div, *omega, *ah, *converged;
-        uint32_t *flag;        // the convergence word: 1 = some particle has not converged; flag[1]: wavefronts skipped
-    };
-    struct Dest { T u, v, w, rho, arho, gx, gy, gz, dwdh; };
-    // Option gasd_skip: with positions, velocities, masses and its own h unchanged since the previous sweep, a converged
-    // particle's sums come out the same again; what the reference's re-summation changes is arho (raw again, where the
-    // sweep in which the particle converged left arho * omega) and div.  The wave-tile kernel only.
-    template <class A> static __device__ __forceinline__ bool wave_skip(const A &a, uint32_t o, bool active)
-    {
-        if (!a.p.skip) return false;
-        if (!__all(!active || a.p.converged[o] == 1.0)) return false;
-        if ((threadIdx.x & 63) == 0) atomicAdd(a.p.flag + 1, 1u); // wavefronts that left here ("n_gasd_skipped")
-        if (active) {
-            const double ar = a.p.araw[o];
-            a.p.arho[o] = ar;
-            a.p.div[o] = -ar / a.p.rho[o];
-        }
-        return true;
-    }
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[1]; D.v = a[2]; D.w = a[3];
-        D.rho = D.arho = D.gx = D.gy = D.gz = D.dwdh = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        PairGeomT<T> gij, g;
-        pair_geom<KK, UH>(gij, pi, pj, r2, a);
-        pair_geom_at<KK, UH>(g, gij, pi.w, a);
-        T wi = pair_w<KK, UH>(g), tg = pair_gradfac<KK, UH>(g), ghi = pair_gradh<KK, UH>(g, a.k.dim);
-        wi = pass ? wi : T(0.0); tg = pass ? tg : T(0.0); ghi = pass ? ghi : T(0.0);
-        const T mj = s[0];
-        const T dw0 = tg * g.xij[0], dw1 = tg * g.xij[1], dw2 = tg * g.xij[2];
-        const T vijdotdwij = (D.u - s[1]) * dw0 + (D.v - s[2]) * dw1 + (D.w - s[3]) * dw2;
-        D.rho += mj * wi;
-        D.arho += mj * vijdotdwij;
-        D.gx += mj * dw0; D.gy += mj * dw1; D.gz += mj * dw2;
-        D.dwdh += mj * ghi;
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        const double rho = (double)D.rho, dwdh = (double)D.dwdh;
-        double arho = (double)D.arho;
-        if (a.p.araw) a.p.araw[o] = arho;
-        if (a.p.iterate && !(a.p.converged[o] == 1.0)) { // :150-213
-            const double mi = a.p.m[o], hi = a.p.h[o], hi0 = a.p.h0[o];
-            const double rhoi = mi / pow(hi / a.p.k, a.p.dim);
-            const double dhdrhoi = -hi / (a.p.dim * rho);
-            double omegai = 1.0 - dhdrhoi * dwdh;
-            if (omegai < 0) omegai = 1.0;
-            const double gradhi = 1.0 / omegai;
-            a.p.omega[o] = gradhi;
-            const double func = rhoi - rho, dfdh = omegai / dhdrhoi;
-            double hnew = hi - func / dfdh;
-            if (hnew > 1.2 * hi) hnew = 1.2 * hi;
-            else if (hnew < 0.8 * hi) hnew = 0.8 * hi;
-            if (hnew <= 1e-6 || gradhi < 1e-6) hnew = a.p.k * pow(mi / rho, 1.0 / a.p.dim);
-            const double diff = fabs(hnew - hi) / hi0;
-            if (!((diff < a.p.htol && omegai > 0) || a.p.once)) {
-                *a.p.flag = 1u; // the same constant from every lane that fails; the host reads the word once per call
-                a.p.h[o] = hnew;
-                a.p.converged[o] = 0.0;
-            } else {
-                arho *= gradhi;
-                a.p.ah[o] = arho * dhdrhoi;
-                a.p.converged[o] = 1.0;
-            }
-        }
-        a.p.rho[o] = rho;
-        a.p.arho[o] = arho;
-        a.p.grhox[o] = (double)D.gx; a.p.grhoy[o] = (double)D.gy; a.p.grhoz[o] = (double)D.gz;
-        a.p.dwdh[o] = dwdh;
-        a.p.div[o] = -arho / rho;
-    }
-};
-
-// MPMAccelerations (:356-483): everything its loop does in one sweep -- the grad-h pressure terms with DWI and DWJ (each
-// at its own h), the artificial viscosity and its heating under dot <= 0, the thermal conduction with the signal
-// velocity sqrt(|p_i - p_j| / RHOIJ), del2e and dt_cfl -- and the post_loop's sources of alpha1 / alpha2.  XIJ is
-// normalised (zeroed below RIJ = 1e-8) AFTER the kernel gradients were formed from it, as in the reference, so Fij is
-// the normalised XIJ against DWIJ at HIJ; the self pair adds to dt_cfl only.
-// Records [x y z h | u v w rho p cs e m omega alpha1 alpha2 -]: 128 B in fp64 (eight 16-B pieces), 64 B in fp32.
-enum { F_MPM = 1 };
-template <class T> struct FamMPM_T {
-    typedef T Real;
-    static constexpr bool PRED = true; // the sums carry a kernel gradient, masked outside the criterion; dt_cfl is selected
-    static constexpr uint32_t CF0 = F_MPM;
-    static constexpr int MINB = 3;
-    static constexpr int NA = 12; // u v w rho p cs e m omega alpha1 alpha2 pad
-    static constexpr int NR = 16;
-    struct Params {
-        T beta;
-        double sigma, alpha1_min, alpha2_min;
-        int update_alpha1, update_alpha2;
-        const double *h, *cs, *e, *div, *alpha1, *alpha2;
-        double *au, *av, *aw, *ae, *del2e, *dt_cfl, *aalpha1, *aalpha2;
-    };
-    struct Dest {
-        T u, v, w, rho, p, cs, e, al1, al2, pwi; // pwi = p_i / rho_i^2 omega_i
-        T au, av, aw, ae, del2e, dtc;
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[3]; D.p = a[4]; D.cs = a[5]; D.e = a[6];
-        D.al1 = a[9]; D.al2 = a[10];
-        D.pwi = a[4] / (a[3] * a[3]) * a[8];
-        D.au = D.av = D.aw = D.ae = D.del2e = D.dtc = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g, gi, gj;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        pair_geom_at<KK, UH>(gi, g, pi.w, a);
-        pair_geom_at<KK, UH>(gj, g, pj.w, a);
-        T tij = pair_gradfac<KK, UH>(g), ti = pair_gradfac<KK, UH>(gi), tj = pair_gradfac<KK, UH>(gj);
-        tij = pass ? tij : T(0.0); ti = pass ? ti : T(0.0); tj = pass ? tj : T(0.0);
-        const T mj = s[7], rhoj = s[3];
-        const T pjw = s[4] / (rhoj * rhoj) * s[8]; // p_j / rho_j^2 omega_j
-        const T cij = T(0.5) * (D.cs + s[5]);
-        // :412-420: the normalised interaction vector
-        const T rn = g.rij < T(1e-8) ? T(0.0) : g.rinv;
-        const T x0 = g.xij[0] * rn, x1 = g.xij[1] * rn, x2 = g.xij[2] * rn;
-        const T v0 = D.u - s[0], v1 = D.v - s[1], v2 = D.w - s[2];
-        const T dot = v0 * x0 + v1 * x1 + v2 * x2;
-        const T dwij0 = tij * g.xij[0], dwij1 = tij * g.xij[1], dwij2 = tij * g.xij[2];
-        const T Fij = x0 * dwij0 + x1 * dwij1 + x2 * dwij2;
-        const T rhoij1 = fast_rcp(T(0.5) * (D.rho + rhoj)); // 1 / RHOIJ
-        const T pdiff = fabs(D.p - s[4]);
-        const T vsig1 = T(0.5) * raw_max(T(2.0) * cij - a.p.beta * dot, T(0.0));
-        const T vsig2 = sqrt(pdiff * rhoij1);
-        const T cfl = cij + a.p.beta * dot;
-        D.dtc = (pass && cfl > D.dtc) ? cfl : D.dtc;
-        if (dot <= T(0.0)) { // :437-447
-            const T alpha1 = T(0.5) * (D.al1 + s[9]);
-            const T tmpv = mj * rhoij1 * alpha1 * vsig1 * dot;
-            D.au += tmpv * dwij0; D.av += tmpv * dwij1; D.aw += tmpv * dwij2;
-            D.ae += T(-0.5) * tmpv * dot * Fij;
-        }
-        // :455-461: the grad-h terms, DWI at h_i and DWJ at h_j
-        const T gsum = D.pwi * ti + pjw * tj;
-        D.au -= mj * gsum * g.xij[0]; D.av -= mj * gsum * g.xij[1]; D.aw -= mj * gsum * g.xij[2];
-        const T vijdotdwi = ti * (v0 * g.xij[0] + v1 * g.xij[1] + v2 * g.xij[2]);
-        D.ae += mj * D.pwi * vijdotdwi;
-        // :463-469: conduction and the Laplacian of e
-        const T alpha2 = T(0.5) * (D.al2 + s[10]);
-        const T eij = D.e - s[6];
-        D.ae += mj * rhoij1 * alpha2 * vsig2 * eij * Fij;
-        D.del2e += mj / rhoj * eij * fast_rcp(g.rij + g.eps) * Fij;
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        a.p.au[o] = (double)D.au; a.p.av[o] = (double)D.av; a.p.aw[o] = (double)D.aw; a.p.ae[o] = (double)D.ae;
-        const double del2e = (double)D.del2e;
-        a.p.del2e[o] = del2e;
-        a.p.dt_cfl[o] = (double)D.dtc;
-        double aa1 = 0.0, aa2 = 0.0; // :471-483
-        if (a.p.update_alpha1 || a.p.update_alpha2) {
-            const double hi = a.p.h[o];
-            const double tau = hi / (a.p.sigma * a.p.cs[o]);
-            if (a.p.update_alpha1) aa1 = (a.p.alpha1_min - a.p.alpha1[o]) / tau + fmax(-a.p.div[o], 0.0);
-            if (a.p.update_alpha2) aa2 = (a.p.alpha2_min - a.p.alpha2[o]) / tau + 0.01 * hi * fabs(del2e) / sqrt(a.p.e[o]);
-        }
-        a.p.aalpha1[o] = aa1; a.p.aalpha2[o] = aa2;
-    }
-};
-
-// ---- ADKE (gas_dynamics/basic.py:32-71, :274-353; boundary_equations.py) -----------------------------------------
-// SummationDensityADKE (:32-71): rho with WIJ at HIJ, arho with DWI at the destination's own h (which is its h0: the
-// host driver runs the reference's `h = h0` over the destinations before the records are packed), and in finish() the
-// post_loop: div, arho = 0, logrho.  The reduce hook -- the sum of logrho and the new h of every row -- is two further
-// launches behind this one (run_adke_sd).  Records [x y z h | m u v w]: 64 B in fp64 (four 16-B pieces), 32 B in fp32.
-// MINB 4, as FamGasSD_T, of which this is the shorter body: 105..128 VGPRs in fp64 under variable h (the only h it runs
-// with), 20 B of scratch in kernel id 10 alone.
-enum { F_ASD = 1 };
-template <class T> struct FamADKESD_T {
-    typedef T Real;
-    static constexpr bool PRED = true; // both sums are selected on the criterion
-    static constexpr uint32_t CF0 = F_ASD;
-    static constexpr int MINB = 4;
-    static constexpr int NA = 4; // m u v w
-    static constexpr int NR = 8;
-    struct Params { double *rho, *arho, *div, *logrho; };
-    struct Dest { T u, v, w, rho, arho; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[1]; D.v = a[2]; D.w = a[3];
-        D.rho = D.arho = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        PairGeomT<T> gij, g;
-        pair_geom<KK, UH>(gij, pi, pj, r2, a);
-        pair_geom_at<KK, UH>(g, gij, pi.w, a);
-        const T wij = pair_w<KK, UH>(gij), tg = pair_gradfac<KK, UH>(g);
-        const T mj = s[0];
-        const T vijdotdwi = tg * ((D.u - s[1]) * g.xij[0] + (D.v - s[2]) * g.xij[1] + (D.w - s[3]) * g.xij[2]);
-        D.rho += pass ? mj * wij : T(0.0);
-        D.arho += pass ? mj * vijdotdwi : T(0.0);
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        const double rho = (double)D.rho;
-        a.p.rho[o] = rho;
-        a.p.div[o] = -(double)D.arho / rho; // :59-62
-        a.p.arho[o] = 0.0;
-        a.p.logrho[o] = log(rho);
-    }
-};
-
-// ADKEAccelerations (:274-353): the pressure term, the Monaghan viscosity under XIJ.VIJ < 0 (HIJ, EPS, RHOIJ1) and the
-// conduction Hij of h, cs, div, e of both particles (RHOIJ), all with DWIJ at HIJ.  A source may be a wall row that no
-// fluid particle reached (rho = 0, cs = NaN: IdealGasEOS on WallBoundary's raw sums): it is never inside the criterion,
-// and the four increments are SELECTED on the criterion, not multiplied by a masked gradient, so that its NaN stays where
-// it is.  Records [x y z h | u v w rho p cs e m div -]: 112 B in fp64 (seven 16-B pieces), 64 B in fp32.
-// MINB 3, as FamMPM_T: 121..139 VGPRs in fp64 under variable h, no scratch; the budget of four blocks is 128.
-enum { F_ADKE = 1 };
-template <class T> struct FamADKE_T {
-    typedef T Real;
-    static constexpr bool PRED = true;
-    static constexpr uint32_t CF0 = F_ADKE;
-    static constexpr int MINB = 3;
-    static constexpr int NA = 9; // u v w rho p cs e m div
-    static constexpr int NR = 14;
-    struct Params {
-        T alpha, beta, g1, g2;
-        double *au, *av, *aw, *ae;
-    };
-    struct Dest {
-        T u, v, w, rho, cs, e, div, pib; // pib = p_i / rho_i^2
-        T au, av, aw, ae;
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[3]; D.cs = a[5]; D.e = a[6]; D.div = a[8];
-        D.pib = a[4] / (a[3] * a[3]);
-        D.au = D.av = D.aw = D.ae = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        const T tg = pair_gradfac<KK, UH>(g);
-        const T rhoj = s[3], mj = s[7];
-        const T pjb = s[4] / (rhoj * rhoj);
-        const T cij = T(0.5) * (D.cs + s[5]);
-        const T hi = pi.w, hj = pj.w;
-        // :319-322: thermal conduction
-        const T Hi = a.p.g1 * hi * D.cs + a.p.g2 * hi * hi * (fabs(D.div) - D.div);
-        const T Hj = a.p.g1 * hj * s[5] + a.p.g2 * hj * hj * (fabs(s[8]) - s[8]);
-        const T rhoij = T(0.5) * (D.rho + rhoj);
-        const T r2e = r2 + g.eps;
-        const T Hij = (Hi + Hj) * (D.e - s[6]) / (rhoij * r2e);
-        const T v0 = D.u - s[0], v1 = D.v - s[1], v2 = D.w - s[2];
-        const T xv = g.xij[0] * v0 + g.xij[1] * v1 + g.xij[2] * v2;
-        const T muij = g.hij * xv / r2e;
-        const T pi_v = muij * (a.p.beta * muij - a.p.alpha * cij) / rhoij; // :324-328
-        const T piij = xv < T(0.0) ? pi_v : T(0.0);
-        const T tmpv = D.pib + pjb + piij;
-        const T f = -mj * tmpv * tg;
-        const T vijdotdwij = tg * xv;
-        const T xijdotdwij = tg * (g.xij[0] * g.xij[0] + g.xij[1] * g.xij[1] + g.xij[2] * g.xij[2]);
-        const T de = T(0.5) * mj * (tmpv * vijdotdwij + T(2.0) * xijdotdwij * Hij);
-        D.au += pass ? f * g.xij[0] : T(0.0);
-        D.av += pass ? f * g.xij[1] : T(0.0);
-        D.aw += pass ? f * g.xij[2] : T(0.0);
-        D.ae += pass ? de : T(0.0);
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        a.p.au[o] = (double)D.au; a.p.av[o] = (double)D.av; a.p.aw[o] = (double)D.aw; a.p.ae[o] = (double)D.ae;
-    }
-};
-
-// WallBoundary (boundary_equations.py:5-48): the destination is a wall, the sources are the fluids.  Eleven sums with WI
-// at the wall row's own h (its h0: the host driver runs `h = h0` first, as for SummationDensityADKE); finish() is the
-// post_loop: every sum over wij where wij > 1e-30 and h = htmp / wij there, else the raw sums and h stays h0.  The
-// records are FamADKE_T's, [x y z h | u v w rho p cs e m div -], read on the fluids' side only.
-// MINB 3: eleven accumulators; up to 136 VGPRs in fp64 under variable h, no scratch; the budget of four blocks is 128.
-enum { F_GWALL = 1 };
-template <class T> struct FamGasWall_T {
-    typedef T Real;
-    static constexpr bool PRED = true; // every sum carries WI, selected on the criterion
-    static constexpr uint32_t CF0 = F_GWALL;
-    static constexpr int MINB = 3;
-    static constexpr int NA = 9; // u v w rho p cs e m div
-    static constexpr int NR = 14;
-    struct Params { double *wij, *p, *u, *v, *w, *m, *rho, *e, *cs, *div, *htmp, *h; };
-    struct Dest { T wij, q[9], htmp; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *, const A &, uint32_t)
-    {
-        D.wij = D.htmp = T(0.0);
-        for (int k = 0; k < 9; k++) D.q[k] = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        PairGeomT<T> gij, g;
-        pair_geom<KK, UH>(gij, pi, pj, r2, a);
-        pair_geom_at<KK, UH>(g, gij, pi.w, a);
-        T wi = pair_w<KK, UH>(g);
-        wi = pass ? wi : T(0.0);
-        D.wij += wi;
-#pragma unroll
-        for (int k = 0; k < 9; k++) D.q[k] += pass ? s[k] * wi : T(0.0);
-        D.htmp += pass ? pj.w * wi : T(0.0);
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        const double wij = (double)D.wij, htmp = (double)D.htmp;
-        const bool reached = wij > 1e-30;
-        double q[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) q[k] = reached ? (double)D.q[k] / wij : (double)D.q[k];
-        a.p.wij[o] = wij;
-        a.p.u[o] = -q[0]; a.p.v[o] = -q[1]; a.p.w[o] = -q[2]; // (d_u -= s_u WI)
-        a.p.rho[o] = q[3]; a.p.p[o] = q[4]; a.p.cs[o] = q[5]; a.p.e[o] = q[6]; a.p.m[o] = q[7]; a.p.div[o] = q[8];
-        a.p.htmp[o] = htmp;
-        if (reached) a.p.h[o] = htmp / wij;
-    }
-};
-
-// ---- Godunov SPH (pysph/sph/gas_dynamics/gsph.py, riemann_solver.py) --------------------------------------------
-// GSPHGradients (:61-101): the twelve sums px..pz ux..uz vx..vz wx..wz with DWI, one launch; finish() writes all of
-// them, which is the reference's initialize.  Records [x y z h | p u v w m/rho -].
-enum { F_GGRAD = 1 };
-template <class T> struct FamGSPHGrad_T {
-    typedef T Real;
-    static constexpr bool PRED = true; // every sum carries DWI, masked for a pair outside the criterion
-    static constexpr uint32_t CF0 = F_GGRAD;
-    static constexpr int MINB = 3; // (4 spills twelve VGPRs in fp64 under variable h: DESIGN.md section 7h)
-    static constexpr int NA = 5; // p u v w m/rho
-    static constexpr int NR = 10;
-    struct Params { double *g[12]; }; // px py pz ux uy uz vx vy vz wx wy wz
-    struct Dest { T q[4]; T g[12]; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        for (int k = 0; k < 4; k++) D.q[k] = a[k];
-        for (int k = 0; k < 12; k++) D.g[k] = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        PairGeomT<T> gij, g;
-        pair_geom<KK, UH>(gij, pi, pj, r2, a);
-        pair_geom_at<KK, UH>(g, gij, pi.w, a);
-        T tg = pair_gradfac<KK, UH>(g);
-        tg = pass ? tg : T(0.0);
-        const T dw[3] = {tg * g.xij[0], tg * g.xij[1], tg * g.xij[2]};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const T tmp = s[4] * (s[i] - D.q[i]);
-#pragma unroll
-            for (int j = 0; j < 3; j++) D.g[3 * i + j] += tmp * dw[j];
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-#pragma unroll
-        for (int k = 0; k < 12; k++) a.p.g[k][o] = (double)D.g[k];
-    }
-};
-
-// The Riemann solvers of riemann_solver.py, in the arithmetic of the sweep.  Each returns 0 with (pstar, ustar) set, or 1
-// where the reference's returns 1 WITHOUT writing its result: the caller's zero-initialised pair stands.  No printing.
-template <class T> __device__ __forceinline__ T gs_pow(T x, T y);
-template <> __device__ __forceinline__ double gs_pow<double>(double x, double y) { return pow(x, y); }
-template <> __device__ __forceinline__ float gs_pow<float>(float x, float y) { return powf(x, y); }
-template <class T> __device__ __forceinline__ T gs_sign(T x, T y) { return y >= T(0) ? fabs(x) : -fabs(x); } // SIGN :12-16
-template <class T> __device__ __forceinline__ T gs_max(T x, T y) { return y > x ? y : x; } // max(x, y) as Python and Cython spell it: x unless y > x
-template <class T> __device__ __forceinline__ T gs_min(T x, T y) { return y < x ? y : x; }
-
-template <class T> __device__ __forceinline__ int gs_van_leer(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, int niter, T tol, T &ps, T &us)
-{ // :54-151
-    if (rhol < T(0) || rhor < T(0) || pl < T(0) || pr < T(0)) { ps = T(0); us = T(0); return 1; }
-    const T gamma2 = T(1) + gamma, gamma1 = T(0.5) * gamma2 / gamma, smallp = T(1e-25);
-    T wl = T(0), wr = T(0), zl, zr, ustar_l, ustar_r;
-    const T Vl = T(1) / rhol, Vr = T(1) / rhor;
-    const T cl = sqrt(gamma * pl * rhol), cr = sqrt(gamma * pr * rhor);
-    T pstar = pr - pl - cr * (ur - ul);
-    pstar = pl + pstar * cl / (cl + cr);
-    pstar = gs_max(pstar, smallp);
-    for (int it = 0; it < niter; it++) {
-        const T pstar_old = pstar;
-        wl = T(1) + gamma1 * (pstar - pl) / pl;
-        wl = cl * sqrt(wl);
-        wr = T(1) + gamma1 * (pstar - pr) / pr;
-        wr = cr * sqrt(wr);
-        zl = T(4) * Vl * wl * wl;
-        zl = -zl * wl / (zl - gamma2 * (pstar - pl));
-        zr = T(4) * Vr * wr * wr;
-        zr = zr * wr / (zr - gamma2 * (pstar - pr));
-        ustar_l = ul - (pstar - pl) / wl;
-        ustar_r = ur + (pstar - pr) / wr;
-        pstar = pstar + (ustar_r - ustar_l) * (zl * zr) / (zr - zl);
-        pstar = gs_max(smallp, pstar);
-        if (fabs(pstar - pstar_old) / pstar < tol) break;
-    }
-    ustar_l = ul - (pstar - pl) / wl;
-    ustar_r = ur + (pstar - pr) / wr;
-    ps = pstar;
-    us = T(0.5) * (ustar_l + ustar_r);
-    return 0; // (not converged: the reference returns 1 but has written its result)
-}
-
-template <class T> __device__ __forceinline__ void gs_prefun(T p, T dk, T pk, T ck, T g1, T g2, T g4, T g5, T g6, T &f, T &fd)
-{ // :154-173
-    if (p <= pk) {
-        const T pratio = p / pk;
-        f = g4 * ck * (gs_pow(pratio, g1) - T(1));
-        fd = (T(1) / (dk * ck)) * gs_pow(pratio, -g2);
-    } else {
-        const T ak = g5 / dk, bk = g6 * pk;
-        const T qrt = sqrt(ak / (bk + p));
-        f = (p - pk) * qrt;
-        fd = (T(1) - T(0.5) * (p - pk) / (bk + p)) * qrt;
-    }
-}
-
-template <class T> __device__ __forceinline__ int gs_exact(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, int niter, T tol, T &ps, T &us)
-{ // :176-286
-    const T tmp1 = T(1) / (T(2) * gamma), tmp2 = T(1) / (gamma - T(1)), tmp3 = T(1) / (gamma + T(1));
-    const T gamma1 = (gamma - T(1)) * tmp1, gamma2 = (gamma + T(1)) * tmp1, gamma3 = T(2) * gamma * tmp2, gamma4 = T(2) * tmp2,
-            gamma5 = T(2) * tmp3, gamma6 = tmp3 / tmp2, gamma7 = T(0.5) * (gamma - T(1));
-    const T cl = sqrt(gamma * pl / rhol), cr = sqrt(gamma * pr / rhor);
-    if (gamma4 * (cl + cr) <= (ur - ul)) return 1; // vacuum
-    const T cup = T(0.25) * (rhol + rhor) * (cl + cr);
-    T ppv = T(0.5) * (pl + pr) + T(0.5) * (ul - ur) * cup;
-    const T pmin = gs_min(pl, pr), pmax = gs_max(pl, pr), qmax = pmax / pmin;
-    ppv = gs_max(T(0), ppv);
-    T pm;
-    if (qmax <= T(2) && pmin <= ppv && ppv <= pmax) {
-        pm = ppv;
-    } else if (ppv < pmin) {
-        const T pq = gs_pow(pl / pr, gamma1);
-        const T um = (pq * ul / cl + ur / cr + gamma4 * (pq - T(1))) / (pq / cl + T(1) / cr);
-        const T ptl = T(1) + gamma7 * (ul - um) / cl, ptr = T(1) + gamma7 * (um - ur) / cr;
-        pm = T(0.5) * (pl * gs_pow(ptl, gamma3) + pr * gs_pow(ptr, gamma3));
-    } else {
-        const T gel = sqrt((gamma5 / rhol) / (gamma6 * pl + ppv)), ger = sqrt((gamma5 / rhor) / (gamma6 * pr + ppv));
-        pm = (gel * pl + ger * pr - (ur - ul)) / (gel + ger);
-    }
-    T pold = pm, p = T(0), fl = T(0), fld = T(0), fr = T(0), frd = T(0);
-    const T udiff = ur - ul;
-    int last = 0; // the reference's loop index after the loop
-    for (int i = 0; i < niter; i++) {
-        last = i;
-        gs_prefun(pold, rhol, pl, cl, gamma1, gamma2, gamma4, gamma5, gamma6, fl, fld);
-        gs_prefun(pold, rhor, pr, cr, gamma1, gamma2, gamma4, gamma5, gamma6, fr, frd);
-        p = pold - (fl + fr + udiff) / (fld + frd);
-        const T change = T(2) * fabs((p - pold) / (p + pold));
-        if (change <= tol) break;
-        pold = p;
-    }
-    if (last == niter - 1) return 1; // (also when it converged in the last iteration allowed: kept)
-    ps = p;
-    us = T(0.5) * (ul + ur + fr - fl);
-    return 0;
-}
-
-template <class T> __device__ __forceinline__ int gs_ducowicz(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, T &ps, T &us)
-{ // :431-525
-    // a, b, c and d are differences of products of order (rho cs)^2 that cancel down to order rho p: a fused multiply-add
-    // rounds them otherwise than the reference's separately rounded products, and at rho = 1e10, p = 1e20 that moved pstar
-    // by more than four times the reference's own distance from the exact value.  Every product here is rounded on its own.
-#pragma clang fp contract(off)
-    const T al = T(0.5) * (gamma + T(1)), ar = al;
-    const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
-    const T umin = ur - T(0.5) * csr / ar, umax = ul + T(0.5) * csl / al;
-    const T plmin = pl - T(0.25) * rhol * csl * csl / al, prmin = pr - T(0.25) * rhor * csr * csr / ar;
-    const T bl = rhol * al, br = rhor * ar;
-    T a = (br - bl) * (prmin - plmin), b = br * umin * umin - bl * umax * umax, c = br * umin - bl * umax;
-    const T d = br * bl * (umin - umax) * (umin - umax);
-    auto pstar_of = [&](T ustar) {
-#pragma clang fp contract(off)
-        const T v = T(0.5) * (plmin + prmin + br * fabs(ustar - umin) * (ustar - umin) - bl * fabs(ustar - umax) * (ustar - umax));
-        return gs_max(v, T(0));
-    };
-    T dd = sqrt(gs_max(T(0), d - a));
-    T ustar = (b + prmin - plmin) / (c - gs_sign(dd, umax - umin));
-    if ((ustar - umin) >= T(0) && (ustar - umax) <= T(0)) { ps = pstar_of(ustar); us = ustar; return 0; } // case A
-    dd = sqrt(gs_max(T(0), d + a));
-    ustar = (b - prmin + plmin) / (c - gs_sign(dd, umax - umin));
-    if ((ustar - umin) <= T(0) && (ustar - umax) >= T(0)) { ps = pstar_of(ustar); us = ustar; return 0; } // case B
-    a = (bl + br) * (plmin - prmin);
-    b = bl * umax + br * umin;
-    c = T(1) / (bl + br);
-    dd = sqrt(gs_max(T(0), a - d));
-    ustar = (b + dd) * c;
-    if ((ustar - umin) >= T(0) && (ustar - umax) >= T(0)) { ps = pstar_of(ustar); us = ustar; return 0; } // case C
-    dd = sqrt(gs_max(T(0), -a - d));
-    ustar = (b - dd) * c; // case D
-    ps = pstar_of(ustar);
-    us = ustar;
-    return 0;
-}
-
-template <class T> __device__ __forceinline__ int gs_hllc(T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, T &ps, T &us)
-{ // :622-717
-    const T gamma1 = T(1) / (gamma - T(1));
-    const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
-    const T ulr = (rrhol * ul + rrhor * ur) / (rrhol + rrhor);
-    const T vl = ul - ulr, vr = ur - ulr;
-    const T csl = sqrt(gamma * pl / rhol), csr = sqrt(gamma * pr / rhor);
-    const T cslr = (rrhol * csl + rrhor * csr) / (rrhol + rrhor);
-    const T sl = gs_min(vl - csl, T(0) - cslr), sr = gs_max(vr + csr, T(0) + cslr);
-    T sm = rhor * vr * (sr - vr) - rhol * vl * (sl - vl) + pl - pr;
-    sm /= (rhor * (sr - vr) - rhol * (sl - vl));
-    const T phat = rhol * (vl - sl) * (vl - sm) + pl;
-    const T el = pl * gamma1 / rhol, El = rhol * (el + T(0.5) * ul * ul);
-    const T er = pr * gamma1 / rhor, Er = rhor * (er + T(0.5) * ur * ur);
-    const T Ml = rhol * ul, Mr = rhor * ur;
-    T pstar, ustar;
-    if (sl > T(0)) {
-        pstar = pl; ustar = ul;
-    } else if (sl <= T(0) && T(0) < sm) {
-        const T mstar = T(1) / (sl - sm) * ((sl - vl) * Ml + (phat - pl));
-        const T estar = T(1) / (sl - sm) * ((sl - vl) * El - pl * vl + phat * sm);
-        pstar = sm * mstar + phat;
-        ustar = sm * estar + (sm + ulr) * phat;
-        ustar /= pstar;
-    } else if (sm <= T(0) && T(0) < sr) {
-        const T mstar = T(1) / (sr - sm) * ((sr - vr) * Mr + (phat - pr));
-        const T estar = T(1) / (sr - sm) * ((sr - vr) * Er - pr * vr + phat * sm);
-        pstar = sm * mstar + phat;
-        ustar = sm * estar + (sm + ulr) * phat;
-        ustar /= pstar;
-    } else if (sr < T(0)) {
-        pstar = pr; ustar = ur;
-    } else {
-        return 1; // "Incorrect wave speeds" (a NaN among them)
-    }
-    ps = pstar; us = ustar;
-    return 0;
-}
-
-// riemann_solve (:19-44): `method` is a launch parameter, uniform over the wavefront
-template <class T> __device__ __forceinline__ int gs_riemann(int method, T rhol, T rhor, T pl, T pr, T ul, T ur, T gamma, int niter, T tol, T &ps, T &us)
-{
-    switch (method) {
-    case 0: ps = T(0.5) * (pl + pr); us = T(0.5) * (ul + ur); return 0; // non_diffusive :47-51
-    case 1: return gs_van_leer(rhol, rhor, pl, pr, ul, ur, gamma, niter, tol, ps, us);
-    case 2: return gs_exact(rhol, rhor, pl, pr, ul, ur, gamma, niter, tol, ps, us);
-    case 3: return gs_hllc(rhol, rhor, pl, pr, ul, ur, gamma, ps, us);
-    case 4: return gs_ducowicz(rhol, rhor, pl, pr, ul, ur, gamma, ps, us);
-    case 5: { // hlle :788-851
-        const T gamma1 = T(1) / (gamma - T(1));
-        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
-        const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
-        const T cslr = (rrhol * csl + rrhor * csr) / (rrhol + rrhor);
-        const T sl = gs_min(ul - csl, -cslr), sr = gs_max(ur + csr, +cslr);
-        const T smax = gs_max(sl, sr), smin = gs_min(sl, sr);
-        const T El = pl * gamma1 / rhol + T(0.5) * ul * ul, Er = pr * gamma1 / rhor + T(0.5) * ur * ur;
-        const T pstar = (smax * pl - smin * pr) / (smax - smin) + smax * smin / (smax - smin) * (ur - ul);
-        const T ustar = (smax * pl * ul - smin * pr * ur) / (smax - smin) + smax * smin / (smax - smin) * (Er - El);
-        ps = pstar; us = ustar / pstar;
-        return 0;
-    }
-    case 6: { // roe :528-572
-        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
-        const T denominator = T(1) / (rrhor + rrhol);
-        const T plr = (rrhol * pl + rrhor * pr) * denominator;
-        const T vlr = (rrhol / rhol + rrhor / rhor) * denominator;
-        const T ulr = (rrhol * ul + rrhor * ur) * denominator;
-        const T cslr = sqrt(gamma * plr / vlr), cslr1 = T(1) / cslr;
-        ps = plr - T(0.5) * (ur - ul) * cslr;
-        us = ulr - T(0.5) * (pr - pl) * cslr1;
-        return 0;
-    }
-    case 7: { // llxf :575-619
-        const T gamma1 = T(1) / (gamma - T(1));
-        const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
-        const T cslr = gs_max(csr, csl);
-        const T El = pl * gamma1 / rhol + T(0.5) * ul * ul, Er = pr * gamma1 / rhor + T(0.5) * ur * ur;
-        const T pstar = T(0.5) * (pl + pr - cslr * (ur - ul));
-        ps = pstar;
-        us = T(1) / pstar * (T(0.5) * ((pl * ul + pr * ur) - cslr * (Er - El)));
-        return 0;
-    }
-    case 8: { // hllc_ball :720-785
-        const T gamma1 = T(0.5) * (gamma + T(1)) / gamma;
-        const T csl = sqrt(gamma * pl / rhol), csr = sqrt(gamma * pr / rhor), cslr = T(0.5) * (csl + csr);
-        const T rholr = T(0.5) * (rhol + rhor);
-        T pstar = T(0.5) * (pl + pr - rholr * cslr * (ur - ul));
-        const T ustar = T(0.5) * (ul + ur - T(1) / (rholr * cslr) * (pr - pl));
-        const T Hl = pstar / pl, Hr = pstar / pr;
-        T ql = T(1), qr = T(1);
-        if (Hl > T(1)) ql = sqrt(T(1) + gamma1 * (Hl - T(1)));
-        if (Hr > T(1)) qr = sqrt(T(1) + gamma1 * (Hr - T(1)));
-        const T Sl = ul - csl * ql, Sr = ur + csr * qr;
-        const T pstar_l = pl + rhol * (ul - Sl) * (ul - ustar), pstar_r = pr + rhor * (ur - Sr) * (ur - ustar);
-        ps = T(0.5) * (pstar_l + pstar_r);
-        us = ustar;
-        return 0;
-    }
-    case 9: { // hll_ball :854-913
-        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
-        const T denominator = T(1) / (rrhor + rrhol);
-        const T csl = sqrt(gamma * pl / rhol), csr = sqrt(gamma * pr / rhor);
-        const T eta = T(0.5) * (gamma - T(1)) * (rrhor * rrhol) * denominator * denominator;
-        const T betal = fabs(ul), betar = fabs(ur);
-        const T ulr = (rrhol * ul + rrhor * ur) / (rrhol * rrhor);
-        const T cslr2 = (rrhol * csl * csl + rrhor * csr * csr) / (rrhol * rrhor);
-        const T cslr = sqrt(cslr2 + eta * (betar - betal) * (betar - betal));
-        const T Sl = gs_min(ulr - cslr, ul - csl), Sr = gs_max(ulr + cslr, ur + csr);
-        const T ustar = (Sr * Sl * (rhor - rhol) + rhol * ul * Sr - rhor * ur * Sl) / (rhol * (ul - Sl) + rhor * (Sr - ur));
-        T pstar = pr * (ustar - Sl) - pl * (ustar - Sr) + rhor * ur * (ustar - Sl) * (ur - Sr) - rhol * ul * (ustar - Sr) * (ul - Sl);
-        ps = pstar / (Sr - Sl);
-        us = ustar;
-        return 0;
-    }
-    case 10: { // hllsy :916-972
-        const T gamma1 = T(1) / (gamma - T(1));
-        const T rrhol = sqrt(rhol), rrhor = sqrt(rhor);
-        const T denominator = T(1) / (rrhor + rrhol);
-        const T csl = sqrt(gamma * pl * rhol), csr = sqrt(gamma * pr * rhor);
-        const T cslr = denominator * (rrhol * csl + rrhor * csr);
-        const T bl = gs_max(csl, cslr), br = gs_max(csr, cslr);
-        const T wl = br / (bl + br), wr = bl / (bl + br), wlr = bl * br / (bl + br);
-        const T El = pl * gamma1 / rhol + T(0.5) * ul * ul, Er = pr * gamma1 / rhor + T(0.5) * ur * ur;
-        const T pstar = wl * pl + wr * pr - wlr * (ur - ul);
-        const T ustar = wl * (pl * ul) + wr * (pr * ur) - wlr * (Er - El);
-        ps = pstar; us = ustar / pstar;
-        return 0;
-    }
-    default: return 0; // (riemann_solve falls through: the result stays as it was)
-    }
-}
-
-template <class T> __device__ __forceinline__ T gs_sgn(T x) { return T((x > T(0)) - (x < T(0))); }
-template <class T> __device__ __forceinline__ T gs_monotonicity_min(T _x1, T _x2, T _x3)
-{ // gsph.py:34-58
-    const T x1 = T(2) * fabs(_x1), x2 = fabs(_x2), x3 = T(2) * fabs(_x3);
-    const T sx1 = gs_sgn(_x1), sx2 = gs_sgn(_x2), sx3 = gs_sgn(_x3);
-    if (sx1 != sx2 || sx2 != sx3) return T(0);
-    T m;
-    if (x2 < x1) m = x3 < x2 ? x3 : x2;
-    else m = x3 < x1 ? x3 : x1;
-    return sx1 * m;
-}
-
-// GSPHAcceleration (:148-541): the whole loop in one sweep -- local frame, specific-volume interpolation, monotonicity
-// limiter, left and right states with their fallbacks, the Riemann solve (and the second one of `hybrid`), au av aw ae with
-// DWI and DWJ each at its own h, the ADKE conduction with DWIJ.  Solver, limiter, interpolation, hybrid and conduction are
-// launch parameters: branches on them are uniform over the wavefront.  A pair whose solve fails contributes with the zero
-// pair and adds one to a device word.  Not PRED: the body is long and, for two solvers, iterates; lanes without a hit wait.
-// Records [x y z h | u v w rho p cs m e div grhox grhoy grhoz px py pz ux uy+vx uz+wx vy vz+wy wz -]: a velocity gradient is
-// read through eij . G . eij only, so its six symmetric sums are formed once at packing (k_pack, derived 6).
-enum { F_GSPH = 1 };
-template <class T> struct FamGSPH_T {
-    typedef T Real;
-    static constexpr bool PRED = false;
-    static constexpr uint32_t CF0 = F_GSPH;
-    static constexpr int MINB = 2;
-    static constexpr int NA = 21;
-    static constexpr int NR = 26;
-    struct Params {
-        T g1, g2, gamma, tol, blend; // blend = exp(-blend_alpha t / tf), computed by the host once per launch
-        int monotonicity, rsolver, interpolation, interface_zero, hybrid, niter, conduction;
-        double *au, *av, *aw, *ae;
-        unsigned long long *fail;
-    };
-    struct Dest {
-        T u, v, w, rho, p, cs, e, div, gr[3], gp[3], gv[6];
-        T au, av, aw, ae;
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[3]; D.p = a[4]; D.cs = a[5]; D.e = a[7]; D.div = a[8];
-        for (int k = 0; k < 3; k++) { D.gr[k] = a[9 + k]; D.gp[k] = a[12 + k]; }
-        for (int k = 0; k < 6; k++) D.gv[k] = a[15 + k];
-        D.au = D.av = D.aw = D.ae = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t, const A &a, bool pass = true)
-    {
-        if (!pass) return;
-        PairGeomT<T> g, gi, gj;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        pair_geom_at<KK, UH>(gi, g, pi.w, a);
-        pair_geom_at<KK, UH>(gj, g, pj.w, a);
-        const T ti = pair_gradfac<KK, UH>(gi), tj = pair_gradfac<KK, UH>(gj); // DWI = ti XIJ, DWJ = tj XIJ
-        const T hi = pi.w, hj = pj.w, RIJ = g.rij, dt = (T)a.dt;
-        T e0 = T(0), e1 = T(0), e2 = T(0), sij; // :237-247
-        if (RIJ < T(1e-14)) {
-            sij = T(1) / (RIJ + g.eps);
-        } else {
-            sij = T(1) / RIJ;
-            e0 = g.xij[0] * sij; e1 = g.xij[1] * sij; e2 = g.xij[2] * sij;
-        }
-        const T vl = s[0] * e0 + s[1] * e1 + s[2] * e2;
-        const T vr = D.u * e0 + D.v * e1 + D.w * e2;
-        const T csi = D.cs, csj = s[5], rhoi = D.rho, rhoj = s[3], p_i = D.p, p_j = s[4];
-        // gradients in the local coordinate system (:254-284)
-        T rsi = D.gr[0] * e0 + D.gr[1] * e1 + D.gr[2] * e2;
-        T rsj = s[9] * e0 + s[10] * e1 + s[11] * e2;
-        T psi = D.gp[0] * e0 + D.gp[1] * e1 + D.gp[2] * e2;
-        T psj = s[12] * e0 + s[13] * e1 + s[14] * e2;
-        T vsi = e0 * e0 * D.gv[0] + e0 * e1 * D.gv[1] + e0 * e2 * D.gv[2] + e1 * e1 * D.gv[3] + e1 * e2 * D.gv[4] + e2 * e2 * D.gv[5];
-        T vsj = e0 * e0 * s[15] + e0 * e1 * s[16] + e0 * e2 * s[17] + e1 * e1 * s[18] + e1 * e2 * s[19] + e2 * e2 * s[20];
-        // interpolate (:429-541) with sij = RIJ, gri_eij = rsi, grj_eij = rsj
-        T vij_i, vij_j, sstar = T(0);
-        {
-            const T Vi = T(1) / rhoi, Vj = T(1) / rhoj;
-            const T hij = T(0.5) * (hi + hj);
-            if (a.p.interpolation == 0) {
-                vij_i = T(1) / (rhoi * rhoi);
-                vij_j = T(1) / (rhoj * rhoj);
-            } else if (a.p.interpolation == 1) {
-                const T cij = RIJ < T(1e-8) ? T(0) : (Vi - Vj) / RIJ;
-                const T dij = T(0.5) * (Vi + Vj);
-                vij_i = T(0.25) * hi * hi * cij * cij + dij * dij;
-                vij_j = T(0.25) * hj * hj * cij * cij + dij * dij;
-                if (!a.p.interface_zero) {
-                    const T vij = T(0.5) * (vij_i + vij_j);
-                    sstar = T(0.5) * hij * hij * cij * dij / vij;
-                }
-            } else {
-                const T Vip = T(-1) / (rhoi * rhoi) * rsi, Vjp = T(-1) / (rhoj * rhoj) * rsj;
-                T aij = T(0), bij = T(0), cij = T(0), dij = T(0.5) * (Vi + Vj);
-                if (!(RIJ < T(1e-8))) {
-                    aij = T(-2) * (Vi - Vj) / (RIJ * RIJ * RIJ) + (Vip + Vjp) / (RIJ * RIJ);
-                    bij = T(0.5) * (Vip - Vjp) / RIJ;
-                    cij = T(1.5) * (Vi - Vj) / RIJ - T(0.25) * (Vip + Vjp);
-                    dij = T(0.5) * (Vi + Vj) - T(0.125) * (Vip - Vjp) * RIJ;
-                }
-                const T hi2 = hi * hi, hj2 = hj * hj, hi4 = hi2 * hi2, hj4 = hj2 * hj2, hi6 = hi4 * hi2, hj6 = hj4 * hj2;
-                vij_i = T(15.0 / 64.0) * hi6 * aij * aij + T(3.0 / 16.0) * hi4 * (T(2) * aij * cij + bij * bij) +
-                        T(0.25) * hi2 * (T(2) * bij * dij + cij * cij) + dij * dij;
-                vij_j = T(15.0 / 64.0) * hj6 * aij * aij + T(3.0 / 16.0) * hj4 * (T(2) * aij * cij + bij * bij) +
-                        T(0.25) * hj2 * (T(2) * bij * dij + cij * cij) + dij * dij;
-                if (!a.p.interface_zero) {
-                    const T hij2 = hij * hij, hij4 = hij2 * hij2;
-                    const T vij = T(0.5) * (vij_i + vij_j);
-                    sstar = (T(15.0 / 32.0) * hij4 * hij2 * aij * bij + T(3.0 / 8.0) * hij4 * (aij * dij + bij * cij) +
-                             T(0.5) * hij2 * cij * dij) / vij;
-                }
-            }
-        }
-        // monotonicity (:293-349)
-        if (a.p.monotonicity == 0) {
-            rsi = rsj = psi = psj = vsi = vsj = T(0);
-        } else if (a.p.monotonicity == 1) {
-            if (vsi * vsj < T(0)) { vsi = T(0); vsj = T(0); }
-            if (gs_min(csi, csj) < T(3) * (vl - vr)) rsi = rsj = psi = psj = vsi = vsj = T(0); // first order near a shock
-        } else if (a.p.monotonicity == 2) {
-            if (RIJ > T(1e-14)) {
-                const T qijr = rhoi - rhoj, qijp = p_i - p_j, qiju = vr - vl;
-                T delr = rsi * RIJ, delp = psi * RIJ, delv = vsi * RIJ;
-                rsi = gs_monotonicity_min(qijr, delr, T(2) * delr - qijr) / RIJ;
-                psi = gs_monotonicity_min(qijp, delp, T(2) * delp - qijp) / RIJ;
-                vsi = gs_monotonicity_min(qiju, delv, T(2) * delv - qiju) / RIJ;
-                delr = rsj * RIJ; delp = psj * RIJ; delv = vsj * RIJ;
-                rsj = gs_monotonicity_min(qijr, delr, T(2) * delr - qijr) / RIJ;
-                psj = gs_monotonicity_min(qijp, delp, T(2) * delp - qijp) / RIJ;
-                vsj = gs_monotonicity_min(qiju, delv, T(2) * delv - qiju) / RIJ;
-            } else if (RIJ < T(1e-14)) {
-                rsi = rsj = psi = psj = vsi = vsj = T(0);
-            }
-        }
-        // the states either side of the interface (:351-376)
-        sstar *= T(2);
-        const T fj = T(1) - csj * dt * sij + sstar, fi = T(1) - csi * dt * sij + sstar;
-        T rhol = rhoj + T(0.5) * rsj * RIJ * fj;
-        T rhor = rhoi - T(0.5) * rsi * RIJ * fi;
-        if (rhol < T(0)) rhol = rhoj;
-        if (rhor < T(0)) rhor = rhoi;
-        T pl = p_j + T(0.5) * psj * RIJ * fj;
-        T pr = p_i - T(0.5) * psi * RIJ * fi;
-        if (pl < T(0)) pl = p_j;
-        if (pr < T(0)) pr = p_i;
-        const T ul = vl + T(0.5) * vsj * RIJ * fj;
-        const T ur = vr - T(0.5) * vsi * RIJ * fi;
-        T pstar = T(0), ustar = T(0);
-        int failed = gs_riemann(a.p.rsolver, rhol, rhor, pl, pr, ul, ur, a.p.gamma, a.p.niter, a.p.tol, pstar, ustar);
-        if (a.p.hybrid) { // :388-396: the second solve writes into the result of the first
-            T pstar2 = pstar, ustar2 = ustar;
-            failed += gs_riemann(10, rhoj, rhoi, pl, pr, vl, vr, a.p.gamma, a.p.niter, a.p.tol, pstar2, ustar2);
-            ustar = ustar + a.p.blend * (ustar2 - ustar);
-            pstar = pstar + a.p.blend * (pstar2 - pstar);
-        }
-        if (failed) atomicAdd(a.p.fail, 1ull);
-        // :398-416
-        const T mj = s[6];
-        const T ci = vij_i * ti, cj = vij_j * tj;
-        const T f = -mj * pstar * (ci + cj);
-        D.au += f * g.xij[0]; D.av += f * g.xij[1]; D.aw += f * g.xij[2];
-        const T edotx = e0 * g.xij[0] + e1 * g.xij[1] + e2 * g.xij[2];
-        D.ae += f * (ustar * edotx);
-        if (a.p.conduction) { // :418-427
-            const T divi = D.div, divj = s[8];
-            const T Hi = a.p.g1 * hi * csi + a.p.g2 * hi * hi * (fabs(divi) - divi);
-            const T Hj = a.p.g1 * hj * csj + a.p.g2 * hj * hj * (fabs(divj) - divj);
-            T Hij = (Hi + Hj) * (D.e - s[7]);
-            Hij /= (T(0.5) * (rhoi + rhoj) * (RIJ * RIJ + g.eps));
-            const T tij = pair_gradfac<KK, UH>(g);
-            D.ae += mj * Hij * (tij * (g.xij[0] * g.xij[0] + g.xij[1] * g.xij[1] + g.xij[2] * g.xij[2]));
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        a.p.au[o] = (double)D.au; a.p.av[o] = (double)D.av; a.p.aw[o] = (double)D.aw; a.p.ae[o] = (double)D.ae;
-    }
-};
-
-// ---- velocity gradient (basic_equations.py:63-148) -------------------------
-template <class T> struct FamVGrad_T {
-    typedef T Real; // arithmetic type of the pair loop
-    static constexpr bool PRED = true; // see FamWCSPH
-    static constexpr uint32_t CF0 = F_VG3; // flag set compiled as a constant (variant 6)
-    static constexpr int MINB = 4; // wavefronts per SIMD the pair kernel is compiled for (VGPR budget)
-    static constexpr int NA = 4; // u v w m/rho
-    static constexpr int NR = 8;
-    struct Params { double *v[9]; };
-    struct Dest { T u, v, w; T g[9]; };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2];
-        for (int k = 0; k < 9; k++) D.g[k] = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        T tg = pair_gradfac<KK, UH>(g);
-        tg = pass ? tg : T(0.0); // PRED
-        const T dw[3] = {tg * g.xij[0], tg * g.xij[1], tg * g.xij[2]};
-        const T tmp = s[3]; // m/rho (divided once per particle by k_pack)
-        const T nv[3] = {-(D.u - s[0]), -(D.v - s[1]), -(D.w - s[2])};
-        const int n = (fl & F_VG3) ? 3 : 2;
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                if (i < n && j < n) D.g[3 * i + j] += tmp * nv[i] * dw[j];
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        const int n = (a.dflags & F_VG3) ? 3 : 2;
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                if (i < n && j < n) a.p.v[3 * i + j][o] = D.g[3 * i + j];
-    }
-};
-typedef FamVGrad_T<double> FamVGrad;
-
-// ---- elastic rates: Continuity + MomentumEquationWithStress +
-//      MonaghanArtificialViscosity + XSPH  (solid_mech/basic.py:245-387,
-//      basic_equations.py:177-300) -------------------------------------------
-template <class T> struct FamElastic_T {
-    typedef T Real; // arithmetic type of the pair loop
-    static constexpr bool PRED = true; // see FamWCSPH
-    static constexpr uint32_t CF0 = F_ECONT | F_ESTRESS | F_EAV | F_EXSPH; // flag set compiled as a constant (variant 6)
-    // wavefronts per SIMD the pair kernel is compiled for (VGPR budget): fp32 120 registers; fp64 215-227, and at 3
-    // (168 registers + 190 B of scratch) the rings take the same 2.99 ms
-    static constexpr int MINB = sizeof(T) == 4 ? 4 : 2;
-    static constexpr int NA = 18; // u v w m rho cs | t00 t01 t02 t11 t12 t22 (= sigma/rho^2) | r00 r01 r02 r11 r12 r22
-    static constexpr int NR = 22;
-    struct Params {
-        T wdeltap, n, alpha, beta, eps;
-        double *arho, *au, *av, *aw, *ax, *ay, *az;
-        const uint32_t *tension; // FamElasticU_T: the source array's "a particle is in tension" word, or null (always gather r_ij)
-    };
-    // The destination's own tensors are NOT live in the pair loop: with S = sum_j m_j DWIJ and F = sum_j m_j f^n DWIJ,
-    //   sum_j m_j ((t_i + t_j) + f^n (r_i + r_j)) . DWIJ = t_i . S + r_i . F + sum_j m_j (t_j + f^n r_j) . DWIJ,
-    // so t_i, r_i (24 registers in fp64) wait in scratch until finish() and the loop carries S and F (12) instead.
-    struct Dest {
-        T u, v, w, rho, cs, t[6], r[6];
-        T arho, au, av, aw, ax, ay, az;
-        T s[3], f[3];
-    };
-    template <class A> static __device__ __forceinline__ void load(Dest &D, const T *a, const A &, uint32_t)
-    {
-        D.u = a[0]; D.v = a[1]; D.w = a[2]; D.rho = a[4]; D.cs = a[5];
-        for (int k = 0; k < 6; k++) { D.t[k] = a[6 + k]; D.r[k] = a[12 + k]; }
-        D.arho = D.au = D.av = D.aw = D.ax = D.ay = D.az = T(0.0);
-        for (int k = 0; k < 3; k++) D.s[k] = D.f[k] = T(0.0);
-    }
-    template <int KK, bool UH, class A>
-    static __device__ __forceinline__ void pair(Dest &D, const real4<T> &pi, const real4<T> &pj, T r2,
-                                                const T (&s)[NA], uint32_t fl, const A &a, bool pass = true)
-    {
-        PairGeomT<T> g;
-        pair_geom<KK, UH>(g, pi, pj, r2, a);
-        T tg = pair_gradfac<KK, UH>(g);
-        tg = pass ? tg : T(0.0); // PRED: terms carry DWIJ, the XSPH one WIJ
-        const T dw0 = tg * g.xij[0], dw1 = tg * g.xij[1], dw2 = tg * g.xij[2];
-        const T vij0 = D.u - s[0], vij1 = D.v - s[1], vij2 = D.w - s[2];
-        const T vdotx = vij0 * g.xij[0] + vij1 * g.xij[1] + vij2 * g.xij[2];
-        const T mj = s[3];
-        if (fl & F_ECONT) D.arho = fma(mj * tg, vdotx, D.arho);
-        T wij = T(0.0);
-        if (fl & (F_ESTRESS | F_EXSPH)) wij = pair_w<KK, UH>(g);
-        wij = pass ? wij : T(0.0);
-        if (fl & F_ESTRESS) { // solid_mech/basic.py:267-387
-            T fab = T(0.0);
-            if (a.p.wdeltap > T(0.)) {
-                const T f = wij * fast_rcp(a.p.wdeltap);
-                if (a.p.n == T(4.0)) { const T f2 = f * f; fab = f2 * f2; }
-                else if (a.p.n == T(2.0)) fab = f * f;
-                else if (a.p.n == T(1.0)) fab = f;
-                else fab = pow(f, a.p.n);
-            }
-            const T m0 = mj * dw0, m1 = mj * dw1, m2 = mj * dw2;
-            D.s[0] += m0; D.s[1] += m1; D.s[2] += m2;
-            D.f[0] = fma(fab, m0, D.f[0]); D.f[1] = fma(fab, m1, D.f[1]); D.f[2] = fma(fab, m2, D.f[2]);
-            const T a00 = fma(fab, s[12], s[6]), a01 = fma(fab, s[13], s[7]), a02 = fma(fab, s[14], s[8]);
-            const T a11 = fma(fab, s[15], s[9]), a12 = fma(fab, s[16], s[10]), a22 = fma(fab, s[17], s[11]);
-            D.au += a00 * m0 + a01 * m1 + a02 * m2;
-            D.av += a01 * m0 + a11 * m1 + a12 * m2;
-            D.aw += a02 * m0 + a12 * m1 + a22 * m2;
-        }
-        if (fl & (F_EAV | F_EXSPH)) {
-            const T rhoij = T(0.5) * (D.rho + s[4]);
-            T rhoij1;
-            if (fl & F_EAV) { // basic_equations.py:236-257
-                const T re = r2 + g.eps;
-                const T tt = fast_rcp(re * rhoij);
-                rhoij1 = re * tt;
-                const T muij = (g.hij * vdotx) * (rhoij * tt);
-                const T cij = T(0.5) * (D.cs + s[5]);
-                T piij = (a.p.beta * muij - a.p.alpha * cij) * muij * rhoij1;
-                piij = vdotx < 0 ? piij : T(0.0);
-                const T f = -mj * piij;
-                D.au = fma(f, dw0, D.au); D.av = fma(f, dw1, D.av); D.aw = fma(f, dw2, D.aw);
-            } else rhoij1 = fast_rcp(rhoij);
-            if (fl & F_EXSPH) { // basic_equations.py:290-295
-                const T tmp = -a.p.eps * mj * wij * rhoij1;
-                D.ax = fma(tmp, vij0, D.ax); D.ay = fma(tmp, vij1, D.ay); D.az = fma(tmp, vij2, D.az);
-            }
-        }
-    }
-    template <class A> static __device__ __forceinline__ void finish(Dest &D, const A &a, uint32_t o)
-    {
-        if (a.dflags & F_ECONT) a.p.arho[o] = D.arho;
-        if (a.dflags & F_ESTRESS) { // the destination's own share of the stress term
-            D.au += D.t[0] * D.s[0] + D.t[1] * D.s[1] + D.t[2] * D.s[2] + D.r[0] * D.f[0] + D.r[1] * D.f[1] + D.r[2] * D.f[2];
-            D.av += D.t[1] * D.s[0] + D.t[3] * D.s[1] + D.t[4] * D.s[2] + D.r[1] * D.f[0] + D.r[3] * D.f[1] + D.r[4] * D.f[2];
-            D.aw += D.t[2] * D.s[0] + D.t[4] * D.s[1] + D.t[5] * D.s[2] + D.r[2] * D.f[0] + D.r[4] * D.f[1] + D.r[5] * D.f[2];
-        }
-        if (a.dflags & (F_ESTRESS | F_EAV)) { a.p.au[o] = D.au; a.p.av[o] = D.av; a.p.aw[o] = D.aw; }
-        if (a.dflags & F_EXSPH) { a.p.ax[o] = D.ax + D.u; a.p.ay[o] = D.ay + D.v; a.p.az[o] = D.az + D.w; }
-    }
-};
-typedef FamElastic_T<double> FamElastic;
-
-// The same terms on records without h and m (uniform h, ONE mass per source array -- seen by the neighbour update's
-// reduction, as for the WCSPH uniform-mass records): [x y | z u | v w | rho cs | t00 t01 | t02 t11 | t12 t22 | r00 r01 |
-// r02 r11 | r12 r22], 160 bytes = ten 16-B pieces instead of eleven; fp32 [x y z u | v w rho cs | t00 t01 t02 t11 |
-// t12 t22 r00 r01 | r02 r11 r12 r22], 80 bytes = five pieces instead of six.
-template <class T> struct FamElasticU_T : FamElastic_T<T> {
-    static constexpr bool EOSF = true;  // own record decoding (load_fused)
-    static constexpr bool TOKEN = true; // wave token: 1 = gather the r_ij, 0 = no particle of the source is in tension (r_ij = 0:
-                                        // MonaghanArtificialStress, solid_mech/basic.py:170-242, leaves them zero under compression)
-    static constexpr int NA = 18;
-    template <class A> static __device__ __forceinline__ uint32_t wave_token(const A &a)
-    {
-        return a.p.tension ? (uint32_t)__builtin_amdgcn_readfirstlane((int)*a.p.tension) : 1u;
-    }
-    // 16-B pieces of one record, and the record decoded from wherever its pieces are (the packed buffer, or the LDS copy
-    // of a row tile: k_pair_rowlds)
-    static constexpr int PIECES = sizeof(T) == 8 ? 10 : 5;
-    static constexpr bool ROWLDS = true;
-    typedef typename std::conditional<sizeof(T) == 8, double2, float4>::type Piece;
-    template <class P> static __device__ __forceinline__ void decode(P p, T mu, real4<T> &pj, T (&s)[18], uint32_t with_r)
-    {
-        if constexpr (sizeof(T) == 8) {
-            double2 q[10];
-#pragma unroll
-            for (int k = 0; k < 7; k++) q[k] = p[k];
-            if (with_r) { q[7] = p[7]; q[8] = p[8]; q[9] = p[9]; }
-            else q[7] = q[8] = q[9] = make_double2(0.0, 0.0);
-            pj.x = q[0].x; pj.y = q[0].y; pj.z = q[1].x; pj.w = 0.0;
-            s[0] = q[1].y; s[1] = q[2].x; s[2] = q[2].y; s[3] = mu; s[4] = q[3].x; s[5] = q[3].y;
-#pragma unroll
-            for (int k = 0; k < 6; k++) { s[6 + 2 * k] = q[4 + k].x; s[7 + 2 * k] = q[4 + k].y; }
-        } else {
-            float4 q[5];
-#pragma unroll
-            for (int k = 0; k < 4; k++) q[k] = p[k];
-            if (with_r) q[4] = p[4];
-            else { q[4] = make_float4(0.f, 0.f, 0.f, 0.f); q[3].z = 0.f; q[3].w = 0.f; }
-            pj.x = q[0].x; pj.y = q[0].y; pj.z = q[0].z; pj.w = 0.f;
-            s[0] = q[0].w; s[1] = q[1].x; s[2] = q[1].y; s[3] = mu; s[4] = q[1].z; s[5] = q[1].w;
-#pragma unroll
-            for (int k = 0; k < 3; k++) { s[6 + 4 * k] = q[2 + k].x; s[7 + 4 * k] = q[2 + k].y; s[8 + 4 * k] = q[2 + k].z; s[9 + 4 * k] = q[2 + k].w; }
-        }
-    }
-    template <class A> static __device__ __forceinline__ void load_fused(const A &a, uint32_t jg, uint32_t, T mu, real4<T> &pj, T (&s)[18],
-                                                                         uint32_t with_r = 1u)
-    {
-        decode(reinterpret_cast<const Piece *>(a.rec) + (unsigned long long)jg * PIECES, mu, pj, s, with_r);
-    }
-};
+#include "sph_fam_wcsph.h"
+#include "sph_fam_tvf.h"
+#include "sph_fam_gas.h"
+#include "sph_fam_elastic.h"
+#include "sph_pack.h"
 
 // ---------------------------------------------------------------------------
 // variant 0: per-lane walk over the 3x3 rows of cells (x-contiguous ranges)
@@ -2781,7 +430,7 @@ static int run_nosrc(sph_ctx *c, const sph_equation &e, size_t start, size_t sto
 }
 
 enum Family { FAM_NONE, FAM_WCSPH, FAM_DENSITY, FAM_TVF, FAM_VGRAD, FAM_ELASTIC, FAM_NBR, FAM_WCSPHX, FAM_DSPRE, FAM_EDAC, FAM_AVGP, FAM_GASSD, FAM_MPM,
-              FAM_GSPHGRAD, FAM_GSPH, FAM_ADKESD, FAM_ADKE, FAM_GASWALL };
+              FAM_GSPHGRAD, FAM_GSPH, FAM_ADKESD, FAM_ADKE, FAM_GASWALL, FAM_COUNT };
 
 static bool is_wcsph_option_kind(int k)
 {
@@ -2869,281 +518,7 @@ static int eq_family(int kind, uint32_t *flag, bool elastic, bool wcsphx = false
     }
 }
 
-struct PackPlan {
-    int nr; // doubles per interleaved record (== Fam::NR)
-    int na;
-    int props[MAX_AUX]; // sph_prop or -1
-    int derived;
-};
-
-static PackPlan pack_plan(int fam)
-{
-    PackPlan p;
-    for (auto &v : p.props) v = -1;
-    p.derived = 0;
-    if (fam == FAM_WCSPH) {
-        p.nr = FamWCSPH::NR;
-        p.na = 8;
-        int pr[8] = {SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO, -1, SPH_CS, SPH_P};
-        for (int k = 0; k < 8; k++) p.props[k] = pr[k];
-        p.derived = 1;
-    } else if (fam == FAM_WCSPHX) { // the WCSPH slots; with a delta-SPH continuity term (sph_eval_group) + gradrho
-        p.nr = 12;
-        p.na = 8;
-        int pr[8] = {SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO, -1, SPH_CS, SPH_P};
-        for (int k = 0; k < 8; k++) p.props[k] = pr[k];
-        p.derived = 1;
-    } else if (fam == FAM_DSPRE) {
-        p.nr = 6;
-        p.na = 2;
-        p.props[0] = SPH_M; p.props[1] = SPH_RHO;
-    } else if (fam == FAM_DENSITY) {
-        p.nr = FamDensity::NR;
-        p.na = 1;
-        p.props[0] = SPH_M;
-    } else if (fam == FAM_AVGP) {
-        p.nr = 6;
-        p.na = 2;
-        p.props[0] = SPH_M; p.props[1] = SPH_P;
-    } else if (fam == FAM_GASSD || fam == FAM_ADKESD) {
-        p.nr = 8;
-        p.na = 4;
-        int pr[4] = {SPH_M, SPH_U, SPH_V, SPH_W};
-        for (int k = 0; k < 4; k++) p.props[k] = pr[k];
-    } else if (fam == FAM_MPM) { // omega, alpha1, alpha2: user properties by name (run_mpm refuses the launch should the slots have run out)
-        p.nr = 16;
-        p.na = 12;
-        int pr[12] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_E, SPH_M, sph_prop_register("omega"),
-                      sph_prop_register("alpha1"), sph_prop_register("alpha2"), -1};
-        for (int k = 0; k < 12; k++) p.props[k] = pr[k];
-    } else if (fam == FAM_ADKE || fam == FAM_GASWALL) { // div: a user property by name (the binders refuse the launch should the slots have run out)
-        p.nr = 14;
-        p.na = 9;
-        int pr[9] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_E, SPH_M, sph_prop_register("div")};
-        for (int k = 0; k < 9; k++) p.props[k] = pr[k];
-    } else if (fam == FAM_GSPHGRAD) { // [p u v w m/rho]
-        p.nr = 10;
-        p.na = 5;
-        int pr[6] = {SPH_P, SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO};
-        for (int k = 0; k < 6; k++) p.props[k] = pr[k];
-        p.derived = 7;
-    } else if (fam == FAM_GSPH) { // the gradients: user properties by name (run_gsph refuses the launch should the slots have run out)
-        p.nr = 26;
-        p.na = 21;
-        static const char *un[16] = {"div", "grhox", "grhoy", "grhoz", "px", "py", "pz", "ux", "uy", "uz", "vx", "vy", "vz", "wx", "wy", "wz"};
-        int pr[8] = {SPH_U, SPH_V, SPH_W, SPH_RHO, SPH_P, SPH_CS, SPH_M, SPH_E};
-        for (int k = 0; k < 8; k++) p.props[k] = pr[k];
-        for (int k = 0; k < 16; k++) p.props[8 + k] = sph_prop_register(un[k]);
-        p.derived = 6;
-    } else if (fam == FAM_NBR) {
-        p.nr = FamNbr::NR;
-        p.na = 1;
-        p.derived = 5; // aux[0] = the particle's original index
-    } else if (fam == FAM_VGRAD) {
-        p.nr = FamVGrad::NR;
-        p.na = 4;
-        int pr[5] = {SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO};
-        for (int k = 0; k < 5; k++) p.props[k] = pr[k];
-        p.derived = 4;
-    } else if (fam == FAM_ELASTIC) {
-        p.nr = FamElastic::NR;
-        p.na = 18;
-        int pr[19] = {SPH_U, SPH_V, SPH_W, SPH_M, SPH_RHO, SPH_CS, SPH_S00, SPH_S01, SPH_S02, SPH_S11, SPH_S12, SPH_S22,
-                      SPH_R00, SPH_R01, SPH_R02, SPH_R11, SPH_R12, SPH_R22, SPH_P};
-        for (int k = 0; k < 19; k++) p.props[k] = pr[k];
-        p.derived = 3;
-    } else { // FAM_TVF and FAM_EDAC
-        p.nr = FamTVF::NR;
-        p.na = 12;
-        int pr[12] = {SPH_U, SPH_V, SPH_W, SPH_UHAT, SPH_VHAT, SPH_WHAT, SPH_RHO, SPH_P, SPH_VOL, SPH_M, -1, -1};
-        for (int k = 0; k < 12; k++) p.props[k] = pr[k];
-        p.derived = 2;
-    }
-    return p;
-}
-
-// The packed records of one (destination, sources) block.  choose_records decides them for a destination of
-// sph_eval_group; the callers that are fp64 by contract (neighbour lists, the interpolator) start from RecordLayout(fam),
-// whatever the options say.  pack_array, the pack cache, fill_common and the choice of the family instantiation read the
-// decision from here and from nowhere else.
-enum RecordKind {
-    REC_PLAIN, // the family's own records (PackPlan; compact under uniform h where pack_layout has a layout for them)
-    REC_EOSF,  // 64-byte WCSPH records, uniform h: p and cs recomputed per record (sph_group.src_eos)
-    REC_EOSV,  // 64-byte WCSPH records with variable h [x y z h u v w rho], one mass per source array
-    REC_TVFF,  // state-fused TVF records: p and V recomputed from rho
-    REC_ELU,   // elastic-rates records without h and m (uniform h, one mass per source array)
-};
-struct RecordLayout {
-    PackPlan pl;             // nr: doubles per record (floats with record_f32 / arith_f32)
-    bool record_f32 = false; // the precision, as the options of these names: fp32 records read by fp64 arithmetic ...
-    bool arith_f32 = false;  // ... fp32 records, arithmetic and accumulators
-    RecordKind kind = REC_PLAIN;
-    bool umass = false;      // REC_EOSF: p / rho^2 in the mass slot (every source array has one mass)
-    bool eos_abs = false;    // REC_EOSF / REC_EOSV: the pack computes the Tait EOS that has not run (PackArgs::eos_abs) ...
-    double eos_par[4] = {};  // ... with these parameters: rho0 c0 gamma p0
-    explicit RecordLayout(int fam) : pl(pack_plan(fam)) {}
-    bool eos_fused() const { return kind == REC_EOSF || kind == REC_EOSV; }
-    // what the pack cache compares: records packed under another signature cannot be reused
-    int sig() const
-    {
-        return pl.nr * 32 + (record_f32 ? 1 : 0) + (arith_f32 ? 2 : 0) + (kind == REC_EOSF ? 4 : 0) + (umass ? 8 : 0) +
-               (kind == REC_TVFF || kind == REC_ELU || kind == REC_EOSV ? 16 : 0);
-    }
-};
-
-// PackArgs::layout of these records
-static int pack_layout(const RecordLayout &rl, int fam, bool wave)
-{
-    static const int special[] = {0, 6, 12, 8, 10}; // by RecordKind, in fp64; the fp32 form of each is the next number
-    if (rl.kind != REC_PLAIN) return special[rl.kind] + (rl.arith_f32 ? 1 : 0);
-    if (!wave) return 0;
-    if (rl.record_f32 || rl.arith_f32) return 5;
-    if (fam == FAM_WCSPH) return 1;
-    if ((fam == FAM_DENSITY || fam == FAM_NBR) && rl.pl.nr == 4) return 2;
-    if ((fam == FAM_TVF || fam == FAM_EDAC) && (rl.pl.nr == 14 || rl.pl.nr == 12)) return 3;
-    return 0;
-}
-
-// which aux slots a family really needs given the union of flags (others may be absent -> 0)
-static bool slot_required(int fam, uint32_t flags, int prop)
-{
-    if (fam == FAM_WCSPH) {
-        if (prop == SPH_M || prop == SPH_U || prop == SPH_V || prop == SPH_W) return true;
-        if (prop == SPH_RHO) return flags & (F_MOM | F_XSPH);
-        if (prop == SPH_P || prop == SPH_CS) return flags & F_MOM;
-        return false;
-    }
-    if (fam == FAM_WCSPHX) {
-        if (prop == SPH_M || prop == SPH_U || prop == SPH_V || prop == SPH_W || prop == SPH_RHO) return true;
-        if (prop == SPH_P || prop == SPH_CS) return flags & F_MOM;
-        return flags & F_DCONT; // SPH_GRADRHO0..2
-    }
-    if (fam == FAM_DSPRE) return true;
-    if (fam == FAM_DENSITY) return prop == SPH_M;
-    if (fam == FAM_NBR) return false;
-    if (fam == FAM_VGRAD) return true;
-    if (fam == FAM_ELASTIC) {
-        if (prop == SPH_U || prop == SPH_V || prop == SPH_W || prop == SPH_M) return true;
-        if (prop == SPH_RHO) return flags & (F_ESTRESS | F_EAV | F_EXSPH);
-        if (prop == SPH_CS) return flags & F_EAV;
-        if (prop == SPH_P) return flags & F_ESTRESS;
-        if (prop >= SPH_S00 && prop <= SPH_S22) return flags & F_ESTRESS;
-        return false; // r_ij default to 0 when absent
-    }
-    if (fam == FAM_TVF || fam == FAM_EDAC) {
-        if (prop == SPH_UHAT || prop == SPH_VHAT || prop == SPH_WHAT) return flags & F_TAS;
-        return true;
-    }
-    if (fam == FAM_AVGP) return prop == SPH_M ? (flags & (F_SD | F_TVFSD)) != 0 : (flags & F_AVGP) != 0;
-    if (fam == FAM_GASSD || fam == FAM_MPM || fam == FAM_GSPHGRAD || fam == FAM_GSPH) return true;
-    if (fam == FAM_ADKESD || fam == FAM_ADKE || fam == FAM_GASWALL) return true;
-    return false;
-}
-
-// 16-B pieces of one packed record, as k_pack counts them; 0: records that are not a whole number of
-// pieces (no LDS transposition, per-lane stores)
-static int pack_pieces(const PackArgs &pa)
-{
-    if (!pa.rec) return 0;
-    // values per piece: four floats (layout 5 and the odd ones of 7 .. 13) or two doubles
-    const int per = (pa.layout == 5 || (pa.layout >= 7 && pa.layout <= 13 && (pa.layout & 1))) ? 4 : 2;
-    return (pa.nr % per) ? 0 : pa.nr / per;
-}
-
-// `launch` false: validate only (the records of this array are already in the packed buffer, see
-// the pack cache in sph_eval_group)
-// k_pack with the layout as a compile-time constant where the library has an instantiation
-static void launch_pack(sph_ctx *c, const PackArgs &pa, size_t n)
-{
-    const dim3 g(div_up(n, 256)), b(256);
-    const size_t lds = (size_t)pa.lds_np * 256 * 16;
-    switch (pa.rec ? pa.layout : -1) {
-    case 2: hipLaunchKernelGGL(k_pack<2>, g, b, lds, c->stream, pa); break;
-    case 3: hipLaunchKernelGGL(k_pack<3>, g, b, lds, c->stream, pa); break;
-    case 8: hipLaunchKernelGGL(k_pack<8>, g, b, lds, c->stream, pa); break;
-    case 9: hipLaunchKernelGGL(k_pack<9>, g, b, lds, c->stream, pa); break;
-    case 6: hipLaunchKernelGGL(k_pack<6>, g, b, lds, c->stream, pa); break;
-    case 7: hipLaunchKernelGGL(k_pack<7>, g, b, lds, c->stream, pa); break;
-    case 10: hipLaunchKernelGGL(k_pack<10>, g, b, lds, c->stream, pa); break;
-    case 11: hipLaunchKernelGGL(k_pack<11>, g, b, lds, c->stream, pa); break;
-    case 12: hipLaunchKernelGGL(k_pack<12>, g, b, lds, c->stream, pa); break;
-    case 13: hipLaunchKernelGGL(k_pack<13>, g, b, lds, c->stream, pa); break;
-    default: hipLaunchKernelGGL(k_pack<-1>, g, b, lds, c->stream, pa); break;
-    }
-}
-
-static int pack_array(sph_ctx *c, int id, size_t off, const RecordLayout &rl, int fam, uint32_t flags, bool dest_only = false,
-                      bool launch = true, int seg = 0)
-{
-    DevArray &A = c->arr[id];
-    const PackPlan &pl = rl.pl;
-    // seg 0: the particles sph_nnps_update binned, through their cell order; seg 1: the ghosts binned after it
-    // (sph_nnps_update_ghosts), through theirs, behind the first segment's records
-    const size_t nseg = seg ? A.g_n : A.n_binned;
-    if (nseg == 0) return SPH_OK;
-    PackArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.perm = seg ? A.g_perm.as<uint32_t>() : A.perm.as<uint32_t>();
-    pa.n = nseg;
-    pa.off = off + (seg ? A.n_binned : 0);
-    pa.x = A.prop[SPH_X]; pa.y = A.prop[SPH_Y]; pa.z = A.prop[SPH_Z]; pa.h = A.prop[SPH_H];
-    pa.na = pl.na;
-    for (int k = 0; k < MAX_AUX; k++) {
-        if ((k < pl.na || (pl.derived == 3 && k == 18) || (pl.derived == 4 && k == 4) || (pl.derived == 6 && k < 24) ||
-             (pl.derived == 7 && k == 5)) && pl.props[k] >= 0) {
-            pa.src[k] = A.prop[pl.props[k]];
-            // a destination that is not among the sources is only read through Fam::load:
-            // it does not need a mass unless the equation uses the destination's own
-            // (transport_velocity.SummationDensity: rho_i = m_i sum W)
-            const bool mass_free = dest_only && pl.props[k] == SPH_M &&
-                                   (fam == FAM_WCSPH || fam == FAM_WCSPHX || (fam == FAM_DENSITY && !(flags & F_TVFSD)));
-            if (!pa.src[k] && !mass_free && slot_required(fam, flags, pl.props[k])) return need_prop(c, id, pl.props[k], "pair loop");
-        }
-    }
-    pa.derived = pl.derived;
-    pa.posh = c->posh.as<double4>();
-    pa.aux = c->aux.as<double>();
-    pa.rec = wave_tiles(c) ? c->posh.as<double>() : nullptr;
-    pa.nr = pl.nr;
-    pa.fpos = wave_tiles(c) ? c->fposb.as<float4>() : nullptr;
-    for (int k = 0; k < 3; k++) pa.gmin[k] = c->xmin[k];
-    pa.radius_scale = c->radius_scale;
-    pa.layout = pack_layout(rl, fam, wave_tiles(c));
-    if (rl.kind == REC_EOSF) {
-        // p, cs (and p / rho^2) are recomputed by the pair kernel: not read here
-        pa.src[5] = pa.src[6] = nullptr;
-        if (rl.umass) { // ... except p / rho^2, which takes the place of the (uniform) mass: derived 1 reads p
-            pa.umass = 1;
-            pa.src[3] = nullptr; // the record holds no mass
-        } else {
-            pa.src[7] = nullptr;
-            pa.derived = 0;
-        }
-        // ... and no h: the prefilter's radius_scale * h from the launch constant of the pair kernel (fill_common: hu)
-        pa.h = nullptr;
-        pa.hu = 0.5 * (c->h_uniform + c->h_uniform);
-    }
-    // REC_ELU: h and m are launch / source constants
-    if (rl.kind == REC_EOSV) { // p, cs, p / rho^2 recomputed, m a source constant: none of them read here
-        pa.src[3] = pa.src[5] = pa.src[6] = pa.src[7] = nullptr;
-        pa.derived = 0;
-    }
-    if (rl.kind == REC_TVFF) { // p and V are functions of rho (and the one mass): not read here
-        pa.src[7] = pa.src[8] = pa.src[9] = nullptr;
-        pa.derived = 0;
-    }
-    if (rl.eos_abs) { // the Tait EOS of this array has not run: p and cs leave from here
-        pa.eos_abs = 1;
-        for (int k = 0; k < 4; k++) pa.eos_par[k] = rl.eos_par[k];
-        pa.p_out = A.prop[SPH_P];
-        pa.cs_out = A.prop[SPH_CS];
-        pa.src[7] = nullptr; // p is computed, not read
-    }
-    pa.lds_np = pack_pieces(pa);
-    if ((size_t)pa.lds_np * 256 * 16 > 48 * 1024) pa.lds_np = 0; // the widest records (GSPH, 13 pieces) leave per lane
-    if (launch) launch_pack(c, pa, nseg);
-    return SPH_OK;
-}
+#include "sph_pack_plan.h" // PackPlan .. pack_array, pack_generic
 
 #endif // SPH_PRIMARY_UNIT
 
@@ -3380,7 +755,7 @@ int nnps_csr_pair_kernel(sph_ctx *c, int src, int dst, uint32_t *count, const ui
     const size_t total = S.n + (dest_is_src ? 0 : D.n);
     if (total >= (1ull << 32)) { sph_set_error("too many particles for 32-bit packed indices"); return SPH_ERR_ARG; }
     RecordLayout rl(FAM_NBR); // lists are exact: fp64 records, whatever the options say
-    if (uh) rl.pl.nr = 4;
+    if (uh) rl.pl.nr = FamNbr::NR_COMPACT;
     for (auto &pc : c->pack_cache) pc.epoch = 0;
     SPH_TRY(c->posh.reserve((total + 64) * sizeof(double) * rl.pl.nr));
     SPH_TRY(c->aux.reserve(64));
@@ -3810,20 +1185,20 @@ static RecordLayout choose_records(sph_ctx *c, const sph_group *g, const DestPla
     rl.arith_f32 = c->arith_f32 != 0;
     if (fam == FAM_WCSPHX && (dflags & F_DCONT)) { // the records carry the sources' gradrho
         for (int k = 0; k < 3; k++) pl.props[8 + k] = SPH_GRADRHO0 + k;
-        pl.na = 11; pl.nr = 16;
+        pl.na = FamWCSPHX_T<double, true>::NA; pl.nr = FamWCSPHX_T<double, true>::NR;
     }
     // compact 80-B WCSPH records when neither h nor p of a neighbour is read
-    if (wave && fam == FAM_WCSPH && uh && !(dflags & F_TENSILE)) pl.nr = c->wcsph_nr ? (int)c->wcsph_nr : 10;
-    if (wave && fam == FAM_DENSITY && uh) pl.nr = 4;
-    if (wave && fam == FAM_TVF && uh) pl.nr = (dflags & F_TAV) ? 14 : 12;
-    if (wave && fam == FAM_EDAC && uh) pl.nr = 14; // (m always: load_record_edac)
+    if (wave && fam == FAM_WCSPH && uh && !(dflags & F_TENSILE)) pl.nr = c->wcsph_nr ? (int)c->wcsph_nr : FamWCSPH::NR_COMPACT;
+    if (wave && fam == FAM_DENSITY && uh) pl.nr = FamDensity::NR_COMPACT;
+    if (wave && fam == FAM_TVF && uh) pl.nr = (dflags & F_TAV) ? FamTVF::NR_COMPACT_M : FamTVF::NR_COMPACT;
+    if (wave && fam == FAM_EDAC && uh) pl.nr = FamEDAC_T<double, true>::NR_COMPACT; // (m always: load_record_edac)
     if (wave && (rl.record_f32 || rl.arith_f32)) pl.nr = (4 + pl.na + 3) & ~3; // floats
     // The caller promised (sph_group.src_eos) that p, cs of every array read here are the Tait EOS of its
     // rho: with gamma = 7 (powers by multiplication), uniform h and no tensile correction the pair kernel
     // recomputes them and the records shrink to 64 bytes (32 in fp32).
     const bool eosf = g->src_eos == 1 && c->eos_fuse && fam == FAM_WCSPH && wave && uh && !(dflags & F_TENSILE) &&
                       tait_gk(g->eos_par[2]) >= 0 && g->eos_par[0] > 0.0 && !rl.record_f32 && !c->wcsph_nr;
-    if (eosf) pl.nr = 8; // doubles, or floats with arith_f32
+    if (eosf) pl.nr = FamWCSPHE_T<double>::NR; // doubles, or floats with arith_f32
     // ... and when every array read here had ONE mass at the last neighbour update, the record's mass slot
     // carries p / rho^2 and most of the per-record EOS goes as well (FamWCSPHE_T<T, true>)
     // (only with the equation flags as a compile-time constant: the run-time-flag kernel of a dam break's three
@@ -3837,7 +1212,7 @@ static RecordLayout choose_records(sph_ctx *c, const sph_group *g, const DestPla
                 !(dflags & F_TENSILE) && tait_gk(g->eos_par[2]) == 3 && g->eos_par[0] > 0.0 && !rl.record_f32 && !c->wcsph_nr;
     if (eosv) c->want_mrange = true;
     for (int j = 0; j < nsrcs && eosv; j++) eosv = c->arr[P.srcs[j]].m_known;
-    if (eosv) pl.nr = 8;
+    if (eosv) pl.nr = FamWCSPHV_T<double>::NR;
     // TVF force pass after StateEquation + density summation (sph_group.src_eos = 2): p and V leave the records
     // when every array read here has ONE mass (V = rho / m)
     bool tvff = g->src_eos == 2 && c->eos_fuse && c->mass_fuse && fam == FAM_TVF && wave && uh && !rl.record_f32 &&
@@ -3845,12 +1220,12 @@ static RecordLayout choose_records(sph_ctx *c, const sph_group *g, const DestPla
     if (tvff) c->want_mrange = true;
     for (int j = 0; j < nsrcs && tvff; j++) tvff = c->arr[P.srcs[j]].m_known;
     if (tvff && !P.dest_is_src) tvff = D.m_known;
-    if (tvff) pl.nr = rl.arith_f32 ? ((dflags & F_TAS) ? 12 : 8) : ((dflags & F_TAS) ? 10 : 8);
+    if (tvff) pl.nr = !(dflags & F_TAS) ? FamTVFE_T<double>::NR_FUSED : rl.arith_f32 ? FamTVFE_T<float>::NR_FUSED_AS : FamTVFE_T<double>::NR_FUSED_AS;
     // elastic rates: uniform h and ONE mass per source array -> neither travels in the records
     bool elu = fam == FAM_ELASTIC && c->mass_fuse && wave && uh && !rl.record_f32;
     if (elu) c->want_mrange = true;
     for (int j = 0; j < nsrcs && elu; j++) elu = c->arr[P.srcs[j]].m_known;
-    if (elu) pl.nr = 20; // doubles, or floats with arith_f32
+    if (elu) pl.nr = FamElasticU_T<double>::NR_U; // doubles, or floats with arith_f32
     rl.kind = eosf ? REC_EOSF : eosv ? REC_EOSV : tvff ? REC_TVFF : elu ? REC_ELU : REC_PLAIN; // (one family each: exclusive)
     rl.umass = umass;
     // The pending Tait EOS is absorbed by the records when they are the EOS-fused ones of ONE array and the pack
@@ -4522,34 +1897,6 @@ extern "C" int sph_gsph_failures(sph_ctx *c, unsigned long long *count)
 // records with the properties the generated bodies read, then call the
 // module's launch function with plain pointers.
 // ---------------------------------------------------------------------------
-static int pack_generic(sph_ctx *c, int id, size_t off, int nprops, const int *props, int nr, int layout)
-{
-    DevArray &A = c->arr[id];
-    if (A.n == 0) return SPH_OK;
-    PackArgs pa;
-    memset(&pa, 0, sizeof pa);
-    pa.perm = A.perm.as<uint32_t>();
-    pa.n = A.n;
-    pa.off = off;
-    pa.x = A.prop[SPH_X]; pa.y = A.prop[SPH_Y]; pa.z = A.prop[SPH_Z]; pa.h = A.prop[SPH_H];
-    pa.na = nprops;
-    for (int k = 0; k < nprops; k++) {
-        pa.src[k] = A.prop[props[k]];
-        if (!pa.src[k]) return need_prop(c, id, props[k], "generated pair loop");
-    }
-    pa.posh = c->posh.as<double4>();
-    pa.aux = c->aux.as<double>();
-    pa.rec = c->posh.as<double>();
-    pa.nr = nr;
-    pa.layout = layout;
-    pa.fpos = c->fposb.as<float4>();
-    for (int k = 0; k < 3; k++) pa.gmin[k] = c->xmin[k];
-    pa.radius_scale = c->radius_scale;
-    pa.lds_np = pack_pieces(pa);
-    launch_pack(c, pa, A.n);
-    return SPH_OK;
-}
-
 // the loop nest of one generated family; sph_eval_generated wraps it with the
 // round trip of the equation attributes the device code assigns
 static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_gen_family *f, double t, double dt, double *d_state);
@@ -4711,7 +2058,7 @@ static int eval_generated_launches(sph_ctx *c, const sph_kernel *K, const sph_ge
             const bool rf32 = c->record_f32 || a32;
             const int nr = rf32 ? ((4 + na_fam + 3) & ~3) /* floats */
                          : compact ? ((3 + na + 1) & ~1) : 4 + ((na + 1) & ~1);
-            const int layout = rf32 ? 5 : (compact ? 4 : 0);
+            const int layout = rf32 ? PL_F32 : (compact ? PL_GEN_UH : PL_PLAIN);
             q.rec_f32 = rf32 ? 1 : 0;
             SPH_TRY(c->posh.reserve((total + 64) * sizeof(double) * nr));
             for (auto &pc : c->pack_cache) pc.epoch = 0; // the generated family's records overwrite the shared WCSPH slots

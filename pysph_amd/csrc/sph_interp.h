@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void k_interp_vol(const double *__restrict__ m
     if (i < n) out[i] = m[i] / rho[i];
 }
 
-// records [x y z h | src[0..na-1] pad] of one array through its cell order (k_pack, layout 0); a null source is 0
+// records [x y z h | src[0..na-1] pad] of one array through its cell order (k_pack, PL_PLAIN); a null source is 0
 static int interp_pack(sph_ctx *c, int id, size_t off, int na, const double *const *src, int nr)
 {
     DevArray &A = c->arr[id];
@@ -235,7 +235,7 @@ static int interp_pack(sph_ctx *c, int id, size_t off, int na, const double *con
     pa.aux = c->aux.as<double>();
     pa.rec = c->posh.as<double>();
     pa.nr = nr;
-    pa.layout = 0;
+    pa.layout = PL_PLAIN;
     pa.fpos = c->fposb.as<float4>();
     for (int k = 0; k < 3; k++) pa.gmin[k] = c->xmin[k];
     pa.radius_scale = c->radius_scale;
@@ -330,7 +330,7 @@ extern "C" int sph_interpolate(sph_ctx *c, const sph_kernel *K, int method, int 
             // SummationDensity(dest = every source, sources = all of them, real = False) with the library's density
             // kernel into private buffers: the sources' own rho stays what it is
             RecordLayout rl(FAM_DENSITY);
-            if (c->uniform_h && c->use_uniform_h) rl.pl.nr = 4;
+            if (c->uniform_h && c->use_uniform_h) rl.pl.nr = FamDensity::NR_COMPACT;
             {
                 ScopedTimer tm(c, T_PACK);
                 for (int j = 0; j < nsrc; j++) SPH_TRY(pack_array(c, srcs[j], off_of[j], rl, FAM_DENSITY, F_SD, false, true, 0));

@@ -10,7 +10,7 @@ damped artificial compressibility for SPH", Computers & Fluids 179 (2019) 579):
 * the fluid equations ``ComputeAveragePressure`` (:62-79), ``MomentumEquation``
   (:301-351), ``MomentumEquationPressureGradient`` (:389-488) and ``EDACEquation``
   (:354-386) are parameter holders: their bodies are the hand-written families
-  ``FamEDAC_T`` / ``FamAvgP_T`` of csrc/sph_eval.hip (DESIGN.md, section EDAC).
+  ``FamEDAC_T`` / ``FamAvgP_T`` of csrc/sph_fam_tvf.h (DESIGN.md, section EDAC).
   ``MomentumEquation`` and ``MomentumEquationPressureGradient`` share their names
   with the WCSPH / TVF classes; ``equations.resolve_equation`` tells them apart by
   the module name (``'edac' in type(eq).__module__``), for these classes and for

@@ -6,7 +6,7 @@ Mirrors the interface of pysph/sph/gas_dynamics/basic.py and ``GasDScheme`` of p
 * the equation classes ``SummationDensity`` (basic.py:74-219), ``IdealGasEOS`` (:222-230), ``MPMAccelerations``
   (:356-483), ``ScaleSmoothingLength`` (:13-19) and ``UpdateSmoothingLengthFromVolume`` (:22-29) are parameter
   holders with the reference's constructor signatures and defaults: their bodies are the hand-written families
-  ``FamGasSD_T`` / ``FamMPM_T`` and three cases of ``k_nosrc`` in csrc/sph_eval.hip.
+  ``FamGasSD_T`` / ``FamMPM_T`` (csrc/sph_fam_gas.h) and three cases of ``k_nosrc`` in csrc/sph_eval.hip.
   ``SummationDensity`` is the third class of that name next to basic_equations' and transport_velocity's;
   ``equations.resolve_equation`` finds it by the module name (``'gas_dynamics' in type(eq).__module__``), for this
   class and for the reference's own;

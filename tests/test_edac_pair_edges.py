@@ -1,4 +1,4 @@
-"""The EDAC force family and the average pressure (``FamEDAC_T<T, INT>``, ``FamAvgP_T``, pysph_amd/csrc/sph_eval.hip), one
+"""The EDAC force family and the average pressure (``FamEDAC_T<T, INT>``, ``FamAvgP_T``, pysph_amd/csrc/sph_fam_tvf.h), one
 isolated cluster at a time, against the reference's own classes evaluated at 50 digits (tests/golden/edac_pair_edges.npz,
 made by tests/golden/make_edac_pair_golden.py with the machinery of make_gasd_pair_golden.py; the tests read nothing
 but that file).

@@ -1,5 +1,5 @@
 """The five gas-dynamics pair families (``FamGasSD_T``, ``FamMPM_T``, ``FamADKESD_T``, ``FamADKE_T``, ``FamGasWall_T``,
-pysph_amd/csrc/sph_eval.hip), one isolated cluster at a time, against the reference's own classes evaluated at 50 digits
+pysph_amd/csrc/sph_fam_gas.h), one isolated cluster at a time, against the reference's own classes evaluated at 50 digits
 (tests/golden/gasd_pair_edges.npz, made by tests/golden/make_gasd_pair_golden.py; the tests read nothing but that file).
 
 Every table is a row of isolated pairs and triples, 1 apart, and runs ONE equation alone in one Group, one sweep (the

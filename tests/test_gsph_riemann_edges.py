@@ -1,4 +1,4 @@
-"""The GSPH Riemann solvers and the state reconstruction of the force sweep (``FamGSPH_T``, pysph_amd/csrc/sph_eval.hip), one
+"""The GSPH Riemann solvers and the state reconstruction of the force sweep (``FamGSPH_T``, pysph_amd/csrc/sph_fam_gas.h), one
 pair at a time, against the reference's own solver text evaluated at 50 digits (tests/golden/gsph_riemann_edges.npz, made
 by tests/golden/make_gsph_riemann_golden.py; the tests read nothing but that file).
 

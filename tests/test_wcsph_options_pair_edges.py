@@ -1,5 +1,5 @@
 """The delta-SPH / laminar-viscosity rates and the delta-SPH pre-passes (``FamWCSPHX_T<T, DS>``, ``FamDSPre_T``,
-pysph_amd/csrc/sph_eval.hip), one isolated cluster at a time, against the reference's own classes evaluated at 50 digits
+pysph_amd/csrc/sph_fam_wcsph.h), one isolated cluster at a time, against the reference's own classes evaluated at 50 digits
 (tests/golden/wcsph_options_pair_edges.npz, made by tests/golden/make_wcsph_options_pair_golden.py on the group sweep
 of make_edac_pair_golden.py; the tests read nothing but that file).  Layout, scale and bound rule: those of
 tests/test_edac_pair_edges.py -- a well-conditioned element (K_ref <= 64, the 50-digit run on the double run's lines,
