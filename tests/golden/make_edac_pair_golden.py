@@ -354,6 +354,13 @@ def gsweep(table, N, classes=None, params=None, scale_cols=None, no_self=False, 
             same = all(all(float(P._val(a)) == float(b) for a, b in zip(A[name][c], table['arrays'][name][c]))
                        for name in A for c in A[name] if not (name == dest and c in bases))
             assert same, (table['key'], 'the reference wrote an input column')
+        if mpmode and 'scales' in table:     # a family whose kernel associates a sum differently states the scale of that sum
+            net = dict((c, list(v)) for c, v in Sout.items())
+            table['scales'](table, Sout, recs)
+            # a stated scale is the sum of |product| where the net one is the sum of |increment|: never below it (up to
+            # the float32 it is stored in), and a column nothing states stays as it was
+            assert set(Sout) == set(net) and all(len(Sout[c]) == len(net[c]) for c in net), table['key']
+            assert all(a >= b * (1 - mp.mpf(2) ** -20) for c in net for a, b in zip(Sout[c], net[c])), (table['key'], 'a stated scale below the net-increment scale')
         return dict(cols=cols, S=Sout if mpmode else None, recs=recs, raised=raised)
     finally:
         N.unbind()
